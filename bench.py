@@ -10,7 +10,9 @@ fused into the head convs -> confidence filter -> per-class greedy NMS) and `Sha
 (yolo_v3_amd/dist.py: the same per-rank pipeline + the ONE all-gather of the [B_local, cap+1, 7] payload -- boxes plus a
 row with candidate / kept counts and the kernels' status word -- over RCCL; it is what `detect_sharded` runs), then
 the result is copied to pinned host memory asynchronously.  The list conversion (`assemble`, the path's one host sync)
-is outside the timed region and runs once after it (it also checks the status word).
+is outside the timed region and runs once after it (it also checks the status word).  `--dump-outputs DIR` then writes what
+the last timed step computed (final boxes, counts, a fixed sample of the decoded detections) as .npy files: weights and scenes are
+seeded, so two builds run with the same arguments can be compared output for output (`dump_outputs`).
 
 Launch: `python bench.py --gpus N` with N > 1 and no torchrun environment RE-LAUNCHES ITSELF under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` (one rank per GPU) and
@@ -114,7 +116,9 @@ def relaunch_under_torchrun(n, dry):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n),
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execvpe(sys.executable, cmd, env)
+    # a fresh child process, not exec: this process may already have initialised the GPU runtime (device count above)
+    import subprocess
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 def barrier(dev=None):
@@ -257,6 +261,17 @@ class Workload:
         self.det.engine.raise_if_overflowed(self.det.plan, int(self.det.plan.flags.item()))
         c = self.host_counts
         return c[:4].tolist(), c[self.B:self.B + 4].tolist()
+
+    def last_outputs(self):
+        """After `run` (it ends in a synchronise): (boxes, counts [B, 2], detections) of the LAST timed step -- the boxes and counts the
+        caller of the timed entry receives (world 1: the host copies of `Detector.run_device`'s result; world > 1: the gathered payload
+        of all ranks) and this rank's decoded detections."""
+        if self.sd is not None:
+            from yolo_v3_amd import dist as ydist
+            boxes, meta = ydist.unpack_payload(self.gathered)
+            return boxes, meta[:, :2], self.det.dets
+        c = self.host_counts
+        return self.host, torch.stack((c[:self.B], c[self.B:]), 1), self.det.dets
 
     def stages_ms(self):
         order = ["start"] + [s for s in STAGES] + (["gather"] if self.sd is not None else []) + ["d2h"]
@@ -619,6 +634,41 @@ def write_full(out, args):
         return None
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6       # --dump-outputs: all files together (64 MB)
+DUMP_SAMPLE_SEED = 0                 # fixed row sample of the decoded detections
+
+
+def dump_outputs(d, boxes, counts, dets):
+    """--dump-outputs DIR: what the timed path computed in its last step, as .npy files, so that two builds run with the same
+    arguments (hence the same seeded weights and scenes) can be compared output for output.  Tensors in (any device):
+      boxes [B, cap, 7] fp32 (the final boxes), counts [B, 2] (candidates, kept per image), dets [B, N, A] fp32 (the decoded detections
+      the filter / NMS read).  Files out:
+      boxes.npy              float32 [B, cap, 7]  rows past an image's kept count are zeroed (they are not part of the result)
+      counts.npy             float64 [B, 2]       candidates, kept
+      detections_sample.npy  float32 [B, R, A]    the same R rows of every image (seeded sample, sorted; all rows when they fit)
+      detection_rows.npy     float64 [R]          ... their row indices
+    Together at most DUMP_LIMIT_BYTES.  Returns {name: bytes}."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    counts = counts.cpu().to(torch.float64).numpy()
+    kept = counts[:, 1].astype(np.int64)
+    bx = boxes.cpu().to(torch.float32).numpy().copy()
+    bx[np.arange(bx.shape[1])[None, :] >= kept[:, None]] = 0.0
+    B, N, A = dets.shape
+    room = DUMP_LIMIT_BYTES - bx.nbytes - counts.nbytes - (1 << 20)      # (1 MiB for the row indices and the .npy headers)
+    R = int(min(N, max(1, room // (B * A * 4))))
+    rows = np.arange(N) if R == N else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(N, size=R, replace=False))
+    sample = dets[:, torch.from_numpy(rows).to(dets.device)].cpu().to(torch.float32).numpy()
+    files = {"boxes": bx, "counts": counts, "detections_sample": sample,
+             "detection_rows": rows.astype(np.float64)}
+    sizes = {}
+    for name, a in files.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+        sizes[name] = a.nbytes
+    assert sum(sizes.values()) <= DUMP_LIMIT_BYTES, sizes
+    return sizes
+
+
 def dry_run(args, rank, world):
     """Launcher / rendezvous / collective / JSON-line rehearsal on CPU tensors: every rank builds a synthetic payload
     with the PRODUCT's pack function, runs the product's single all-gather K times (barrier + max-over-ranks timing as
@@ -683,10 +733,14 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="launcher + collective rehearsal on CPU tensors (no GPU needed)")
     ap.add_argument("--weights", default="sw1", choices=["sw1", "dense", "eval"],
                     help="sw1: ~50-150 candidates/img; dense: ~1e4 rows/img pass conf (BASELINE configs[4]); eval: SW-eval")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed to DIR/*.npy "
+                    "(final boxes, counts, a fixed sample of the decoded detections; float32 / float64, <= 64 MB; see dump_outputs)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         relaunch_under_torchrun(args.gpus, args.dry_run)              # does not return
@@ -728,6 +782,8 @@ def main():
     t_build = time.perf_counter() - t_proc - t_setup
     elapsed = main_w.run(args.steps, args.warmup)
     cand4, kept4 = main_w.finish(rank)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *main_w.last_outputs())     # before anything else runs the Detector again
     rank_info = {"rank": rank, "device": str(dev), "lanes": main_w.det.lanes,
                  "setup_s": round(t_setup, 2), "detector_build_s": round(t_build, 2),
                  "own_ms_per_step": round(main_w.own_elapsed / args.steps * 1e3, 4)}

@@ -1,7 +1,7 @@
-"""Worker of tests/test_gpu_headline.py::test_config4_full_size_8_ranks_equals_single_gpu (launched under torch.distributed.run
-with 8 ranks and YV3_DIST_BACKEND=gloo on a box with ONE GPU: the ranks time-share it, gloo carries the gather).
+"""Worker of tests/test_gpu_headline.py::test_config4_full_size_4_ranks_equals_single_gpu (launched under torch.distributed.run
+with 4 ranks and YV3_DIST_BACKEND=gloo on a box with ONE GPU: the ranks time-share it, gloo carries the gather).
 
-BASELINE configs[3]: 416x416, global batch 256 (seed 3), contiguous shards of 32 per rank, one gather of the final boxes.
+BASELINE configs[3]: 416x416, global batch 256 (seed 3), contiguous shards of 256 / world per rank, one gather of the final boxes.
 Every rank: ``detect_sharded(net, x_global)`` with ``net.deterministic = True`` (direct one-tile-per-workgroup kernels, one lane:
 the result of an image does not depend on the batch it is in), then a second call in the DEFAULT mode (per-launch kernel
 choice).  Rank 0 alone then runs the single-GPU ``detect`` on all 256 images and prints one JSON line:
@@ -36,11 +36,16 @@ def make_net(stream, deterministic, shared_gpu):
 
 
 def main():
-    """Two ways to run: (a) 8 ranks over gloo on ONE GPU (test_config4_full_size_8_ranks_equals_single_gpu); (b) one rank per GPU
-    over RCCL on a box with >= 2 GPUs (tests/test_gpu_dist.py::test_rccl_multi_gpu_sharded_equals_single_gpu, self-arming)."""
+    """Two ways to run: (a) 4 ranks over gloo on ONE GPU (test_config4_full_size_4_ranks_equals_single_gpu); (b) one rank per GPU
+    over RCCL (tests/test_gpu_dist.py::test_rccl_multi_gpu_sharded_equals_single_gpu, self-arming; a group of one on a box with
+    one GPU, its all-gather forced)."""
     rank, local, world = ydist.init_from_env()
+    if not dist.is_initialized():          # a world of one (a box with one GPU): an RCCL group of one, the all-gather forced below
+        torch.cuda.set_device(local)
+        dist.init_process_group(backend="nccl", rank=rank, world_size=world)
+    force = world == 1
     rccl = dist.get_backend() == "nccl"
-    assert (rccl and world <= torch.cuda.device_count()) or (not rccl and world == 8)
+    assert (rccl and world <= torch.cuda.device_count()) or (not rccl and world == 4)
     torch.cuda.set_device(local if rccl else 0)
     stream = synth.weight_stream()
     x = torch.from_numpy(synth.images(64, 416, 3)).repeat(4, 1, 1, 1)          # 256 images on the host (64 distinct scenes x 4)
@@ -53,14 +58,15 @@ def main():
     dist.all_gather_into_tensor = lambda *a, **k: (calls.append(tuple(a[1].shape)), orig(*a, **k))[1]
     net_d = make_net(stream, True, not rccl)
     with torch.no_grad():
-        got_d = detect_sharded(net_d, x)                       # warm (builds the sharded detector: no collective beyond the gather at lanes=1)
+        # warm (builds the sharded detector: no collective beyond the gather at lanes=1)
+        got_d = detect_sharded(net_d, x, force_collective=force)
         calls.clear()
-        got_d = detect_sharded(net_d, x)
+        got_d = detect_sharded(net_d, x, force_collective=force)
     per_call = len(calls)
     shapes = list(calls)
     net = make_net(stream, False, not rccl)
     with torch.no_grad():
-        got = detect_sharded(net, x)
+        got = detect_sharded(net, x, force_collective=force)
     lanes_here = [sd.det.lanes for sd in net.__dict__.get("_sharded_detectors", {}).values()]
     dist.all_gather_into_tensor = orig
     assert len(got_d) == len(got) == 256

@@ -64,6 +64,42 @@ def load_sw1_net(stream, size=416, num_class=80):
     return net
 
 
+def trained_like_stream(num_class=80, seed=20260935, b_obj=-2.0, b_cls=-2.0, head_gain=0.25):
+    """Stand-in for a trained darknet weight file (which cannot ship with the tests): the SW-1 layout with the value ranges of a
+    trained network instead of SW-1's narrow uniform ones.  Conv weights are c**3 * a with c uniform in [-1, 1] (He variance,
+    heavy-tailed: |w| spans ~1e-13 ... 1, half of them below 1e-2); BatchNorm running variances span 1e-2 ... 10 (log-uniform)
+    with gamma and running mean scaled by their square root, and biases in [-0.5, 0.5].  On the dog image (tests/golden/e2e.npz)
+    the oracle's activations reach ~97, 363 rows pass score 0.5 (47 boxes after NMS) and no score lies within 3.9e-4 of 0.5.
+    Seeded integer RNG + float32 arithmetic (yolo_v3_amd.synth): bit-identical everywhere."""
+    from yolo_v3_amd import synth, arch
+    specs = arch.conv_specs(num_class)
+    out = np.empty(arch.floats_in_stream(specs), dtype=np.float32)
+    p, attrib = 0, num_class + 5
+    for i, sp in enumerate(specs):
+        fan_in = sp.cin * sp.k * sp.k
+        nw = sp.cout * fan_in
+        c = synth.uniform(seed, i * 8 + 4, nw, -1.0, 1.0)
+        if sp.bn:
+            var = np.float32(10.0) ** synth.uniform(seed, i * 8 + 3, sp.cout, -2.0, 1.0)
+            sd = np.sqrt(var).astype(np.float32)
+            gscale = np.float32(0.35 if sp.res2 else 1.0)
+            out[p:p + sp.cout] = synth.uniform(seed, i * 8 + 0, sp.cout, -0.5, 0.5); p += sp.cout                # bn.bias
+            out[p:p + sp.cout] = sd * synth.uniform(seed, i * 8 + 1, sp.cout, 0.6, 1.2) * gscale; p += sp.cout   # bn.weight
+            out[p:p + sp.cout] = sd * synth.uniform(seed, i * 8 + 2, sp.cout, -0.5, 0.5); p += sp.cout           # running_mean
+            out[p:p + sp.cout] = var; p += sp.cout                                                               # running_var
+            a = np.float32(np.sqrt(14.0 / (1.01 * fan_in)))          # E[c**6] = 1/7: variance 2 / (1.01 fan_in), as SW-1
+        else:
+            bias = np.zeros(sp.cout, dtype=np.float32)
+            for anchor in range(3):
+                bias[anchor * attrib + 4] = b_obj
+                bias[anchor * attrib + 5:(anchor + 1) * attrib] = b_cls
+            out[p:p + sp.cout] = bias; p += sp.cout
+            a = np.float32(head_gain * np.sqrt(7.0 / fan_in))
+        out[p:p + nw] = a * c * c * c; p += nw
+    assert p == out.size
+    return out
+
+
 # ----------------------------------------------------------------------------- layer-by-layer ("teacher-forced") runs
 def teacher_forced_layers(net, mode, x, taps):
     """Run every one of the 75 convolutions of `net` ALONE through the C-ABI in math mode `mode`, each fed the

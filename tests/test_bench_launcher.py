@@ -100,3 +100,36 @@ def test_live_traffic_counter_parsing(tmp_path):
     total, n = bench.sum_counter(str(p), "conv_planes_kernel")
     assert n == 2 and abs(total - 150.5) < 1e-9
     assert bench.sum_counter(str(p), "conv_igemm_f32_kernel") == (0, 0)
+
+
+def test_steps_must_be_positive():
+    r = _run(["--dry-run", "--steps", "0"])
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
+def test_dump_outputs_files(tmp_path):
+    """bench.dump_outputs on CPU tensors: float32 / float64 files, boxes past an image's kept count zeroed, the detection sample a
+    fixed sorted set of rows (identical from call to call) that fits the 64 MB budget at the headline's bs=64 x 10647 rows x 85."""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    B, cap, N, A = 3, 6, 500, 85
+    boxes = torch.rand(B, cap, 7)
+    counts = torch.tensor([[4, 0], [9, 2], [6, 6]], dtype=torch.int32)
+    dets = torch.rand(B, N, A)
+    d = str(tmp_path / "small")
+    bench.dump_outputs(d, boxes, counts, dets)
+    f = {n: np.load(os.path.join(d, n + ".npy")) for n in ("boxes", "counts", "detections_sample", "detection_rows")}
+    assert [f[n].dtype for n in ("boxes", "counts", "detections_sample", "detection_rows")] == [np.float32, np.float64, np.float32, np.float64]
+    assert f["counts"].tolist() == [[4, 0], [9, 2], [6, 6]]
+    for i, k in enumerate((0, 2, 6)):
+        assert np.array_equal(f["boxes"][i, :k], boxes[i, :k].numpy()) and not f["boxes"][i, k:].any()
+    assert f["detection_rows"].tolist() == list(range(N)) and np.array_equal(f["detections_sample"], dets.numpy())     # all rows fit
+    B, N = 64, 10647
+    dets = torch.arange(N, dtype=torch.float32).view(1, N, 1).expand(B, N, A)          # value = row index
+    sizes = [bench.dump_outputs(str(tmp_path / name), torch.zeros(B, 512, 7), torch.zeros(B, 2), dets) for name in ("a", "b")]
+    assert sizes[0] == sizes[1] and sum(sizes[0].values()) <= 64 * 10 ** 6
+    ra, rb = (np.load(str(tmp_path / name / "detection_rows.npy")) for name in ("a", "b"))
+    assert np.array_equal(ra, rb) and 0 < len(ra) < N and (np.diff(ra) > 0).all()
+    s = np.load(str(tmp_path / "a" / "detections_sample.npy"))
+    assert s.shape == (B, len(ra), A) and (s == ra[None, :, None]).all()
