@@ -33,6 +33,7 @@ extern "C" {
 #define YV3_EWORKSPACE (-3)      /* workspace too small                                     */
 #define YV3_EDTYPE   (-4)        /* unknown dtype code                                      */
 #define YV3_ERCCL    (-5)        /* yv3_gather_boxes: librccl not found, or ncclAllGather failed */
+#define YV3_ELIMIT   (-6)        /* input beyond a documented kernel limit (yv3_cocoeval)   */
 
 /* Tensor / math modes.  "Plane" tensors are NP bf16 planes [NP][B,H,W,C] (plane stride B*H*W*C).   */
 #define YV3_F32  0               /* fp32 NHWC tensors, exact fp32 MFMA (v_mfma_f32_32x32x2_f32)          */
@@ -400,6 +401,51 @@ int yv3_upsample2x_concat(const float* up, const float* tail, float* out, int B,
  * communicator cannot be handed out; this entry point is for hosts that own their communicator.
  * ------------------------------------------------------------------------------------------ */
 int yv3_gather_boxes(const float* payload, float* gathered, int b_local, int rows, void* rccl_comm, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * COCO bbox evaluation.  Replaces pycocotools' COCOeval(gt, dt, 'bbox').evaluate() + accumulate() (useCats = 1), which
+ * the reference notebook runs on the files evaluate.generate_annotations_file / generate_results_file write
+ * (evaluate.ipynb cells 22-25, 48-51).  The caller parses the JSON and maps ids to dense indices: image index = position
+ * in the sorted params.imgIds, category index = position in the sorted params.catIds, -1 = not evaluated (dropped).
+ * Grouping, greedy matching, ordering and accumulation all run on the device; results are bit-identical to a float64
+ * restatement of pycocotools (the file is compiled with -ffp-contract=off).
+ *
+ * Limits: len(iouThrs) * len(areaRng) <= 64, len(recThrs) <= 128, 1 <= n_maxdet <= YV3_COCO_MAX_MAXDETS, maxDets
+ * ascending (COCOeval.evaluate sorts them) with maxDets[-1] <= 1024 -- checked here, YV3_ELIMIT / YV3_EINVAL.  At most
+ * 256 GTs per (image, category) group -- found on the device, reported as YV3_ELIMIT in *status (0 = ok), which the
+ * caller reads with the outputs; the outputs are then not valid.
+ * ------------------------------------------------------------------------------------------ */
+#define YV3_COCO_MAX_MAXDETS 8
+
+typedef struct yv3_cocoeval_desc {
+    int n_gt, n_det, n_img, n_cat;
+    const int* gt_img;           /* [n_gt] dense image index, -1 = dropped                                  */
+    const int* gt_cat;           /* [n_gt] dense category index, -1 = dropped                               */
+    const double* gt_box;        /* [n_gt][4] x, y, w, h                                                    */
+    const double* gt_area;       /* [n_gt] the annotation's 'area' field (area ranges)                      */
+    const int* gt_crowd;         /* [n_gt] iscrowd (also the 'ignore' flag, as COCOeval._prepare sets it)   */
+    const long long* gt_id;      /* [n_gt] annotation id; a det matched to id 0 counts as unmatched         */
+    const int* det_img;          /* [n_det] dense image index, -1 = dropped                                 */
+    const int* det_cat;          /* [n_det] dense category index, -1 = dropped                              */
+    const double* det_box;       /* [n_det][4] x, y, w, h (area = w * h)                                    */
+    const double* det_score;     /* [n_det] score; ties are broken by the position in this array            */
+    int n_iou, n_rec, n_area, n_maxdet;
+    const double* iou_thrs;      /* [n_iou] params.iouThrs                                                  */
+    const double* rec_thrs;      /* [n_rec] params.recThrs                                                  */
+    const double* area_rng;      /* [n_area][2] params.areaRng                                              */
+    int max_dets[YV3_COCO_MAX_MAXDETS];   /* params.maxDets, ascending (host values)                        */
+    double* precision;           /* [n_iou][n_rec][n_cat][n_area][n_maxdet] out                             */
+    double* recall;              /* [n_iou][n_cat][n_area][n_maxdet] out                                    */
+    double* scores;              /* [n_iou][n_rec][n_cat][n_area][n_maxdet] out                             */
+    int* status;                 /* [1] out: 0, or YV3_ELIMIT when a group holds more than 256 GTs           */
+} yv3_cocoeval_desc;
+
+/* Bytes of device workspace yv3_cocoeval needs (0 on a bad argument). */
+size_t yv3_cocoeval_workspace_bytes(int n_gt, int n_det, int n_img, int n_cat, int n_area);
+
+/* Enqueues the whole evaluation on `stream`; ws: caller-owned device workspace of at least
+ * yv3_cocoeval_workspace_bytes(...) bytes (no alignment beyond 256 bytes required). */
+int yv3_cocoeval(const yv3_cocoeval_desc* desc, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -42,6 +42,22 @@ class ConvDesc(ctypes.Structure):
                 ("w_wino4", c_void_p)]
 
 
+COCO_MAX_MAXDETS = 8
+ELIMIT = -6
+
+
+class CocoEvalDesc(ctypes.Structure):
+    """struct yv3_cocoeval_desc (include/yv3.h)."""
+    _fields_ = [("n_gt", c_int), ("n_det", c_int), ("n_img", c_int), ("n_cat", c_int),
+                ("gt_img", c_void_p), ("gt_cat", c_void_p), ("gt_box", c_void_p), ("gt_area", c_void_p),
+                ("gt_crowd", c_void_p), ("gt_id", c_void_p),
+                ("det_img", c_void_p), ("det_cat", c_void_p), ("det_box", c_void_p), ("det_score", c_void_p),
+                ("n_iou", c_int), ("n_rec", c_int), ("n_area", c_int), ("n_maxdet", c_int),
+                ("iou_thrs", c_void_p), ("rec_thrs", c_void_p), ("area_rng", c_void_p),
+                ("max_dets", c_int * COCO_MAX_MAXDETS),
+                ("precision", c_void_p), ("recall", c_void_p), ("scores", c_void_p), ("status", c_void_p)]
+
+
 _SIGNATURES = {
     "yv3_version": (c_int, []),
     "yv3_conv_workspace_bytes": (ctypes.c_size_t, []),
@@ -81,6 +97,8 @@ _SIGNATURES = {
     "yv3_postproc_filter": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "yv3_postproc_nms": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_int, c_void_p, c_int,
                                  c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "yv3_cocoeval_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "yv3_cocoeval": (c_int, [ctypes.POINTER(CocoEvalDesc), c_void_p, c_size_t, c_void_p]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

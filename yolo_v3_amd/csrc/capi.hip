@@ -17,6 +17,7 @@ extern "C" const char* yv3_error_string(int code) {
         case YV3_EWORKSPACE: return "workspace too small";
         case YV3_EDTYPE: return "unknown dtype";
         case YV3_ERCCL: return "RCCL: librccl.so not found or ncclAllGather failed";
+        case YV3_ELIMIT: return "input beyond a documented kernel limit";
         default: return code > 0 ? hipGetErrorString((hipError_t)code) : "unknown yv3 error";
     }
 }

@@ -1,4 +1,14 @@
-"""COCO-results writer of the reference's ``evaluate.py``, fed by the GPU hot path.
+"""COCO ground-truth and results writers of the reference's ``evaluate.py``, the results fed by the GPU hot path.
+
+Ground truth (reference evaluate.py:38-115, ``generate_annotations_file`` and its helpers): same names, arguments, entry
+layout and bytes on disk (``json.dump(d, f, indent=4, separators=(',', ':'))``); darknet label files (``cls cx cy w h``,
+relative) become absolute ``xywh`` with the reference's float64 operation order (boundingbox.py:30-33,45-48,59-80),
+``area = w*h``, ``iscrowd = 0``, annotation ids ``0, 1, 2, ...`` (the first id is 0: see ``yolo_v3_amd.cocoeval`` on what
+that does to the score).  One difference: an image without a label file has no annotations (the reference reuses the
+previous image's labels, or raises ``NameError`` on the first image).  Image sizes are those of the decoded, EXIF-rotated
+image, as ``cv2.imread`` and `read_image_rgb` see it.
+
+Results:
 
 Mirrors reference evaluate.py:117-121 (``create_results_entry``), :151-195 (``open_json_pred_writer``,
 ``JsonPredictionWriter``) and :197-206 (``predict_and_process``): same names, arguments, entry layout
@@ -16,9 +26,11 @@ class index 0..C-1 as in the reference (it never maps to COCO's sparse ids).
 import json
 import os.path as osp
 import re
+import warnings
 from collections import OrderedDict
 from contextlib import contextmanager
 
+import numpy as np
 import torch
 
 from . import _ffi
@@ -29,6 +41,99 @@ def get_image_id_from_path(image_path):
     image_path = osp.splitext(image_path)[0]
     m = re.search(r'\d+$', image_path)
     return int(m.group())
+
+
+def create_annotations(cat_list, img_list, ann_list):
+    """reference evaluate.py:42-45"""
+    return OrderedDict({'categories': cat_list, 'images': img_list, 'annotations': ann_list})
+
+
+def create_images_entry(image_id, width=None, height=None):
+    """reference evaluate.py:47-51"""
+    if width is None or height is None:
+        return OrderedDict({'id': image_id})
+    return OrderedDict({'id': image_id, 'width': width, 'height': height})
+
+
+def create_categories(class_names):
+    """reference evaluate.py:53-54"""
+    return [{'id': i, 'name': cls} for i, cls in enumerate(class_names)]
+
+
+def create_annotations_entry(image_id, bbox, category_id, ann_id, iscrowd=0, area=None, segmentation=None):
+    """reference evaluate.py:56-71"""
+    if area is None:
+        if segmentation is None:
+            area = bbox[2] * bbox[3]
+        else:
+            raise NotImplementedError()
+    return OrderedDict({"id": ann_id, "image_id": image_id, "category_id": category_id, "iscrowd": iscrowd, "area": area,
+                        "bbox": bbox})
+
+
+def generate_annotations_file(target_txt, class_names, out):
+    """reference evaluate.py:73-76: the COCO ground-truth file of the images listed in ``target_txt``."""
+    ann_dict = create_annotations_dict(target_txt, class_names)
+    with open(out, 'w') as f:
+        json.dump(ann_dict, f, indent=4, separators=(',', ':'))
+
+
+def create_annotations_dict(target_txt, class_names):
+    """reference evaluate.py:78-87: label path = image path with every ``jpg`` -> ``txt`` and every ``images`` -> ``labels``."""
+    with open(target_txt, 'r') as f:
+        img_path_list = [lines.strip() for lines in f.readlines()]
+    label_path_list = [img_path.replace('jpg', 'txt').replace('images', 'labels') for img_path in img_path_list]
+    img_list, ann_list = get_img_ann_list(img_path_list, label_path_list)
+    cat_list = create_categories(class_names)
+    return create_annotations(cat_list, img_list, ann_list)
+
+
+def image_size(path):
+    """(width, height) of the decoded image after its EXIF orientation is applied -- the shape `read_image_rgb` returns and
+    ``cv2.imread`` gives, read from the header without decoding the pixels (orientations 5-8 swap the axes)."""
+    from PIL import Image
+    with Image.open(path) as im:
+        w, h = im.size
+        orientation = im.getexif().get(0x0112, 1)
+    return (h, w) if orientation in (5, 6, 7, 8) else (w, h)
+
+
+def labels_to_xywh(labels, width, height):
+    """Darknet rows ``cls cx cy w h`` (relative) -> ``cls x y w h`` (absolute), float64, in the reference's order:
+    BoundingBoxConverter.convert (boundingbox.py:59-80) = cxcywh -> xywh (x = cx - w/2, y = cy - h/2) on the relative
+    values, then x, w *= width and y, h *= height."""
+    labels = np.array(labels, dtype=np.float64).reshape(-1, 5)
+    if len(labels) == 0:
+        return labels
+    box = labels[..., [1, 2, 3, 4]]
+    x, y = box[..., 0] - box[..., 2] / 2, box[..., 1] - box[..., 3] / 2
+    box[..., 0], box[..., 1] = x, y
+    box[..., [0, 2]] *= width
+    box[..., [1, 3]] *= height
+    labels[..., 1:5] = box
+    return labels
+
+
+def get_img_ann_list(img_path_list, label_path_list):
+    """reference evaluate.py:89-115: one images entry per path, one annotation per label row, ids in order from 0.
+    A missing label file means "no annotations" (the one difference from the reference, see the module docstring)."""
+    img_list, ann_list = [], []
+    for img_path, label_path in zip(img_path_list, label_path_list):
+        image_id = get_image_id_from_path(img_path)
+        width, height = image_size(img_path)
+        img_list.append(create_images_entry(image_id, width, height))
+        if not osp.exists(label_path):
+            continue
+        with warnings.catch_warnings():                    # (an empty label file: "input contained no data")
+            warnings.simplefilter("ignore", UserWarning)
+            rows = np.loadtxt(label_path).reshape(-1, 5)
+        labels = labels_to_xywh(rows, width, height)
+        for label in labels:
+            category_id = int(label[0])
+            bbox = list(label[1:5])
+            ann_id = len(ann_list)
+            ann_list.append(create_annotations_entry(image_id, bbox, category_id, ann_id))
+    return img_list, ann_list
 
 
 def create_results_entry(image_id, category_id, bbox, score):
