@@ -36,29 +36,36 @@ static int check_desc(const yv3_conv_desc* d, bool need_output = true) {
     return 0;
 }
 
-extern "C" int yv3_conv2d(const yv3_conv_desc* d, void* stream) {
-    const int rc = check_desc(d);
-    if (rc) return rc;
+static int plane_count(int dtype) {
+    return dtype == YV3_BF16 ? 1 : dtype == YV3_F32_F16X2 ? 2 : dtype == YV3_F32_BF16X3 ? 3 : 0;
+}
+
+// The dtype / output-format errors of yv3_conv2d: ONE function, called by the launch and by the form query, so that
+// yv3_conv2d_form returns "the YV3_E* code yv3_conv2d would return" (include/yv3.h).
+static int check_dtype(const yv3_conv_desc* d) {
     if (d->dtype == YV3_F32) {
         if (d->out_dtype != YV3_F32) return YV3_EDTYPE;
-        if (d->dec_out || !d->y) return YV3_EDTYPE;            // the fused decode lives in the plane kernels' epilogue
-        return yv3_conv2d_f32(d, (hipStream_t)stream);
+        if (d->dec_out) return YV3_EDTYPE;                     // the fused decode lives in the plane kernels' epilogue
+        return 0;
     }
-    if (d->dtype == YV3_F32_BF16X3 || d->dtype == YV3_BF16 || d->dtype == YV3_F32_F16X2) {
-        if (d->out_dtype != YV3_F32 && d->out_dtype != d->dtype) return YV3_EDTYPE;
-        if (d->cin % 32) return YV3_ESHAPE;
-        return yv3_conv2d_planes(d, d->dtype == YV3_BF16 ? 1 : d->dtype == YV3_F32_F16X2 ? 2 : 3, (hipStream_t)stream);
-    }
+    if (plane_count(d->dtype)) return d->out_dtype != YV3_F32 && d->out_dtype != d->dtype ? YV3_EDTYPE : 0;
     return YV3_EDTYPE;
 }
 
+extern "C" int yv3_conv2d(const yv3_conv_desc* d, void* stream) {
+    int rc = check_desc(d);
+    if (!rc) rc = check_dtype(d);
+    if (rc) return rc;
+    if (d->dtype == YV3_F32) return yv3_conv2d_f32(d, (hipStream_t)stream);
+    return yv3_conv2d_planes(d, plane_count(d->dtype), (hipStream_t)stream);
+}
+
 extern "C" int yv3_conv2d_form(const yv3_conv_desc* d) {
-    const int rc = check_desc(d, false);            // (a fused-decode head may not have its output bound yet)
+    int rc = check_desc(d, false);                  // (a fused-decode head may not have its output bound yet)
+    if (!rc) rc = check_dtype(d);
     if (rc) return rc;
     if (d->dtype == YV3_F32) return yv3_conv2d_f32_form(d);
-    if (d->dtype == YV3_F32_F16X2) return yv3_conv2d_planes_form(d, 2);
-    if (d->dtype == YV3_F32_BF16X3 || d->dtype == YV3_BF16) return YV3_FORM_DIRECT;
-    return YV3_EDTYPE;
+    return yv3_conv2d_planes_form(d, plane_count(d->dtype));
 }
 
 extern "C" int yv3_conv2d_launches(const yv3_conv_desc* d) {
