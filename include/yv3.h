@@ -447,6 +447,44 @@ size_t yv3_cocoeval_workspace_bytes(int n_gt, int n_det, int n_img, int n_cat, i
  * yv3_cocoeval_workspace_bytes(...) bytes (no alignment beyond 256 bytes required). */
 int yv3_cocoeval(const yv3_cocoeval_desc* desc, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * YOLO training loss of one head and dL/dlogits (reference yololayer.py:64-95 + build_target_tensor, yololayer.py:107-172,
+ * which builds its targets on the CPU with a Python loop over images and GT rows).  One call = one head; YoloNet makes three.
+ * Semantics are the reference's, quirks included: rows of an image are used up to the first all-zero row; the ignore mask
+ * (IoU > 0.7 with ANY valid GT of the image) is not cleared at object cells; the best anchor is the first argmax over all
+ * nine of the zero-centred IoU, in this head's grid units; two rows on one (image, anchor, cell): offsets and box_coord_mask
+ * from the LAST row, classes united, both counted in nGT.  Sums are fp64 in a fixed order: identical calls, identical bits.
+ *
+ * Rows the reference cannot process -- a class outside [0, C), a negative or NaN value, a cell outside this head's grid,
+ * w*h > 2 (math.sqrt of a negative number) -- are reported as YV3_EINVAL in *status; more than YV3_YOLO_LOSS_MAX_ROWS valid
+ * rows in one image as YV3_ELIMIT.  Both are found on the device: the caller reads *status with the outputs, which are then
+ * not valid.  Zero w / h are accepted, as the reference accepts them.
+ * ------------------------------------------------------------------------------------------ */
+#define YV3_YOLO_LOSS_MAX_ROWS 1024
+
+typedef struct yv3_yolo_loss_desc {
+    const float* logits;         /* raw head logits: element (b, p = gy*W + gx, c = anchor*(5+C) + attr) at
+                                    b*stride_b + p*stride_p + c*stride_c (NCHW: H*W*3(5+C), 1, H*W; NHWC rows of ld: H*W*ld, ld, 1) */
+    float* grad;                 /* optional out: dL/dlogits at the same offsets, every element written; NULL = skip        */
+    long long stride_b, stride_p, stride_c;   /* element strides; they must address distinct elements                     */
+    const float* target;         /* [B][T][5] rows (cls, cx, cy, w, h), relative, zero-padded; may be NULL when T == 0      */
+    int B, H, W, T, num_class;
+    float img_dim_h;             /* img_dim[1] of the reference: stride = img_dim_h / H                                      */
+    float anchors[18];           /* all nine anchors (w, h), input pixels (host values)                                      */
+    int mask[3];                 /* this head's anchor indices into anchors[]                                                */
+    double* sums;                /* [6] out: loss_x, loss_y, loss_w, loss_h, loss_conf, loss_cls (the reference's sums)     */
+    int* counts;                 /* [2] out: nCorrect, nGT                                                                   */
+    int* status;                 /* [1] out: 0, YV3_EINVAL (a row the reference cannot process) or YV3_ELIMIT               */
+} yv3_yolo_loss_desc;
+
+/* Bytes of device workspace yv3_yolo_loss needs for B images of an H x W head and T target rows (0 on a bad argument). */
+size_t yv3_yolo_loss_workspace_bytes(int B, int H, int W, int T);
+
+/* Enqueues the loss (and the gradient when desc->grad is set) on `stream`: three launches, no allocation, no synchronisation.
+ * ws: caller-owned device workspace of at least yv3_yolo_loss_workspace_bytes(B, H, W, T) bytes.  Pointers, sizes, anchors
+ * and strides are checked here, before any launch (YV3_EINVAL / YV3_ESHAPE / YV3_EWORKSPACE). */
+int yv3_yolo_loss(const yv3_yolo_loss_desc* desc, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

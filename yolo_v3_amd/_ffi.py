@@ -58,6 +58,19 @@ class CocoEvalDesc(ctypes.Structure):
                 ("precision", c_void_p), ("recall", c_void_p), ("scores", c_void_p), ("status", c_void_p)]
 
 
+YOLO_LOSS_MAX_ROWS = 1024
+EINVAL, ESHAPE, EWORKSPACE = -1, -2, -3
+
+
+class YoloLossDesc(ctypes.Structure):
+    """struct yv3_yolo_loss_desc (include/yv3.h)."""
+    _fields_ = [("logits", c_void_p), ("grad", c_void_p),
+                ("stride_b", c_longlong), ("stride_p", c_longlong), ("stride_c", c_longlong),
+                ("target", c_void_p), ("B", c_int), ("H", c_int), ("W", c_int), ("T", c_int), ("num_class", c_int),
+                ("img_dim_h", c_float), ("anchors", c_float * 18), ("mask", c_int * 3),
+                ("sums", c_void_p), ("counts", c_void_p), ("status", c_void_p)]
+
+
 _SIGNATURES = {
     "yv3_version": (c_int, []),
     "yv3_conv_workspace_bytes": (ctypes.c_size_t, []),
@@ -99,6 +112,8 @@ _SIGNATURES = {
                                  c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "yv3_cocoeval_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "yv3_cocoeval": (c_int, [ctypes.POINTER(CocoEvalDesc), c_void_p, c_size_t, c_void_p]),
+    "yv3_yolo_loss_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "yv3_yolo_loss": (c_int, [ctypes.POINTER(YoloLossDesc), c_void_p, c_size_t, c_void_p]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -106,7 +121,11 @@ _lib = None
 
 
 class Yv3Error(RuntimeError):
-    pass
+    code = None          # the YV3_E* code (or hipError_t) behind the error, when it came from the library
+
+
+class GpuOnlyError(Yv3Error, NotImplementedError):
+    """A CPU tensor where only the GPU path exists (the reference's training branch runs on CPU tensors; this package does not)."""
 
 
 def lib():
@@ -129,7 +148,9 @@ def lib():
 def check(rc, what=""):
     if rc != 0:
         msg = lib().yv3_error_string(rc).decode()
-        raise Yv3Error("%s failed: %s (code %d)" % (what or "libyv3 call", msg, rc))
+        err = Yv3Error("%s failed: %s (code %d)" % (what or "libyv3 call", msg, rc))
+        err.code = rc
+        raise err
 
 
 def stream_ptr():

@@ -8,14 +8,19 @@ the modules below are *parameter containers*; ``forward`` never calls ``nn.Conv2
 HIP kernels in ``csrc/`` (NHWC implicit-GEMM on MFMA, fused BN/LeakyReLU/residual epilogues,
 fused upsample+concat, fused decode).  GPU only: a CPU tensor raises (no fallback).
 
-Not carried over: the training branch (``target is not None`` -> loss, reference
-darknet.py:225-229 / yololayer.py:64-95) raises ``NotImplementedError``.
+``forward(x, target)`` (reference darknet.py:225-229 / yololayer.py:64-95) returns the summed
+loss and fills ``self.stats`` like the reference; the targets, masks and loss terms run on the
+GPU (csrc/yololoss.hip) on the head logits of a plan that materialises them.  The loss does not
+require grad: backpropagation into the parameters (BatchNorm in training mode, dgrad / wgrad of
+the 75 convolutions) is not provided.  ``YoloLayer`` gives the loss's gradient with respect to
+its head logits.
 """
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import _ffi, arch, engine as _engine
+from . import yololayer as _yololayer
 from .yololayer import YoloLayer
 
 DEFAULT_MATH_MODE = _ffi.F32H2
@@ -326,10 +331,45 @@ class YoloNet(nn.Module):
         dets, _ = self.engine(dtype).forward(x)
         return dets
 
+    def head_logits(self, x):
+        """The three heads' raw logits ``[B, 3*(5+C), h, w]`` (13x13, 26x26, 52x52 at 416), fp32 on the GPU: NCHW views
+        (channels_last strides) of copies the caller owns.  Computed by the same plan as ``forward(x, target)``."""
+        _, plan = self.engine().forward(x, logits=True)
+        return tuple(lg.clone().permute(0, 3, 1, 2) for lg, _, _ in plan.logits)
+
+    def _loss(self, x, target):
+        """forward(x, target): the reference's summed loss of the three heads (darknet.py:225-229) and ``self.stats``."""
+        if not x.is_cuda:
+            raise _ffi.GpuOnlyError("input images must live on the GPU: this package runs only on MI355X (HIP kernels), "
+                                    "there is no CPU path")
+        _, plan = self.engine().forward(x, logits=True)
+        B = x.shape[0]
+        heads = (self.yolo1, self.yolo2, self.yolo3)
+        with torch.cuda.device(x.device):
+            t = _yololayer.loss_target(target, B, x.device)
+            out = torch.empty(3 * _yololayer.HEAD_OUT_BYTES, device=x.device, dtype=torch.uint8)
+            for k, ((lg, hh, ww), head) in enumerate(zip(plan.logits, heads)):
+                ld = lg.shape[-1]
+                _yololayer.launch_loss(lg, (hh * ww * ld, ld, 1), t, hh, ww, self.numClass, x.shape[2], head.anchors_all,
+                                       head.anchors_mask, out[k * _yololayer.HEAD_OUT_BYTES:])
+            host = out.cpu().numpy()                      # (the one device->host read: the reference calls .item())
+            res = [_yololayer.head_results(host, k, B) for k in range(3)]
+            loss = np.float32(0.0)
+            for l, _ in res:
+                loss = np.float32(loss + l)               # sum(det) over the three heads, fp32
+            stats = [sum(r[1][i] for r in res) for i in range(9)]
+            self.stats = dict(zip(self.stat_keys, stats))
+            self.stats['recall'] = self.stats['nCorrect'] / self.stats['nGT'] if self.stats['nGT'] else 0
+            return torch.tensor(float(loss), dtype=torch.float32, device=x.device)
+
     def forward(self, x, target=None):
+        """``forward(x)`` -> ``(det1, det2, det3)``.  ``forward(x, target)`` -> the summed loss of the three heads as a 0-d fp32
+        GPU tensor, with ``self.stats`` set as the reference sets it (``loss, loss_x, loss_y, loss_w, loss_h, loss_conf,
+        loss_cls``: per-head values / B summed over the heads; ``nCorrect``, ``nGT`` summed; ``recall``).  target: ``[B, T, 5]``
+        rows (cls, cx, cy, w, h), relative, zero-padded, on the CPU or the GPU.  The loss does not require grad:
+        backpropagation into the parameters is not provided (``YoloLayer`` gives dL/d head logits)."""
         if target is not None:
-            raise NotImplementedError("training loss (reference darknet.py:225-229, yololayer.py:64-95) "
-                                      "is outside the inference hot path")
+            return self._loss(x, target)
         dets, plan = self.engine().forward(x)
         r1, r2 = plan.rows[0], plan.rows[0] + plan.rows[1]
         return dets[:, :r1], dets[:, r1:r2], dets[:, r2:]

@@ -310,9 +310,10 @@ class Plan:
             raise _ffi.Yv3Error("input height/width must be multiples of 32 (got %dx%d)" % (H, W))
         return 3 * sum((H // s) * (W // s) for s in (32, 16, 8)), 5 + engine.num_class
 
-    def __init__(self, engine, B, H, W, flags=None, two_lanes=False):
+    def __init__(self, engine, B, H, W, flags=None, two_lanes=False, logits=False):
         """two_lanes: this plan is one of two equal lanes that run concurrently (`Detector`): tells the library's per-launch
-        kernel choice that the chip is shared (yv3.h YV3_OPT_TWO_LANES)."""
+        kernel choice that the chip is shared (yv3.h YV3_OPT_TWO_LANES).  logits: the head convs write their fp32 logits
+        (`self.logits`) instead of decoding in their epilogue -- the training-loss path (YoloNet.forward(x, target))."""
         if H % 32 or W % 32:
             raise _ffi.Yv3Error("input height/width must be multiples of 32 (got %dx%d)" % (H, W))
         self.B, self.H, self.W = B, H, W
@@ -354,7 +355,7 @@ class Plan:
 
         # the YOLO decode is fused into the three head convs' epilogue (plane kernels): their logits are then not
         # materialised and the descriptors' dec_out is pointed at the caller's detections tensor before each launch
-        self.fused_decode = bool(engine.fuse_decode and dt != F32)
+        self.fused_decode = bool(engine.fuse_decode and dt != F32 and not logits)
         self.head_descs = []     # (descriptor index, ho, wo)
         self.desc_spec = []      # descriptor index -> index into arch.conv_specs (a layer may run as two launches: batch_split)
         ncu = torch.cuda.get_device_properties(dev).multi_processor_count
@@ -651,10 +652,22 @@ class Engine:
     # -- plans
     def drop_plan(self, B, H, W):
         self._plans.pop((B, H, W), None)
+        self._plans.pop((B, H, W, "logits"), None)
 
-    def plan(self, B, H, W):
+    def plan(self, B, H, W, logits=False):
+        """The cached plan for (B, H, W).  logits=True: a plan whose head convs write their logits -- the same plan where that
+        is already so (exact F32, or the fused decode switched off), else a second plan cached next to it (its own buffers:
+        the plan the inference entry points use is not touched)."""
         key = (B, H, W)
         p = self._plans.get(key)
+        if logits and (p is None or p.fused_decode):
+            if p is None and not (self.fuse_decode and self.dtype != F32):
+                return self.plan(B, H, W)
+            key = (B, H, W, "logits")
+            p = self._plans.get(key)
+            if p is None:
+                p = self._plans[key] = Plan(self, B, H, W, logits=True)
+            return p
         if p is None:
             p = self._plans[key] = Plan(self, B, H, W)
         return p
@@ -781,8 +794,11 @@ class Engine:
         self._plans = {}
         self.generation += 1
 
-    def forward(self, x, dets=None, _retry=True):
+    def forward(self, x, dets=None, _retry=True, logits=False):
         """x: [B,3,H,W] fp32 on the GPU -> detections [B, N, 5+C] (cx,cy,w,h,conf,cls...).
+
+        logits=True: run the logits plan (``plan(..., logits=True)``) and skip the decode: returns ``(None, plan)`` with the
+        three heads' fp32 logits in ``plan.logits``, under the same status checks and fall-backs as the detections.
 
         In F32H2 mode (and BF16, whose first layer splits its operands into fp16) the kernels' saturation flag of THIS call is copied to pinned host memory behind the last
         kernel and checked before returning (one event wait: the call then returns with the work complete, like the
@@ -796,7 +812,7 @@ class Engine:
         with torch.cuda.device(x.device):
             self.ensure_packed()
             B, _, H, W = x.shape
-            plan = self.plan(B, H, W)
+            plan = self.plan(B, H, W, logits=logits)
             if self.checks_status() and plan.flags_event is not None and plan.flags_event.query():
                 try:
                     self.raise_if_overflowed(plan, int(plan.flags_host[0]))
@@ -806,10 +822,13 @@ class Engine:
                 except RangeOverflow:
                     self.range_fallback()
                     raise
-            if dets is None:
-                dets = torch.empty((B, plan.N, plan.attrib), device=x.device, dtype=torch.float32)
-            self.run_convs(plan, x, dets)
-            self.run_decode(plan, dets)
+            if logits:
+                self.run_convs(plan, x)
+            else:
+                if dets is None:
+                    dets = torch.empty((B, plan.N, plan.attrib), device=x.device, dtype=torch.float32)
+                self.run_convs(plan, x, dets)
+                self.run_decode(plan, dets)
             if self.checks_status():
                 plan.flags_host.copy_(plan.flags, non_blocking=True)
                 plan.flags_event = torch.cuda.Event()
@@ -822,12 +841,12 @@ class Engine:
                         if not _retry:
                             raise
                         self.disable_stream_k()               # (fall back instead of failing the call)
-                        return self.forward(x, dets, _retry=False)
+                        return self.forward(x, dets, _retry=False, logits=logits)
                     except RangeOverflow:                     # (the default mode computes where the reference computes)
                         fb = self.range_fallback()
                         if fb is None:
                             raise
-                        return fb.forward(x, dets)
+                        return fb.forward(x, dets, logits=logits)
                 else:
                     # asynchronous callers: a time-out / saturation seen at the start of the NEXT call cannot be repaired for the call that
                     # produced it; the schedule / mode is switched for the calls that follow and the error still tells the caller that the
