@@ -485,6 +485,66 @@ size_t yv3_yolo_loss_workspace_bytes(int B, int H, int W, int T);
  * and strides are checked here, before any launch (YV3_EINVAL / YV3_ESHAPE / YV3_EWORKSPACE). */
 int yv3_yolo_loss(const yv3_yolo_loss_desc* desc, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training step (reference train.py: `loss = net(inp, labels); loss.backward()`, with darknet.py:27-53 in train mode), exact fp32
+ * only (csrc/train.hip).  Activations and gradients are fp32 NHWC [B][H][W][C] (P = B*H*W rows of C), except the first layer's
+ * input, which is read in place as the caller's NCHW batch (x_nchw = 1).  Weights are torch's [cout][cin][k][k].  k is 1 or 3,
+ * stride 1 or 2, padding (k-1)/2.  cin_up > 0: the input is cat(up2x(x2), x) along channels (reference darknet.py:161-162), read
+ * in place: x2 is the low-resolution [B][H/2][W/2][cin_up] map, x the [B][H][W][cin-cin_up] route tail.  No call allocates or
+ * synchronises; workspaces come from the caller.  Nothing uses float atomics and every sum runs in a fixed order, so identical
+ * calls give identical bits.  YV3_EINVAL: null pointer / non-positive size; YV3_ESHAPE: k, stride, cin_up outside the above.
+ * ------------------------------------------------------------------------------------------ */
+
+/* wf (optional): [k*k*cin][cout], wd (optional): [k*k*cout][cin] -- the operand images of yv3_train_conv_fwd / _dgrad. */
+int yv3_train_pack_weight(const float* w, float* wf, float* wd, int cout, int cin, int k, void* stream);
+
+/* z = conv(x, w) [+ bias]: the pre-BatchNorm output of a conv_bn_relu (darknet.py:40, nn.Conv2d(bias=False)) or a head conv's
+ * logits (darknet.py:115, bias given).  z: [B][Ho][Wo][cout]. */
+int yv3_train_conv_fwd(const float* x, const float* x2, const float* wf, const float* bias, float* z,
+                       int B, int H, int W, int cin, int cin_up, int cout, int k, int stride, int x_nchw, void* stream);
+
+/* dx (+)= dL/dx of z = conv(x, w) for dz = dL/dz ([B][Ho][Wo][cout]); dx: [B][H][W][cin], added to when accumulate != 0. */
+int yv3_train_conv_dgrad(const float* dz, const float* wd, float* dx, int B, int H, int W, int cin, int cout, int k, int stride,
+                         int accumulate, void* stream);
+
+/* dw = dL/dw ([cout][cin][k][k], overwritten), a sum over all B*Ho*Wo output pixels split into chunks whose partials live in ws
+ * and are added in chunk order.  The workspace size query takes the full cin (cin_up does not change it); 0 on a bad shape. */
+size_t yv3_train_conv_wgrad_workspace_bytes(int B, int H, int W, int cin, int cout, int k, int stride);
+int yv3_train_conv_wgrad(const float* x, const float* x2, const float* dz, float* dw, int B, int H, int W, int cin, int cin_up,
+                         int cout, int k, int stride, int x_nchw, void* ws, size_t ws_bytes, void* stream);
+
+/* Workspace of the per-channel reductions below over P rows of C channels (0 on a bad argument). */
+size_t yv3_train_channel_workspace_bytes(long long P, int C);
+
+/* Train-mode BatchNorm statistics of z (nn.BatchNorm2d, darknet.py:41): mean and 1/sqrt(biased var + eps) per channel.  With
+ * run_*_out set, run_*_out = (1 - momentum) run_* + momentum (mean, unbiased var); they may alias run_*. */
+int yv3_train_bn_stats(const float* z, long long P, int C, float eps, float momentum, const float* run_mean, const float* run_var,
+                       float* run_mean_out, float* run_var_out, float* mean, float* invstd, void* ws, size_t ws_bytes, void* stream);
+
+/* Eval-mode BatchNorm: mean = running_mean, invstd = 1/sqrt(running_var + eps). */
+int yv3_train_bn_eval_stats(const float* run_mean, const float* run_var, float eps, float* mean, float* invstd, int C, void* stream);
+
+/* y = LeakyReLU_0.1(gamma (z - mean) invstd + beta) [+ residual]  (darknet.py:41-44; the residual after the activation, :53). */
+int yv3_train_bn_act_fwd(const float* z, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                         const float* residual, float* y, long long P, int C, void* stream);
+
+/* Backward of yv3_train_bn_act_fwd for dy = dL/dy: with du = dy * act'(u), dbeta = sum du, dgamma = sum du * xhat, and
+ * dz = gamma invstd (du - dbeta/P - xhat dgamma/P) when train != 0 (batch statistics), dz = gamma invstd du otherwise. */
+int yv3_train_bn_act_bwd(const float* z, const float* dy, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                         float* dz, float* dgamma, float* dbeta, long long P, int C, int train, void* ws, size_t ws_bytes, void* stream);
+
+/* Head conv bias (darknet.py:115): dout = dlogits * (*scale) (scale: device fp32 scalar, NULL = 1), dbias = sum over P of dout. */
+int yv3_train_bias_bwd(const float* dlogits, const float* scale, float* dout, float* dbias, long long P, int C, void* ws, size_t ws_bytes,
+                       void* stream);
+
+/* dst += src (the gradient of an activation that fans out: residual skips, route tails, route heads). */
+int yv3_train_add(const float* src, float* dst, long long n, void* stream);
+
+/* Backward of cat(up2x(low), tail) (darknet.py:161-162): dlow (+)= the 2x2 sums of channels [0, cin_up) of dcat, dtail (+)= the
+ * other ctail channels.  H, W: the full resolution; either output may be NULL. */
+int yv3_train_upcat_bwd(const float* dcat, float* dlow, float* dtail, int B, int H, int W, int cin_up, int ctail,
+                        int acc_low, int acc_tail, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

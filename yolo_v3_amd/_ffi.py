@@ -114,6 +114,19 @@ _SIGNATURES = {
     "yv3_cocoeval": (c_int, [ctypes.POINTER(CocoEvalDesc), c_void_p, c_size_t, c_void_p]),
     "yv3_yolo_loss_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "yv3_yolo_loss": (c_int, [ctypes.POINTER(YoloLossDesc), c_void_p, c_size_t, c_void_p]),
+    "yv3_train_pack_weight": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "yv3_train_conv_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
+    "yv3_train_conv_dgrad": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 8 + [c_void_p]),
+    "yv3_train_conv_wgrad_workspace_bytes": (c_size_t, [c_int] * 7),
+    "yv3_train_conv_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_size_t, c_void_p]),
+    "yv3_train_channel_workspace_bytes": (c_size_t, [c_longlong, c_int]),
+    "yv3_train_bn_stats": (c_int, [c_void_p, c_longlong, c_int, c_float, c_float] + [c_void_p] * 7 + [c_size_t, c_void_p]),
+    "yv3_train_bn_eval_stats": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p]),
+    "yv3_train_bn_act_fwd": (c_int, [c_void_p] * 7 + [c_longlong, c_int, c_void_p]),
+    "yv3_train_bn_act_bwd": (c_int, [c_void_p] * 9 + [c_longlong, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "yv3_train_bias_bwd": (c_int, [c_void_p] * 4 + [c_longlong, c_int, c_void_p, c_size_t, c_void_p]),
+    "yv3_train_add": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p]),
+    "yv3_train_upcat_bwd": (c_int, [c_void_p] * 3 + [c_int] * 7 + [c_void_p]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

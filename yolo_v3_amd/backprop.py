@@ -1,0 +1,306 @@
+"""Backpropagation of YoloNet's loss into every parameter (reference train.py: ``loss = net(inp, labels); loss.backward()``).
+
+``net.backprop = True`` routes ``net(x, target)`` here.  The step runs in exact fp32 on the kernels of csrc/train.hip, whatever
+``net.math_mode`` says (that attribute governs inference only):
+
+* forward: each conv_bn_relu is ``z = conv(x, w)`` (yv3_train_conv_fwd), the BatchNorm statistics (yv3_train_bn_stats: the batch's
+  mean and biased variance in ``.train()``, the running statistics in ``.eval()``) and ``y = leaky(bn(z)) [+ residual]``
+  (yv3_train_bn_act_fwd); a head conv is ``z = conv(x, w) + b``; the loss and dL/dlogits come from yv3_yolo_loss;
+* backward, in reverse order: dz from dy (yv3_train_bn_act_bwd, or yv3_train_bias_bwd for a head), dw (yv3_train_conv_wgrad)
+  and dx (yv3_train_conv_dgrad, plus yv3_train_upcat_bwd after an upsample).  Gradients of activations that fan out -- residual
+  skips, the route tails (Darknet layers 36 and 61) and the route heads -- are summed in a fixed order (yv3_train_add).
+
+One ``torch.autograd.Function`` covers the whole network: it takes the input and the parameters (``net.parameters()`` order, i.e.
+``state_dict`` order without the buffers) and keeps z, y and the statistics of every layer for the backward.  Backward stops at the
+first layer whose inputs need no gradient, e.g. at the backbone/head boundary when the backbone is frozen.  In ``.train()``
+the running statistics move as nn.BatchNorm2d moves them (momentum, unbiased variance, ``num_batches_tracked``)."""
+import torch
+import torch.nn as nn
+
+from . import _ffi
+from . import yololayer as _yl
+
+
+class _Op:
+    """One convolution of the net: the conv_bn_relu (or head nn.Conv2d) `module`, reading buffer `src` (and the low-resolution
+    `src2`, upsampled and concatenated in front of `src`, when cin_up > 0), writing buffer `out`; `res`: buffer added after the
+    activation."""
+    __slots__ = ("module", "conv", "bn", "head", "src", "src2", "cin_up", "res", "out", "head_idx")
+
+    def __init__(self, module, src, out, res=None, src2=None, cin_up=0, head_idx=None):
+        self.module, self.src, self.out, self.res, self.src2, self.cin_up, self.head_idx = module, src, out, res, src2, cin_up, head_idx
+        self.head = isinstance(module, nn.Conv2d)
+        self.conv = module if self.head else module.conv
+        self.bn = None if self.head else module.bn
+
+
+def graph(net):
+    """The net as a list of _Op in execution order (reference darknet.py:198-231)."""
+    from .darknet import res_layer
+    ops = []
+    feat = net.feature.mlist
+    ops.append(_Op(feat[0], "x", "f0"))
+    cur = "f0"
+    for pos in range(1, len(feat)):
+        m = feat[pos]
+        if isinstance(m, res_layer):
+            ops.append(_Op(m.conv1, cur, "f%da" % pos))
+            ops.append(_Op(m.conv2, "f%da" % pos, "f%d" % pos, res=cur))
+        else:
+            ops.append(_Op(m, cur, "f%d" % pos))
+        cur = "f%d" % pos
+    r61, r36 = "f%d" % net.feature.map2yolocfg[61], "f%d" % net.feature.map2yolocfg[36]
+
+    def predet(group, name, src, k, src2=None, cin_up=0):
+        prev = src
+        for i, m in enumerate(group.mlist[:-1]):
+            out = "%s.%d" % (name, i)
+            ops.append(_Op(m, prev, out, src2=src2 if i == 0 else None, cin_up=cin_up if i == 0 else 0))
+            prev = out
+        ops.append(_Op(group.mlist[-1], prev, "%s.logits" % name, head_idx=k))
+        return "%s.%d" % (name, group.getIdxFromYoloIdx(-3))
+
+    h1 = predet(net.pre_det1, "pre_det1", cur, 0)
+    ops.append(_Op(net.up1.conv, h1, "up1"))
+    h2 = predet(net.pre_det2, "pre_det2", r61, 1, src2="up1", cin_up=net.up1.conv.conv.out_channels)
+    ops.append(_Op(net.up2.conv, h2, "up2"))
+    predet(net.pre_det3, "pre_det3", r36, 2, src2="up2", cin_up=net.up2.conv.conv.out_channels)
+    return ops
+
+
+def _f32(t, what):
+    _ffi.require_cuda(t, what)
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise _ffi.Yv3Error("%s must be a contiguous fp32 tensor for the training path" % what)
+    return t.detach()
+
+
+class _Run:
+    """Forward state of one training step: what the backward needs."""
+
+    def __init__(self, net, x, target):
+        self.net, self.x, self.target = net, x, target
+        self.ops = graph(net)
+        self.saved = {}            # op index -> dict of tensors
+        self.shape = {}            # buffer -> (B, H, W, C)
+        self.need = {}             # buffer -> some parameter upstream of it needs a gradient
+        self.loss = None
+
+
+def _ws(nbytes, dev):
+    if nbytes == 0:
+        raise _ffi.Yv3Error("training kernel shape out of range")
+    return torch.empty(nbytes, device=dev, dtype=torch.uint8)
+
+
+def forward(run, want_grad):
+    """The training forward of the whole net, the loss and dL/dlogits; returns the loss (fp32 0-d GPU tensor) and sets net.stats."""
+    lib, s = _ffi.lib(), _ffi.stream_ptr()
+    net, x = run.net, run.x
+    B, _, H, W = x.shape
+    dev = x.device
+    bufs = {"x": x}
+    run.shape["x"] = (B, H, W, 3)
+    run.need["x"] = False
+    logits = [None] * 3
+    for i, op in enumerate(run.ops):
+        c = op.conv
+        cin, cout, k, st = c.in_channels, c.out_channels, c.kernel_size[0], c.stride[0]
+        b_, h, w, ct = run.shape[op.src]
+        if ct + op.cin_up != cin:
+            raise _ffi.Yv3Error("%s: %d input channels, expected %d" % (op.out, ct + op.cin_up, cin))
+        ho, wo = (h + 2 * ((k - 1) // 2) - k) // st + 1, (w + 2 * ((k - 1) // 2) - k) // st + 1
+        wt = _f32(c.weight, "weight of " + op.out)
+        params = [c.weight] + ([c.bias] if op.head else [op.bn.weight, op.bn.bias])
+        run.need[op.out] = any(p.requires_grad for p in params) or run.need[op.src] or \
+            (op.src2 is not None and run.need[op.src2]) or (op.res is not None and run.need[op.res])
+        sv = {}
+        wf = torch.empty(cout * cin * k * k, device=dev, dtype=torch.float32)
+        wd = torch.empty_like(wf) if want_grad else None
+        _ffi.check(lib.yv3_train_pack_weight(wt.data_ptr(), wf.data_ptr(), wd.data_ptr() if wd is not None else None,
+                                             cout, cin, k, s), "yv3_train_pack_weight")
+        z = torch.empty((b_, ho, wo, cout), device=dev, dtype=torch.float32)
+        bias = _f32(c.bias, "bias of " + op.out) if op.head else None
+        x2 = bufs[op.src2] if op.src2 is not None else None
+        _ffi.check(lib.yv3_train_conv_fwd(bufs[op.src].data_ptr(), x2.data_ptr() if x2 is not None else None, wf.data_ptr(),
+                                          bias.data_ptr() if bias is not None else None, z.data_ptr(), b_, h, w, cin, op.cin_up,
+                                          cout, k, st, int(op.src == "x"), s), "yv3_train_conv_fwd")
+        run.shape[op.out] = (b_, ho, wo, cout)
+        sv.update(wd=wd, geo=(b_, h, w, cin, cout, k, st))
+        if op.head:
+            bufs[op.out] = z
+            logits[op.head_idx] = (z, ho, wo)
+        else:
+            bn = op.bn
+            P = b_ * ho * wo
+            mean = torch.empty(cout, device=dev, dtype=torch.float32)
+            invstd = torch.empty_like(mean)
+            g, bt = _f32(bn.weight, "bn.weight of " + op.out), _f32(bn.bias, "bn.bias of " + op.out)
+            if bn.training:
+                rm, rv = _f32(bn.running_mean, "running_mean"), _f32(bn.running_var, "running_var")
+                with torch.no_grad():
+                    bn.num_batches_tracked.add_(1)
+                mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+                rm_new, rv_new = torch.empty_like(rm), torch.empty_like(rv)
+                nb = lib.yv3_train_channel_workspace_bytes(P, cout)
+                ws = _ws(nb, dev)
+                _ffi.check(lib.yv3_train_bn_stats(z.data_ptr(), P, cout, float(bn.eps), float(mom), rm.data_ptr(), rv.data_ptr(),
+                                                  rm_new.data_ptr(), rv_new.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
+                                                  ws.data_ptr(), nb, s), "yv3_train_bn_stats")
+                with torch.no_grad():          # (copy_ moves the buffers' _version: the inference engine re-packs)
+                    bn.running_mean.copy_(rm_new)
+                    bn.running_var.copy_(rv_new)
+            else:
+                _ffi.check(lib.yv3_train_bn_eval_stats(bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.eps),
+                                                       mean.data_ptr(), invstd.data_ptr(), cout, s), "yv3_train_bn_eval_stats")
+            y = torch.empty_like(z)
+            res = bufs[op.res] if op.res is not None else None
+            _ffi.check(lib.yv3_train_bn_act_fwd(z.data_ptr(), mean.data_ptr(), invstd.data_ptr(), g.data_ptr(), bt.data_ptr(),
+                                                res.data_ptr() if res is not None else None, y.data_ptr(), P, cout, s),
+                       "yv3_train_bn_act_fwd")
+            bufs[op.out] = y
+            sv.update(z=z, mean=mean, invstd=invstd, gamma=g, beta=bt, train=int(bn.training))
+        run.saved[i] = sv
+    if want_grad:
+        run.bufs = bufs
+    # the loss of the three heads (as YoloNet._loss), with dL/dlogits when a backward will follow
+    heads = (net.yolo1, net.yolo2, net.yolo3)
+    t = _yl.loss_target(run.target, B, dev)
+    out = torch.empty(3 * _yl.HEAD_OUT_BYTES, device=dev, dtype=torch.uint8)
+    run.dlogits = []
+    for kk, ((lg, hh, ww), head) in enumerate(zip(logits, heads)):
+        ld = lg.shape[-1]
+        gr = torch.empty_like(lg) if want_grad else None
+        _yl.launch_loss(lg, (hh * ww * ld, ld, 1), t, hh, ww, net.numClass, H, head.anchors_all, head.anchors_mask,
+                        out[kk * _yl.HEAD_OUT_BYTES:], gr)
+        run.dlogits.append(gr)
+    return net._loss_from_device(out, B, dev)
+
+
+def backward(run, grad_output):
+    """dL/dparameter for every parameter that requires grad, as {id(param): tensor}, for dL/dloss = grad_output."""
+    lib, s = _ffi.lib(), _ffi.stream_ptr()
+    dev = run.x.device
+    g = grad_output.detach().to(device=dev, dtype=torch.float32).reshape(()).contiguous()
+    grads = {}                 # buffer -> dL/dbuffer (NHWC fp32)
+    pg = {}
+
+    def give(buf, t):
+        """Add t into the gradient of buf (takes ownership of t when buf has none yet)."""
+        if buf in grads:
+            _ffi.check(lib.yv3_train_add(t.data_ptr(), grads[buf].data_ptr(), t.numel(), s), "yv3_train_add")
+        else:
+            grads[buf] = t
+
+    head_ops = {op.head_idx: op for op in run.ops if op.head}
+    for kk in range(3):
+        grads[head_ops[kk].out] = run.dlogits[kk]
+    for i in range(len(run.ops) - 1, -1, -1):
+        op, sv = run.ops[i], run.saved[i]
+        dy = grads.pop(op.out, None)
+        if dy is None or not run.need[op.out]:
+            continue
+        b_, h, w, cin, cout, k, st = sv["geo"]
+        _, ho, wo, _ = run.shape[op.out]
+        P = b_ * ho * wo
+        nb = lib.yv3_train_channel_workspace_bytes(P, cout)
+        ws = _ws(nb, dev)
+        dz = torch.empty_like(dy)
+        c = op.conv
+        if op.head:
+            db = torch.empty(cout, device=dev, dtype=torch.float32)
+            _ffi.check(lib.yv3_train_bias_bwd(dy.data_ptr(), g.data_ptr(), dz.data_ptr(), db.data_ptr(), P, cout, ws.data_ptr(), nb, s),
+                       "yv3_train_bias_bwd")
+            pg[id(c.bias)] = db
+        else:
+            dgam = torch.empty(cout, device=dev, dtype=torch.float32)
+            dbet = torch.empty_like(dgam)
+            _ffi.check(lib.yv3_train_bn_act_bwd(sv["z"].data_ptr(), dy.data_ptr(), sv["mean"].data_ptr(), sv["invstd"].data_ptr(),
+                                                sv["gamma"].data_ptr(), sv["beta"].data_ptr(), dz.data_ptr(), dgam.data_ptr(),
+                                                dbet.data_ptr(), P, cout, sv["train"], ws.data_ptr(), nb, s), "yv3_train_bn_act_bwd")
+            pg[id(op.bn.weight)], pg[id(op.bn.bias)] = dgam, dbet
+            if op.res is not None and run.need[op.res]:
+                give(op.res, dy)            # y = act(...) + res: dres = dy (dy is not read again)
+        if c.weight.requires_grad:
+            nw = lib.yv3_train_conv_wgrad_workspace_bytes(b_, h, w, cin, cout, k, st)
+            wsw = _ws(nw, dev)
+            dw = torch.empty_like(c.weight, dtype=torch.float32, memory_format=torch.contiguous_format)
+            x2 = run.bufs[op.src2] if op.src2 is not None else None
+            _ffi.check(lib.yv3_train_conv_wgrad(run.bufs[op.src].data_ptr(), x2.data_ptr() if x2 is not None else None, dz.data_ptr(),
+                                                dw.data_ptr(), b_, h, w, cin, op.cin_up, cout, k, st, int(op.src == "x"),
+                                                wsw.data_ptr(), nw, s), "yv3_train_conv_wgrad")
+            pg[id(c.weight)] = dw
+        need_src = run.need[op.src]
+        need_src2 = op.src2 is not None and run.need[op.src2]
+        if not (need_src or need_src2):
+            continue
+        if op.cin_up == 0:
+            acc = op.src in grads
+            dx = grads[op.src] if acc else torch.empty((b_, h, w, cin), device=dev, dtype=torch.float32)
+            _ffi.check(lib.yv3_train_conv_dgrad(dz.data_ptr(), sv["wd"].data_ptr(), dx.data_ptr(), b_, h, w, cin, cout, k, st,
+                                                int(acc), s), "yv3_train_conv_dgrad")
+            grads[op.src] = dx
+        else:
+            dcat = torch.empty((b_, h, w, cin), device=dev, dtype=torch.float32)
+            _ffi.check(lib.yv3_train_conv_dgrad(dz.data_ptr(), sv["wd"].data_ptr(), dcat.data_ptr(), b_, h, w, cin, cout, k, st, 0, s),
+                       "yv3_train_conv_dgrad")
+            ct = cin - op.cin_up
+            dlow = dtail = None
+            acc_low = acc_tail = 0
+            if need_src2:
+                acc_low = int(op.src2 in grads)
+                dlow = grads[op.src2] if acc_low else torch.empty((b_, h // 2, w // 2, op.cin_up), device=dev, dtype=torch.float32)
+                grads[op.src2] = dlow
+            if need_src:
+                acc_tail = int(op.src in grads)
+                dtail = grads[op.src] if acc_tail else torch.empty((b_, h, w, ct), device=dev, dtype=torch.float32)
+                grads[op.src] = dtail
+            _ffi.check(lib.yv3_train_upcat_bwd(dcat.data_ptr(), dlow.data_ptr() if dlow is not None else None,
+                                               dtail.data_ptr() if dtail is not None else None, b_, h, w, op.cin_up, ct,
+                                               acc_low, acc_tail, s), "yv3_train_upcat_bwd")
+    return pg
+
+
+class _TrainStep(torch.autograd.Function):
+    """loss = YoloNet(x, target) in training form; backward fills the parameters' gradients (one Function for the whole net)."""
+
+    @staticmethod
+    def forward(ctx, run, x, *params):
+        loss = forward(run, want_grad=True)
+        ctx.run = run
+        ctx.save_for_backward(*params)         # (an in-place change of a parameter before backward() then raises, as in torch)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        params = ctx.saved_tensors
+        run = ctx.run
+        ctx.run = None
+        with torch.cuda.device(run.x.device):
+            pg = backward(run, grad_output)
+        out = []
+        for i, p in enumerate(params):
+            gp = pg.get(id(p)) if ctx.needs_input_grad[2 + i] else None
+            out.append(gp.view_as(p) if gp is not None else None)
+        return (None, None) + tuple(out)
+
+
+def loss(net, x, target):
+    """net(x, target) with net.backprop = True (see the module docstring)."""
+    if not x.is_cuda:
+        raise _ffi.GpuOnlyError("input images must live on the GPU: this package runs only on MI355X (HIP kernels), "
+                                "there is no CPU path")
+    if x.requires_grad:
+        raise NotImplementedError("the training path does not compute the input gradient: pass x without requires_grad")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise _ffi.Yv3Error("input must be [B, 3, H, W], got %s" % (tuple(x.shape),))
+    if x.shape[2] % 32 or x.shape[3] % 32:
+        raise _ffi.Yv3Error("input height and width must be multiples of 32, got %dx%d" % (x.shape[2], x.shape[3]))
+    x = x.detach().float().contiguous()
+    params = list(net.parameters())
+    with torch.cuda.device(x.device):
+        run = _Run(net, x, target)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            return _TrainStep.apply(run, x, *params)
+        with torch.no_grad():
+            return forward(run, want_grad=False)

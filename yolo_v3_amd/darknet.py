@@ -10,16 +10,19 @@ fused upsample+concat, fused decode).  GPU only: a CPU tensor raises (no fallbac
 
 ``forward(x, target)`` (reference darknet.py:225-229 / yololayer.py:64-95) returns the summed
 loss and fills ``self.stats`` like the reference; the targets, masks and loss terms run on the
-GPU (csrc/yololoss.hip) on the head logits of a plan that materialises them.  The loss does not
-require grad: backpropagation into the parameters (BatchNorm in training mode, dgrad / wgrad of
-the 75 convolutions) is not provided.  ``YoloLayer`` gives the loss's gradient with respect to
-its head logits.
+GPU (csrc/yololoss.hip) on the head logits of a plan that materialises them.  By default the loss
+does not require grad.  With ``net.backprop = True`` it is a training step (yolo_v3_amd/backprop.py,
+csrc/train.hip): BatchNorm in the module's mode (batch statistics and running-stat updates in
+``.train()``), exact fp32 whatever ``math_mode`` says, and ``loss.backward()`` fills ``.grad`` of
+every parameter that requires grad.  ``YoloLayer`` gives the loss's gradient with respect to its
+head logits.
 """
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import _ffi, arch, engine as _engine
+from . import backprop as _backprop
 from . import yololayer as _yololayer
 from .yololayer import YoloLayer
 
@@ -277,6 +280,8 @@ class YoloNet(nn.Module):
         #   F32             exact fp32 MFMA                                    -- ~2.7x slower
         # _ffi.BF16 is the reduced-precision throughput mode (not a 1e-4 mode).
         self.math_mode = DEFAULT_MATH_MODE
+        # net(x, target) as a differentiable training step (yolo_v3_amd/backprop.py): False keeps the no-grad loss
+        self.backprop = False
 
     # ---- HIP execution
     def engine(self, dtype=None):
@@ -352,23 +357,30 @@ class YoloNet(nn.Module):
                 ld = lg.shape[-1]
                 _yololayer.launch_loss(lg, (hh * ww * ld, ld, 1), t, hh, ww, self.numClass, x.shape[2], head.anchors_all,
                                        head.anchors_mask, out[k * _yololayer.HEAD_OUT_BYTES:])
-            host = out.cpu().numpy()                      # (the one device->host read: the reference calls .item())
-            res = [_yololayer.head_results(host, k, B) for k in range(3)]
-            loss = np.float32(0.0)
-            for l, _ in res:
-                loss = np.float32(loss + l)               # sum(det) over the three heads, fp32
-            stats = [sum(r[1][i] for r in res) for i in range(9)]
-            self.stats = dict(zip(self.stat_keys, stats))
-            self.stats['recall'] = self.stats['nCorrect'] / self.stats['nGT'] if self.stats['nGT'] else 0
-            return torch.tensor(float(loss), dtype=torch.float32, device=x.device)
+            return self._loss_from_device(out, B, x.device)
+
+    def _loss_from_device(self, out, B, device):
+        """The three heads' loss outputs (``HEAD_OUT_BYTES`` each, on the GPU) -> the summed loss tensor; sets ``self.stats``."""
+        host = out.cpu().numpy()                      # (the one device->host read: the reference calls .item())
+        res = [_yololayer.head_results(host, k, B) for k in range(3)]
+        loss = np.float32(0.0)
+        for l, _ in res:
+            loss = np.float32(loss + l)               # sum(det) over the three heads, fp32
+        stats = [sum(r[1][i] for r in res) for i in range(9)]
+        self.stats = dict(zip(self.stat_keys, stats))
+        self.stats['recall'] = self.stats['nCorrect'] / self.stats['nGT'] if self.stats['nGT'] else 0
+        return torch.tensor(float(loss), dtype=torch.float32, device=device)
 
     def forward(self, x, target=None):
         """``forward(x)`` -> ``(det1, det2, det3)``.  ``forward(x, target)`` -> the summed loss of the three heads as a 0-d fp32
         GPU tensor, with ``self.stats`` set as the reference sets it (``loss, loss_x, loss_y, loss_w, loss_h, loss_conf,
         loss_cls``: per-head values / B summed over the heads; ``nCorrect``, ``nGT`` summed; ``recall``).  target: ``[B, T, 5]``
-        rows (cls, cx, cy, w, h), relative, zero-padded, on the CPU or the GPU.  The loss does not require grad:
-        backpropagation into the parameters is not provided (``YoloLayer`` gives dL/d head logits)."""
+        rows (cls, cx, cy, w, h), relative, zero-padded, on the CPU or the GPU.  With ``self.backprop`` False (the default)
+        the loss does not require grad; with ``self.backprop = True`` it is the training step of yolo_v3_amd.backprop (BatchNorm
+        in the module's mode, exact fp32) and ``loss.backward()`` fills every parameter's ``.grad``."""
         if target is not None:
+            if getattr(self, "backprop", False):
+                return _backprop.loss(self, x, target)
             return self._loss(x, target)
         dets, plan = self.engine().forward(x)
         r1, r2 = plan.rows[0], plan.rows[0] + plan.rows[1]
