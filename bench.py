@@ -2,7 +2,11 @@
 """Headline benchmark: YOLOv3 inference hot path on MI355X (BASELINE.json metric: images/sec + ms/img at
 416x416 bs=64 on 1/2/4/8 GPUs; NMS boxes delta vs ref).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64 | --global-batch G] [--size 416] [--dtype f32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64 | --global-batch G] [--size 416] [--dtype f32] [--full]
+
+A plain run measures the headline alone: it sets up, warms up, times the steps, writes --dump-outputs if given and prints the
+result line.  Everything that takes runs of its own -- the one-lane roofline pass, the PMC child passes, the other modes and
+configs, the PCIe passes, the CPU baseline and boxes_delta -- and the full-object side file belong to `--full`.
 
 A step = one pass of the whole hot path over one batch of synthetic images already resident in HBM, run through
 the PRODUCT entry points: `Detector.run_device` at N = 1 (yolo_v3_amd/detect.py: conv0 -> 74 convs with the YOLO decode
@@ -39,9 +43,9 @@ peak of the instruction's operand type (157.3 TFLOP/s fp32; 2500 for the 16-bit 
 `algorithmic_tflops` / `algorithmic_frac` = the direct form's 2*MAC over the same time (above 1 where Winograd saves more than the
 kernels lose).  Measured with ONE lane (the kernels alone on the chip); `roofline.two_lanes_section` is the rate of the
 concurrent section as the timed step runs it (all 75 convs' FLOPs over the fork -> join wall time, which also contains the lanes'
-filter + NMS).
+filter + NMS).  A plain run whose timed step runs two lanes has no one-lane pass: its `roofline` holds `two_lanes_section` alone.
 
-Extra objects on the same line (--no-extras skips them):
+Extra objects on the same line, --full only (--no-extras skips them):
   cpu_baseline   the CPU oracle (oracle/oracle_cpu.py: the reference path restated in torch fp32 CPU ops) timed on this
                  box's host cores on bounded samples (416x416 bs=8, 608x608 bs=4, the dog image
                  bs=1; forward / decode / post-processing split);
@@ -505,7 +509,7 @@ def live_traffic(roof, args, B, timeout_s=60, dtype=None, size=None, weights=Non
     for ctr in ("FETCH_SIZE", "WRITE_SIZE", "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE"):
         d = tempfile.mkdtemp(prefix="yv3_pmc_", dir="/tmp")
         cmd = [exe, "--pmc"] + ctr.split() + ["--kernel-trace", "--output-format", "csv", "-d", d, "-o", "t", "--", sys.executable,
-               os.path.abspath(__file__), "--lanes", "1", "--no-extras", "--no-cpu-baseline", "--no-live-traffic", "--steps", "3",
+               os.path.abspath(__file__), "--lanes", "1", "--steps", "3",                  # a plain run: the headline steps alone
                "--warmup", "1", "--batch", str(B), "--size", str(size), "--dtype", dtype, "--weights", weights,
                "--conf", str(conf), "--nms", str(nms)]
         try:
@@ -724,12 +728,15 @@ def main():
     ap.add_argument("--nms", type=float, default=0.4)
     ap.add_argument("--lanes", type=int, default=0, help="sub-batches run concurrently on separate HIP streams (0 = Detector's default: "
                     "2 when it measures a gain on this GPU, else 1)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra modes / configs measurements")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-live-traffic", action="store_true", help="do not run the two rocprofv3 --pmc passes for roofline.traffic "
+    ap.add_argument("--full", action="store_true", help="besides the headline, measure and check everything else: the one-lane roofline "
+                    "pass, the rocprofv3 --pmc passes, the other modes and configs, the PCIe passes, the CPU baseline and boxes_delta "
+                    "(about two minutes); the full object also goes to a side file, named by the line's `full`")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra modes / configs measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and boxes_delta")
+    ap.add_argument("--no-live-traffic", action="store_true", help="with --full: do not run the rocprofv3 --pmc passes for roofline.traffic "
                     "(~1 min, N=1 only); attach the committed summary of such passes instead")
-    ap.add_argument("--full-line", action="store_true", help="also print the FULL result object (modes, configs, per-rank table, notes; "
-                    "~20 KB) as an earlier stdout line; it is always written to gpurun_out/bench_full.json")
+    ap.add_argument("--full-line", action="store_true", help="also print the result object (with --full: modes, configs, per-rank table, "
+                    "notes; ~20 KB) as an earlier stdout line")
     ap.add_argument("--dry-run", action="store_true", help="launcher + collective rehearsal on CPU tensors (no GPU needed)")
     ap.add_argument("--weights", default="sw1", choices=["sw1", "dense", "eval"],
                     help="sw1: ~50-150 candidates/img; dense: ~1e4 rows/img pass conf (BASELINE configs[4]); eval: SW-eval")
@@ -741,6 +748,8 @@ def main():
         ap.error("--gpus must be >= 1")
     if args.steps < 1:
         ap.error("--steps must be >= 1")
+    if not args.full:                          # a plain run: the headline alone, every extra measurement is --full's
+        args.no_extras = args.no_cpu_baseline = args.no_live_traffic = True
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         relaunch_under_torchrun(args.gpus, args.dry_run)              # does not return
@@ -821,7 +830,7 @@ def main():
     # durations that sum to ~2x the wall time).  The two-lane section rate (FLOPs over wall) is reported next to it.
     lanes_used = main_w.det.lanes
     roof_w, head1 = main_w, head
-    if lanes_used > 1 and rank == 0:
+    if lanes_used > 1 and rank == 0 and args.full:
         # rank-local (world=1: no collective inside) and placed AFTER the last collective-bearing section of the run (configs "3"
         # above): the other ranks wait for rank 0 only in the final barrier, never inside a data-path collective
         roof_w = Workload(net, x, args.dtype, args.conf, args.nms, world=1, lanes=1)
@@ -829,9 +838,6 @@ def main():
         head1 = roof_w.summary(e1, min(args.steps, 10))
     out = None
     if rank == 0:
-        fa, fi, n_desc = roof_w.flops()
-        alg_bytes = roof_w.algorithmic_bytes()
-        st = head1["stages_ms"]
         out = {
             "metric": "images/sec (YOLOv3 forward + decode + NMS, %dx%d, bs=%d per GPU)" % (args.size, args.size, B),
             "value": head["value"], "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -846,29 +852,36 @@ def main():
                        "collective": ("1 x all_gather_into_tensor of [%d, %d, 7] fp32 per rank, backend %s" % (B, main_w.sd.cap + 1, dist.get_backend()))
                        if world > 1 else None,
                        "candidates_first_images": cand4, "boxes_kept_first_images": kept4},
-            "stages_ms": head["stages_ms"], "stages_note": head["stages_note"], "lanes": lanes_used,
+            "stages_ms": head["stages_ms"], "stages_note": head["stages_note"], "lanes": lanes_used, "roofline": {},
+        }
+        if roof_w.det.lanes == 1:                # (a plain run whose timed step runs two lanes has no one-lane pass)
+            fa, fi, n_desc = roof_w.flops()
+            alg_bytes = roof_w.algorithmic_bytes()
+            st = head1["stages_ms"]
             # the per-stage split that means what it says: consecutive stages of the ONE-lane pass (under two lanes everything from the
             # fork to the join is one concurrent section and the later marks are event order, not stage cost)
-            "stages_ms_one_lane": head1["stages_ms"],
-            "roofline": dict(head1["roofline"], traffic=None,
-                             algorithmic_bytes=round(alg_bytes / n_desc),
-                             **({"form_bytes": round(roof_w.form_bytes() / n_desc)} if args.dtype == "f32" else {}),
-                             conv_ms_per_step=st["convs"], avg_launch_ms=round(st["convs"] / n_desc, 5),
-                             flop_per_launch_avg=fi / n_desc,
-                             end_to_end_frac=round(fa / (head["ms_per_step"] * 1e-3) / 1e12 / PEAK_TFLOPS[args.dtype], 4)),
-        }
+            out["stages_ms_one_lane"] = head1["stages_ms"]
+            out["roofline"] = dict(head1["roofline"], traffic=None,
+                                   algorithmic_bytes=round(alg_bytes / n_desc),
+                                   **({"form_bytes": round(roof_w.form_bytes() / n_desc)} if args.dtype == "f32" else {}),
+                                   conv_ms_per_step=st["convs"], avg_launch_ms=round(st["convs"] / n_desc, 5),
+                                   flop_per_launch_avg=fi / n_desc,
+                                   end_to_end_frac=round(fa / (head["ms_per_step"] * 1e-3) / 1e12 / PEAK_TFLOPS[args.dtype], 4))
+            if lanes_used > 1:
+                out["roofline"]["measured_with"] = ("lanes=1 (%.2f images/s, %.3f ms/step): the kernels run alone, so HIP-event and rocprofv3 per-kernel "
+                                                    "durations mean what they say; the timed step above runs %d concurrent lanes"
+                                                    % (head1["value"], head1["ms_per_step"], lanes_used))
+            if args.no_live_traffic or world > 1 or not live_traffic(out["roofline"], args, B, dispatches_per_launch=roof_w.family_dispatches() / n_desc):
+                attach_traffic(out["roofline"], args.dtype, args.size, B, n_desc)
+            if args.dtype in ("f32x3", "f32h2"):
+                nm = {"f32x3": 6, "f32h2": 3}[args.dtype]
+                out["roofline"]["note"] = ("achieved = matrix-instruction FLOP/s issued (%d MFMAs per fp32 product) against the 2500 TFLOP/s dense 16-bit "
+                                           "peak; algorithmic_* = fp32 FLOP/s of the direct form against 2500 / %d; mfma_util / clock_ghz are the PMC reading"
+                                           % (nm, nm))
+                out["roofline"]["frac_vs_fp32_mfma_peak"] = round(out["roofline"]["algorithmic_tflops"] / PEAK_TFLOPS["f32"], 4)
         if lanes_used > 1:
-            out["roofline"]["measured_with"] = ("lanes=1 (%.2f images/s, %.3f ms/step): the kernels run alone, so HIP-event and rocprofv3 per-kernel durations "
-                                                "mean what they say; the timed step above runs %d concurrent lanes" % (head1["value"], head1["ms_per_step"], lanes_used))
-            out["roofline"]["two_lanes_section"] = {k: head["roofline"][k] for k in ("kernel", "achieved", "frac", "algorithmic_tflops", "algorithmic_frac", "launches",
-                                                                                  "winograd_launches", "winograd4_launches")}
-        if args.no_live_traffic or world > 1 or not live_traffic(out["roofline"], args, B, dispatches_per_launch=roof_w.family_dispatches() / n_desc):
-            attach_traffic(out["roofline"], args.dtype, args.size, B, n_desc)
-        if args.dtype in ("f32x3", "f32h2"):
-            nm = {"f32x3": 6, "f32h2": 3}[args.dtype]
-            out["roofline"]["note"] = ("achieved = matrix-instruction FLOP/s issued (%d MFMAs per fp32 product) against the 2500 TFLOP/s dense 16-bit peak; "
-                                       "algorithmic_* = fp32 FLOP/s of the direct form against 2500 / %d; mfma_util / clock_ghz are the PMC reading" % (nm, nm))
-            out["roofline"]["frac_vs_fp32_mfma_peak"] = round(out["roofline"]["algorithmic_tflops"] / PEAK_TFLOPS["f32"], 4)
+            out["roofline"]["two_lanes_section"] = {k: head["roofline"][k] for k in ("kernel", "achieved", "frac", "algorithmic_tflops", "algorithmic_frac",
+                                                                                  "launches", "winograd_launches", "winograd4_launches")}
         if cfg3 is not None:
             out.setdefault("configs", {})["3"] = cfg3
         out["ranks"] = ranks
@@ -1104,7 +1117,7 @@ def main():
             "max_abs_err_conf": float("%.3g" % d["max_abs_err_conf"]), "max_abs_err_score": float("%.3g" % d["max_abs_err_score"]),
             "tolerance": 1e-4}
     if rank == 0:
-        full_path = write_full(out, args)
+        full_path = write_full(out, args) if args.full else None
         if args.full_line:
             print(json.dumps(out))                                       # an EARLIER stdout line; the compact line stays the last one
         print(json.dumps(compact_line(out, full_path), separators=(",", ":")))

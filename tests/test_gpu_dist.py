@@ -88,7 +88,7 @@ def test_bench_two_ranks_on_this_gpu_over_gloo():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["YV3_DIST_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--batch", "8", "--steps", "3", "--warmup", "1",
-                        "--lanes", "1", "--no-extras"], cwd=repo, env=env, capture_output=True, text=True, timeout=900)
+                        "--lanes", "1", "--full", "--no-extras"], cwd=repo, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 2 and out["config"]["global_batch"] == 16 and out["config"]["parallelism"] == "dp2"

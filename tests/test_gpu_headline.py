@@ -293,3 +293,21 @@ def test_bench_dump_outputs_are_the_last_timed_step(sw1_sd, tmp_path):
     dl = boxes_delta([files["boxes"][i, :k] for i, k in enumerate(kept)], oc.postprocess(ref, 80, 0.5, 0.4), 2)
     print("bench --dump-outputs: %d sampled rows, max det err %.3g; boxes %s" % (rows.numel(), err, dl))
     assert dl["ref_boxes"] > 20 and dl["max_rel_err_coords"] <= TOL and dl["max_abs_err_conf"] <= TOL and dl["unmatched_frac"] <= 0.005, dl
+
+
+def test_bench_plain_run_is_the_headline_alone():
+    """``bench.py`` without ``--full`` on a two-lane step: one result line with the headline fields; its only roofline figure is the
+    rate of the timed two-lane section (the one-lane pass takes a run of its own), and none of the --full objects is there (other
+    modes, configs, PCIe passes, cpu_baseline, boxes_delta, the side file)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--batch", "4", "--lanes", "2", "--steps", "2", "--warmup", "1"],
+                       cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["value"] > 0 and out["ms_per_step"] > 0 and out["unit"] == "images/sec"
+    assert out["higher_is_better"] is True and out["dtype"].startswith("f32 (exact fp32") and out["config"]["lanes"] == 2
+    assert set(out["roofline"]) == {"two_lanes"} and out["roofline"]["two_lanes"]["achieved"] > 0
+    assert not {"stages_ms_one_lane", "cpu_baseline", "boxes_delta", "exact_f32", "f32h2", "f32x3", "bf16", "configs", "pcie_inclusive",
+                "full"} & set(out), sorted(out)

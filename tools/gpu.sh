@@ -5,6 +5,7 @@
 #
 #   tests  [pytest args]                      pytest -m gpu (default: the whole suite)            -> TAG_tests.log
 #   bench  [bench.py args]                    one bench.py run                                     -> TAG_bench.json / .err
+#   rehearse N NAME [bench.py args]           bench.py --gpus N over gloo: N ranks time-share the GPU (functional, not a measurement) -> TAG_NAME.json / .err
 #   benchab "LIB.." "ENV.." "bench args" [R]  same-box A/B: R (2) alternating passes over library builds (names given to
 #                                             tools/build_variant.sh; `base` = libyv3.so) x environment settings (`-` = none,
 #                                             e.g. "YV3_TUNE=0,8")                                 -> TAG_benchab.txt
@@ -31,7 +32,7 @@ bench)  timeout 900 python bench.py "$@" > $O/${TAG}_bench.json 2> $O/${TAG}_ben
 benchab) LIBS=$1; ENVS=$2; ARGS=$3; R=${4:-2}
         for rep in $(seq $R); do for l in $LIBS; do for e in $ENVS; do
           uselib $l; [ "$e" = - ] && e="YV3_NOP=1"
-          env $e python bench.py $ARGS --no-extras --no-cpu-baseline --no-live-traffic 2>/dev/null | tail -1 | line "$l $e | $ARGS | rep$rep" >> $O/${TAG}_benchab.txt
+          env $e python bench.py $ARGS --full --no-extras --no-cpu-baseline --no-live-traffic 2>/dev/null | tail -1 | line "$l $e | $ARGS | rep$rep" >> $O/${TAG}_benchab.txt
         done; done; done; unset YV3_LIB; cat $O/${TAG}_benchab.txt ;;
 tool)   LIBS=$1; S=$2; shift 2; ENVV=(); while [ "$1" != "--" ] && [ $# -gt 0 ]; do ENVV+=("$1"); shift; done; shift
         for l in $LIBS; do uselib $l; echo "=== $l ${ENVV[*]} $*" >> $O/${TAG}_$S.log
@@ -58,6 +59,8 @@ plan)   BS=$1; SIZE=$2; DT=$3; : > $O/${TAG}_plan_table.txt
           echo "=== $DT ${SIZE}x${SIZE} batch $b, one lane" >> $O/${TAG}_plan_table.txt
           python tools/trace_layers.py $t $b $SIZE $O/${TAG}_pl.json >> $O/${TAG}_plan_table.txt; rm -rf $O/${TAG}_pl
         done; cat $O/${TAG}_plan_table.txt ;;
+rehearse) N=$1; NAME=$2; shift 2
+        YV3_DIST_BACKEND=gloo timeout 900 python bench.py --gpus $N "$@" > $O/${TAG}_$NAME.json 2> $O/${TAG}_$NAME.err; tail -c 600 $O/${TAG}_$NAME.json ;;
 probe)  timeout 300 ./tools/probes/$1 > $O/${TAG}_$1.txt 2>&1; cat $O/${TAG}_$1.txt ;;
 *) echo "unknown command $CMD"; exit 2 ;;
 esac
