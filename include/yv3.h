@@ -382,6 +382,34 @@ int yv3_resize_linear(const unsigned char* img_hwc, int H, int W, float* out_chw
 int yv3_correct_boxes(const float* boxes, int B, int cap, int ld, const int* counts, const int* org_wh,
                       int img_w, int img_h, int is_letterbox, int out_xyxy, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training augmentation (reference transforms.py + custom_data_train.ipynb getTransforms(aug=True), csrc/augment.hip):
+ *   Compose([IaaAugmentations([iaa_hsv_aug(h, s, e), iaa_random_crop(j), iaa.Fliplr(0.5), IaaLetterbox(dim)]), ToTensor()])
+ * for B images in one call.  params [B][8] float64 = dhue, dsat, dexp, top, right, bottom, left, flip: the colour draws (read as
+ * float32 by the pixel pass), the signed CropAndPad side counts (positive pads with 128, negative crops; whole numbers) and the
+ * flip (0 or 1).  hw [B][2] int32 = source (H, W).  Per image, the checks a host cannot make without a synchronisation are made
+ * on the device, and each call writes status[b] for every image: 0, YV3_EINVAL (H or W <= 0, a source outside src_bytes, a
+ * non-finite parameter, dsat or dexp < 0, a fractional side, flip not 0 / 1) or YV3_ESHAPE (a crop leaves H1 = H + top + bottom
+ * or W1 = W + left + right below 1, or the letterboxed box has no pixel); such an image's outputs are zeros.  The return value
+ * covers the host arguments (YV3_EINVAL: null pointer, non-positive size; YV3_EWORKSPACE).  Nothing allocates or synchronises.
+ * Same cv2 caveat as yv3_letterbox (the resampling is the same fixed-point INTER_CUBIC).
+ * ------------------------------------------------------------------------------------------ */
+
+/* Bytes of workspace yv3_augment_images needs for src_bytes of packed sources (the colour-jittered copy; 0 if src_bytes <= 0). */
+size_t yv3_augment_workspace_bytes(long long src_bytes);
+
+/* Pixels, two launches.  src: packed uint8 RGB sources, image b = H*W*3 bytes at src + offsets[b] (int64, no alignment needed).
+ * out: fp32 [B][3][out_h][out_w] in [0,1].  workspace: >= yv3_augment_workspace_bytes(src_bytes) device bytes. */
+int yv3_augment_images(const unsigned char* src, long long src_bytes, const long long* offsets, const int* hw,
+                       const double* params, int B, float* out, int out_h, int out_w,
+                       void* workspace, size_t workspace_bytes, int* status, void* stream);
+
+/* Labels, one launch, float64 arithmetic.  labels [B][T][5] float64 rows (cls, cx, cy, w, h) relative to the source (NULL when
+ * T == 0); rows with w or h <= 0 (zero padding among them) are dropped, as label_np_to_bbs drops them.  target: fp32
+ * [B][max_rows][5], the first max_rows kept rows (cls, cx, cy, w, h relative to out_w x out_h) in input order, zero-filled. */
+int yv3_augment_labels(const double* labels, int B, int T, const int* hw, const double* params,
+                       float* target, int max_rows, int out_h, int out_w, int* status, void* stream);
+
 /* Stand-alone UpsampleGroup tail (reference darknet.py:159-162: ``F.interpolate(out, scale_factor=2, mode='nearest')`` then
  * ``torch.cat((out, route_tail), 1)``), NCHW fp32:  out[b, c, y, x] = up[b, c, y/2, x/2] for c < c_up, tail[b, c - c_up, y, x] beyond.
  * up [B, c_up, h, w], tail [B, c_tail, 2h, 2w], out [B, c_up + c_tail, 2h, 2w].  Pure data movement (bit-exact).  Inside YoloNet

@@ -1,0 +1,304 @@
+"""The reference's training augmentation for a whole batch on the GPU (csrc/augment.hip, three launches per batch).
+
+The reference builds each training sample on the host with imgaug 0.2.6 and cv2 (dataset.py:181-204, transforms.py, the
+notebook's ``getTransforms(aug=True)`` with darknet's yolov3 settings)::
+
+    Compose([IaaAugmentations([iaa_hsv_aug(0.1, 1.5, 1.5), iaa_random_crop(0.3), iaa.Fliplr(0.5), IaaLetterbox(dim)]),
+             ToTensor()])                                   # max_labels=90, max_label_cols=5
+
+Here the random draws are made on the host (``sample_params``: 8 float64 per image) and the pixels and labels are transformed by
+HIP kernels: ``augment_batch(images, labels, dim, params) -> (x [B,3,h,w], target [B,90,5])``, both fp32 on the GPU, ``target``
+in the form ``net(x, target)`` takes.  ``TrainBatches`` is a thin iterator over the reference's list file.
+
+Differences from the reference, all deliberate:
+  - crop and flip are drawn from a numpy stream of the image's seed (``sample_params``), not from imgaug's RNG, which cannot be
+    reproduced; the three colour draws are the reference's own (``np.random.seed(seed)``, then ``iaa_hsv_aug``'s order);
+  - cv2 is not a dependency: the colour conversions and the cubic resize restate OpenCV's 8-bit integer / fixed-point paths,
+    parity with a given cv2 build is unpinned (as for ``letterbox_batch``);
+  - the flip of a box uses imgaug 0.2.6's keypoint rule ``(width - 1) - x``, recalled from its source and not pinned by a test;
+  - one ``dim`` per batch (the reference may mix dims inside a batch; its collate then returns a list).
+Kept on purpose, as the reference does them: a hue sum below 0 clips to 0 and one from 180 to 255 wraps inside HSV2RGB; the pad
+after the colour step stays 128; a box partly cropped away is clipped only at the canvas; rows beyond 90 are dropped.
+"""
+import math
+import os
+import warnings
+
+import numpy as np
+import torch
+
+from . import _ffi
+
+MAX_LABELS = 90
+N_PARAMS = 8                 # dhue, dsat, dexp, top, right, bottom, left, flip
+_ALIGN = 256
+
+
+def _rand_scale(rng, s):
+    """reference transforms.py:81-85 (rand_scale) on the stream ``rng``."""
+    v = rng.uniform(1, s)
+    if rng.random_sample() < 0.5:
+        v = 1 / v
+    return v
+
+
+def sample_params(seeds, hue=0.1, saturation=1.5, exposure=1.5, jitter=0.3, flip=0.5, shapes=None):
+    """Per-image augmentation parameters ``[B,8]`` float64 on the CPU: dhue, dsat, dexp, top, right, bottom, left, flip.
+
+    For image ``i`` the numpy stream ``RandomState(seeds[i])`` -- the stream ``np.random.seed(seed)`` sets, as dataset.py:181-186
+    seeds it -- gives, in this order: ``dhue = uniform(-hue, hue) * 179``, ``dsat = rand_scale(saturation)``, ``dexp =
+    rand_scale(exposure)`` (transforms.py:77-104: the reference's own values), then the CropAndPad sides top, right, bottom, left,
+    each ``rint(uniform(-jitter, jitter) * n)`` with n = H for top / bottom and W for right / left (positive pads, negative crops;
+    ``keep_one_pixel`` gives crops back where they would leave no pixel),
+    and ``flip = random_sample() < flip``.  ``shapes``: the sources' ``(H, W)`` (or arrays, whose first two dims are used)."""
+    seeds = [int(s) for s in seeds]
+    if shapes is None:
+        raise ValueError("sample_params needs the sources' shapes (H, W) to size the crop / pad sides")
+    shapes = [tuple(int(v) for v in (s.shape if hasattr(s, "shape") else s)[:2]) for s in shapes]
+    if len(shapes) != len(seeds):
+        raise ValueError("one shape per seed")
+    out = np.zeros((len(seeds), N_PARAMS), dtype=np.float64)
+    for i, (seed, (H, W)) in enumerate(zip(seeds, shapes)):
+        rng = np.random.RandomState(seed)
+        out[i, 0] = rng.uniform(-hue, hue) * 179
+        out[i, 1] = _rand_scale(rng, saturation)
+        out[i, 2] = _rand_scale(rng, exposure)
+        for k, n in zip((3, 4, 5, 6), (H, W, H, W)):
+            out[i, k] = np.rint(rng.uniform(-jitter, jitter) * n)
+        out[i, 3], out[i, 5] = keep_one_pixel(out[i, 3], out[i, 5], H)
+        out[i, 6], out[i, 4] = keep_one_pixel(out[i, 6], out[i, 4], W)
+        out[i, 7] = 1.0 if rng.random_sample() < flip else 0.0
+    return out
+
+
+def keep_one_pixel(a, b, n):
+    """Two opposite sides of an n-pixel dimension, with crops given back one pixel at a time (the larger crop first) until at least
+    one pixel remains -- as imgaug's CropAndPad never crops an image to nothing.  Only tiny sources (n <= 3 at jitter 0.3) need it."""
+    while n + a + b < 1:
+        if a <= b:
+            a += 1
+        else:
+            b += 1
+    return a, b
+
+
+def letterbox_geometry(H1, W1, dim):
+    """IaaLetterbox._compute_height_width_pad (transforms.py:196-205) of an (H1, W1) image on a ``dim`` = (w, h) canvas:
+    (resize_w, resize_h, x_pad, y_pad)."""
+    out_w, out_h = dim
+    ratio = min(out_w / W1, out_h / H1)
+    rw, rh = int(W1 * ratio), int(H1 * ratio)
+    return rw, rh, (out_w - rw) // 2, (out_h - rh) // 2
+
+
+def check_params(params, shapes, dim):
+    """The per-image checks the kernels make on the device (csrc/augment.hip aug_geometry), in the same order, on the host:
+    raises ``Yv3Error`` with ``code`` YV3_EINVAL / YV3_ESHAPE before anything is launched."""
+    def fail(code, i, why):
+        err = _ffi.Yv3Error("augment: image %d: %s" % (i, why))
+        err.code = code
+        raise err
+    p = np.asarray(params, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != N_PARAMS or p.shape[0] != len(shapes):
+        raise ValueError("params must be [B,8] (one row per image)")
+    for i, ((H, W), r) in enumerate(zip(shapes, p)):
+        if H <= 0 or W <= 0:
+            fail(_ffi.EINVAL, i, "empty source")
+        if not np.all(np.isfinite(r)):
+            fail(_ffi.EINVAL, i, "non-finite parameter")
+        if r[1] < 0 or r[2] < 0:
+            fail(_ffi.EINVAL, i, "negative dsat / dexp")
+        if any(r[k] != np.rint(r[k]) or abs(r[k]) > 2 ** 30 for k in (3, 4, 5, 6)):
+            fail(_ffi.EINVAL, i, "crop / pad sides must be whole pixel counts")
+        if r[7] not in (0.0, 1.0):
+            fail(_ffi.EINVAL, i, "flip must be 0 or 1")
+        H1, W1 = H + int(r[3]) + int(r[5]), W + int(r[6]) + int(r[4])
+        if H1 < 1 or W1 < 1 or H1 > 2 ** 30 or W1 > 2 ** 30:
+            fail(_ffi.ESHAPE, i, "the crop leaves a %d x %d image" % (H1, W1))
+        rw, rh, _, _ = letterbox_geometry(H1, W1, dim)
+        if rw <= 0 or rh <= 0:
+            fail(_ffi.ESHAPE, i, "the letterboxed %d x %d image has no pixel on the canvas" % (H1, W1))
+
+
+class _Staging:
+    """Pinned host buffers for augment_batch's one upload, used in turn.  A buffer is rewritten only after the copy that last read
+    it has completed: waiting for that copy's event is the path's only host synchronisation."""
+
+    def __init__(self, n=2):
+        self.bufs, self.events, self.i = [None] * n, [None] * n, 0
+
+    def take(self, nbytes):
+        i = self.i
+        self.i = (i + 1) % len(self.bufs)
+        if self.events[i] is not None:
+            self.events[i].synchronize()
+            self.events[i] = None
+        if self.bufs[i] is None or self.bufs[i].numel() < nbytes:
+            self.bufs[i] = None
+            self.bufs[i] = torch.empty(max(1 << 20, 1 << (nbytes - 1).bit_length()), dtype=torch.uint8, pin_memory=True)
+        return i, self.bufs[i]
+
+    def release(self, i):
+        ev = torch.cuda.Event()
+        ev.record()
+        self.events[i] = ev
+
+
+_staging = {}
+
+
+def _round_up(n, a=_ALIGN):
+    return (n + a - 1) // a * a
+
+
+def _as_image(img):
+    t = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
+    if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise _ffi.Yv3Error("images must be uint8 [H,W,3] RGB")
+    return t
+
+
+def augment_batch(images, labels, dim, params, max_labels=MAX_LABELS):
+    """The training transform of a batch: ``(x [B,3,h,w] fp32, target [B,max_labels,5] fp32)``, both on the current GPU.
+
+    ``images``: list of uint8 RGB ``[H,W,3]`` numpy arrays or tensors (CPU or GPU), any sizes.  ``labels``: list of ``[n_i,5]``
+    arrays (cls, cx, cy, w, h relative to the source; n_i may be 0), or a zero-padded ``[B,T,5]`` tensor, or None.  ``dim`` =
+    (w, h).  ``params``: ``[B,8]`` float64 on the host (``sample_params``), checked here (``check_params``).
+
+    Host inputs (params, shapes, offsets, labels, host images) are packed into one pinned buffer and uploaded in one copy; GPU
+    images are copied on the device.  Three kernels follow: colour, crop / pad / flip / letterbox / ToTensor, labels.  Everything
+    is ordered on the current stream; the host waits only before a pinned buffer is reused (two are kept)."""
+    if not torch.cuda.is_available():
+        raise _ffi.Yv3Error("no GPU available: this package has no CPU path")
+    out_w, out_h = int(dim[0]), int(dim[1])
+    if out_w <= 0 or out_h <= 0 or max_labels <= 0:
+        raise ValueError("dim and max_labels must be positive")
+    imgs = [_as_image(im) for im in images]
+    B = len(imgs)
+    if B == 0:
+        raise ValueError("empty batch")
+    shapes = [(int(t.shape[0]), int(t.shape[1])) for t in imgs]
+    if isinstance(params, torch.Tensor):
+        if params.is_cuda:
+            raise _ffi.Yv3Error("params must be on the host (they are checked there before the launch)")
+        params = params.numpy()
+    params = np.ascontiguousarray(params, dtype=np.float64)
+    check_params(params, shapes, (out_w, out_h))
+
+    dev_labels, host_labels, T = None, None, 0
+    if isinstance(labels, torch.Tensor):
+        if labels.dim() != 3 or labels.shape[0] != B or labels.shape[2] != 5:
+            raise ValueError("padded labels must be [B,T,5]")
+        T = int(labels.shape[1])
+        if labels.is_cuda:
+            dev_labels = labels.to(torch.float64).contiguous()
+        else:
+            host_labels = labels.to(torch.float64).numpy()
+    elif labels is not None:
+        if len(labels) != B:
+            raise ValueError("one label array per image")
+        rows = [np.asarray(l, dtype=np.float64).reshape(-1, 5) for l in labels]
+        T = max(r.shape[0] for r in rows)
+        host_labels = np.zeros((B, T, 5), dtype=np.float64)
+        for b, r in enumerate(rows):
+            host_labels[b, :r.shape[0]] = r
+
+    # staging layout: params | offsets | hw | labels | images (each image 256-aligned)
+    o_par = 0
+    o_off = _round_up(o_par + B * N_PARAMS * 8)
+    o_hw = _round_up(o_off + B * 8)
+    o_lab = _round_up(o_hw + B * 8)
+    o_img = _round_up(o_lab + (host_labels.nbytes if host_labels is not None else 0))
+    offsets, pos = [], 0
+    for H, W in shapes:
+        offsets.append(pos)
+        pos = _round_up(pos + H * W * 3)
+    src_bytes = pos
+    host_img_bytes = sum(H * W * 3 for (H, W), t in zip(shapes, imgs) if not t.is_cuda)
+    total = o_img + src_bytes
+    upload = total if host_img_bytes else o_img
+
+    lib = _ffi.lib()
+    dev_index = torch.cuda.current_device()
+    staging = _staging.setdefault(dev_index, _Staging())
+    slot, buf = staging.take(upload)
+    host = buf.numpy()
+    host[o_par:o_par + params.nbytes].view(np.float64)[:] = params.reshape(-1)
+    host[o_off:o_off + B * 8].view(np.int64)[:] = offsets
+    host[o_hw:o_hw + B * 8].view(np.int32)[:] = np.asarray(shapes, dtype=np.int32).reshape(-1)
+    if host_labels is not None and host_labels.size:
+        host[o_lab:o_lab + host_labels.nbytes].view(np.float64)[:] = host_labels.reshape(-1)
+    for off, t in zip(offsets, imgs):
+        if not t.is_cuda:
+            n = t.numel()
+            host[o_img + off:o_img + off + n] = t.reshape(-1).numpy()
+    dev = torch.empty(total, dtype=torch.uint8, device="cuda")
+    dev[:upload].copy_(buf[:upload], non_blocking=True)
+    staging.release(slot)
+    for off, t in zip(offsets, imgs):
+        if t.is_cuda:
+            dev[o_img + off:o_img + off + t.numel()].copy_(t.reshape(-1))
+
+    base = dev.data_ptr()
+    x = torch.empty((B, 3, out_h, out_w), dtype=torch.float32, device="cuda")
+    target = torch.empty((B, max_labels, 5), dtype=torch.float32, device="cuda")
+    ws = torch.empty(max(1, lib.yv3_augment_workspace_bytes(src_bytes)), dtype=torch.uint8, device="cuda")
+    status = torch.empty((2, B), dtype=torch.int32, device="cuda")
+    s = _ffi.stream_ptr()
+    _ffi.check(lib.yv3_augment_images(base + o_img, src_bytes, base + o_off, base + o_hw, base + o_par, B,
+                                      x.data_ptr(), out_h, out_w, ws.data_ptr(), ws.numel(), status.data_ptr(), s),
+               "yv3_augment_images")
+    if dev_labels is not None:
+        lab_ptr = dev_labels.data_ptr() if T else None
+    else:
+        lab_ptr = base + o_lab if T else None
+    _ffi.check(lib.yv3_augment_labels(lab_ptr, B, T, base + o_hw, base + o_par, target.data_ptr(), max_labels, out_h, out_w,
+                                      status.data_ptr() + 4 * B, s), "yv3_augment_labels")
+    return x, target
+
+
+def label_path(img_path):
+    """reference dataset.py:175-179: the label file of an image."""
+    return img_path.replace('jpg', 'txt').replace('images', 'labels')
+
+
+def read_labels(path):
+    """``np.loadtxt(path).reshape(-1, 5)`` (dataset.py:199-200); a missing or empty file means no rows."""
+    if not os.path.exists(path):
+        return np.zeros((0, 5), dtype=np.float64)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")              # loadtxt warns on an empty file
+        return np.loadtxt(path, dtype=np.float64).reshape(-1, 5)
+
+
+class TrainBatches:
+    """Training batches ``(x, target)`` from the reference's list file (one image path per line).
+
+    Each epoch (each ``iter()``) draws a permutation (when ``shuffle``) and one seed per image from ``RandomState([seed, epoch])``;
+    images are decoded with ``evaluate.read_image_rgb``, labels read from the reference's label path (a missing file: no rows),
+    and every batch goes through ``sample_params(seeds, shapes=..., **aug)`` and ``augment_batch``.  The last batch may be smaller.
+    One ``dim`` = (w, h) for all batches."""
+
+    def __init__(self, list_file, batch_size, dim, seed, shuffle=True, max_labels=MAX_LABELS, **aug):
+        with open(list_file, 'r') as f:
+            self.img_list = [line.strip() for line in f.readlines() if line.strip()]
+        self.label_list = [label_path(p) for p in self.img_list]
+        self.batch_size, self.dim, self.seed, self.shuffle = int(batch_size), tuple(dim), int(seed), shuffle
+        self.max_labels, self.aug, self.epoch = max_labels, aug, 0
+
+    def __len__(self):
+        return math.ceil(len(self.img_list) / self.batch_size)
+
+    def __iter__(self):
+        from .evaluate import read_image_rgb
+        rng = np.random.RandomState([self.seed, self.epoch])
+        self.epoch += 1
+        n = len(self.img_list)
+        order = rng.permutation(n) if self.shuffle else np.arange(n)
+        seeds = rng.randint(0, 2 ** 31 - 1, size=n)
+        for i in range(0, n, self.batch_size):
+            idx = order[i:i + self.batch_size]
+            imgs = [read_image_rgb(self.img_list[j]) for j in idx]
+            labels = [read_labels(self.label_list[j]) for j in idx]
+            params = sample_params(seeds[i:i + len(idx)], shapes=imgs, **self.aug)
+            yield augment_batch(imgs, labels, self.dim, params, self.max_labels)
