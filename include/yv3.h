@@ -515,7 +515,7 @@ int yv3_yolo_loss(const yv3_yolo_loss_desc* desc, void* ws, size_t ws_bytes, voi
 
 /* ------------------------------------------------------------------------------------------
  * Training step (reference train.py: `loss = net(inp, labels); loss.backward()`, with darknet.py:27-53 in train mode), exact fp32
- * only (csrc/train.hip).  Activations and gradients are fp32 NHWC [B][H][W][C] (P = B*H*W rows of C), except the first layer's
+ * (csrc/train.hip; the bf16 counterparts of the convolution calls follow below).  Activations and gradients are fp32 NHWC [B][H][W][C] (P = B*H*W rows of C), except the first layer's
  * input, which is read in place as the caller's NCHW batch (x_nchw = 1).  Weights are torch's [cout][cin][k][k].  k is 1 or 3,
  * stride 1 or 2, padding (k-1)/2.  cin_up > 0: the input is cat(up2x(x2), x) along channels (reference darknet.py:161-162), read
  * in place: x2 is the low-resolution [B][H/2][W/2][cin_up] map, x the [B][H][W][cin-cin_up] route tail.  No call allocates or
@@ -572,6 +572,35 @@ int yv3_train_add(const float* src, float* dst, long long n, void* stream);
  * other ctail channels.  H, W: the full resolution; either output may be NULL. */
 int yv3_train_upcat_bwd(const float* dcat, float* dlow, float* dtail, int B, int H, int W, int cin_up, int ctail,
                         int acc_low, int acc_tail, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * BF16 training step (net.backprop_math = BF16, csrc/train_bf16.hip): the three convolution products above with both operands
+ * rounded to bf16 (round to nearest even, as torch's fp32 -> bf16 conversion) and fp32 accumulation; z, dx and dw stay fp32.
+ * bf16 tensors are passed as raw 16-bit images (void*).  coutp = cout rounded up to a multiple of 8: a bf16 dz has coutp
+ * channels, the padding ones zero (yv3_train_to_bf16 with ld = coutp).  Except on the first layer (x_nchw = 1), cin and cin_up
+ * must be multiples of 8 (YV3_ESHAPE otherwise).  Errors, determinism and the absence of allocation / synchronisation are as for
+ * the fp32 calls.
+ * ------------------------------------------------------------------------------------------ */
+
+/* dst[r][c] = bf16(src[r][c]) for c < C, 0 for C <= c < ld (rows of C fp32 in, rows of ld bf16 out).  NaN -> 0x7fc0. */
+int yv3_train_to_bf16(const float* src, void* dst, long long rows, int C, int ld, void* stream);
+
+/* wf (optional): [coutp][k*k*cin] bf16 (K index tap*cin + ci), wd (optional): [cin][k*k*coutp] bf16 (K index tap*coutp + co);
+ * padding channels zero -- the operand images of yv3_train_conv_fwd_bf16 / _dgrad_bf16. */
+int yv3_train_pack_weight_bf16(const float* w, void* wf, void* wd, int cout, int cin, int k, void* stream);
+
+/* z = conv(bf16 x, bf16 w) [+ bias], fp32 [B][Ho][Wo][cout]; x, x2 as yv3_train_conv_fwd's, in bf16. */
+int yv3_train_conv_fwd_bf16(const void* x, const void* x2, const void* wf, const float* bias, float* z,
+                            int B, int H, int W, int cin, int cin_up, int cout, int k, int stride, int x_nchw, void* stream);
+
+/* dx (+)= dL/dx for the bf16 dz ([B][Ho][Wo][coutp]); dx fp32 [B][H][W][cin]. */
+int yv3_train_conv_dgrad_bf16(const void* dz, const void* wd, float* dx, int B, int H, int W, int cin, int cout, int k, int stride,
+                              int accumulate, void* stream);
+
+/* dw = dL/dw (fp32 [cout][cin][k][k]) from bf16 x and dz ([B][Ho][Wo][coutp]); fp32 split partials summed in split order in fp64. */
+size_t yv3_train_conv_wgrad_bf16_workspace_bytes(int B, int H, int W, int cin, int cout, int k, int stride);
+int yv3_train_conv_wgrad_bf16(const void* x, const void* x2, const void* dz, float* dw, int B, int H, int W, int cin, int cin_up,
+                              int cout, int k, int stride, int x_nchw, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,8 +1,10 @@
-"""Time one training step at 416x416 (net(x, target) + loss.backward(), net.backprop = True, .train()) at bs=8 and bs=16, against the
-same network run by torch's own modules in fp32 (F.conv2d / F.batch_norm on MIOpen, tests/train_ref.forward) in the same process.
-7 interleaved rounds, median reported; then one profiled step of ours split by kernel class.
+"""Time one training step at 416x416 (net(x, target) + loss.backward(), net.backprop = True, .train()) at bs=8 and bs=16, for each
+net.backprop_math in --math (f32: exact fp32; bf16: bf16 convolution operands), against the same network run by torch's own modules
+in fp32 (F.conv2d / F.batch_norm on MIOpen, tests/train_ref.forward) and, with bf16 in --math, the same under
+torch.autocast("cuda", torch.bfloat16), all in the same process.  7 interleaved rounds, median reported; then one profiled step of
+each of ours split by kernel class (conv classes also in TFLOP/s of the products they compute).
 
-    python tools/train_bench.py [--batches 8 16] [--rounds 7]
+    python tools/train_bench.py [--batches 8 16] [--rounds 7] [--math f32 bf16]
 """
 import argparse
 import json
@@ -19,7 +21,7 @@ sys.path.insert(0, REPO)
 from tests import train_ref as T                      # noqa: E402
 from tests import yolo_loss_ref as R                  # noqa: E402
 from tests.helpers import trained_like_stream         # noqa: E402
-from yolo_v3_amd import YoloNet, WeightManager, synth  # noqa: E402
+from yolo_v3_amd import YoloNet, WeightManager, synth, arch, F32, BF16  # noqa: E402
 
 DEV = "cuda:0"
 
@@ -40,17 +42,28 @@ def kernel_classes(fn):
     cls = {}
     for ev in prof.key_averages():
         n = ev.key
-        k = ("conv fwd" if "conv_gemm<0>" in n else "conv dgrad" if "conv_gemm<1>" in n else "conv wgrad" if "conv_gemm<2>" in n
-             or "wgrad_reduce" in n else "BN / act" if any(s in n for s in ("channel_partials", "finalize", "bn_act", "eval_stats"))
+        k = ("conv fwd" if "conv_gemm<0>" in n or "conv_bf16<0," in n else "conv dgrad" if "conv_gemm<1>" in n or "conv_bf16<1," in n
+             else "conv wgrad" if "conv_gemm<2>" in n or "conv_bf16<2," in n or "wgrad_reduce" in n
+             else "cast" if "to_bf16" in n else "weight pack" if "pack_weight" in n
+             else "BN / act" if any(s in n for s in ("channel_partials", "finalize", "bn_act", "eval_stats"))
              else "loss" if "yolo" in n.lower() or "loss" in n.lower() else "other")
         cls[k] = cls.get(k, 0.0) + getattr(ev, "device_time_total", getattr(ev, "cuda_time_total", 0.0)) / 1e3
     return {k: round(v, 3) for k, v in sorted(cls.items())}
+
+
+def step_gflop(B, size=416):
+    """GFLOP of one forward's convolutions (2 M N K over all layers); dgrad and wgrad compute the same products once more each."""
+    tot = 0
+    for sp, (ho, wo) in zip(arch.conv_specs(80), arch.conv_output_hw(size, 80)):
+        tot += 2 * B * ho * wo * sp.cout * sp.cin * sp.k * sp.k
+    return tot / 1e9
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[8, 16])
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--math", nargs="+", choices=("f32", "bf16"), default=["f32"])
     a = ap.parse_args()
     net = YoloNet((416, 416), numClass=80)
     WeightManager(net).load_stream(trained_like_stream(80))
@@ -62,24 +75,45 @@ def main():
         x = torch.from_numpy(synth.images(B, 416, 7)).to(DEV)
         tg = torch.from_numpy(R.random_rows(5, B, 30, 80, (0.03, 0.8)))
 
-        def ours():
-            net.zero_grad(set_to_none=True)
-            net(x, tg).backward()
+        def ours(math):
+            def step():
+                net.backprop_math = math
+                net.zero_grad(set_to_none=True)
+                net(x, tg).backward()
+            return step
 
         def torch_modules():
             logits, _, _ = T.forward(sd_gpu, x, True, torch.float32)
             torch.autograd.backward(logits, [torch.ones_like(l) * 1e-3 for l in logits])
 
-        ours(); torch_modules()
-        t_ours, t_torch = [], []
+        def torch_autocast():
+            with torch.autocast("cuda", torch.bfloat16):
+                logits, _, _ = T.forward(sd_gpu, x, True, torch.float32)
+            torch.autograd.backward(logits, [torch.ones_like(l) * 1e-3 for l in logits])
+
+        fns = {"ours_f32_ms": ours(F32)} if "f32" in a.math else {}
+        if "bf16" in a.math:
+            fns["ours_bf16_ms"] = ours(BF16)
+        fns["torch_miopen_fp32_ms"] = torch_modules
+        if "bf16" in a.math:
+            fns["torch_autocast_bf16_ms"] = torch_autocast
+        for f in fns.values():
+            f()
+        times = {k: [] for k in fns}
         for _ in range(a.rounds):
-            t_ours.append(timed(ours))
-            t_torch.append(timed(torch_modules))
-        out[B] = dict(ours_ms=float(np.median(t_ours)), torch_miopen_fp32_ms=float(np.median(t_torch)))
-        try:
-            out[B]["ours_by_kernel_class_ms"] = kernel_classes(ours)
-        except Exception as e:                       # (the profiler is a diagnostic only)
-            out[B]["ours_by_kernel_class_ms"] = "profiler unavailable: %s" % e
+            for k, f in fns.items():
+                times[k].append(timed(f))
+        out[B] = {k: float(np.median(v)) for k, v in times.items()}
+        gf = step_gflop(B)
+        for m in a.math:
+            key = "ours_%s_by_kernel_class_ms" % m
+            try:
+                cls = kernel_classes(fns["ours_%s_ms" % m])
+                out[B][key] = cls
+                out[B]["ours_%s_conv_tflops" % m] = {c: round(gf / cls[c], 1) for c in ("conv fwd", "conv dgrad", "conv wgrad")
+                                                     if cls.get(c)}
+            except Exception as e:                   # (the profiler is a diagnostic only)
+                out[B][key] = "profiler unavailable: %s" % e
         print(B, json.dumps(out[B]), flush=True)
     print(json.dumps(out))
 

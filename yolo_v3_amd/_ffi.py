@@ -131,6 +131,12 @@ _SIGNATURES = {
     "yv3_train_bias_bwd": (c_int, [c_void_p] * 4 + [c_longlong, c_int, c_void_p, c_size_t, c_void_p]),
     "yv3_train_add": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p]),
     "yv3_train_upcat_bwd": (c_int, [c_void_p] * 3 + [c_int] * 7 + [c_void_p]),
+    "yv3_train_to_bf16": (c_int, [c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p]),
+    "yv3_train_pack_weight_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "yv3_train_conv_fwd_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
+    "yv3_train_conv_dgrad_bf16": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 8 + [c_void_p]),
+    "yv3_train_conv_wgrad_bf16_workspace_bytes": (c_size_t, [c_int] * 7),
+    "yv3_train_conv_wgrad_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_size_t, c_void_p]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -1,7 +1,10 @@
 """Backpropagation of YoloNet's loss into every parameter (reference train.py: ``loss = net(inp, labels); loss.backward()``).
 
-``net.backprop = True`` routes ``net(x, target)`` here.  The step runs in exact fp32 on the kernels of csrc/train.hip, whatever
-``net.math_mode`` says (that attribute governs inference only):
+``net.backprop = True`` routes ``net(x, target)`` here.  ``net.backprop_math`` picks the arithmetic of the convolutions (``net.math_mode``
+governs inference only): ``F32`` (the default) runs the step in exact fp32 on the kernels of csrc/train.hip; ``BF16`` rounds the two
+operands of every convolution product to bf16 (forward: x and w; dgrad: dz and w; wgrad: x and dz) and accumulates in fp32 on the
+kernels of csrc/train_bf16.hip, with z, dx and dw in fp32 and everything else exactly as in F32.  The steps below name the F32 calls;
+BF16 uses their ``_bf16`` counterparts and keeps a bf16 copy (yv3_train_to_bf16) of each conv input and each dz beside the fp32 one:
 
 * forward: each conv_bn_relu is ``z = conv(x, w)`` (yv3_train_conv_fwd), the BatchNorm statistics (yv3_train_bn_stats: the batch's
   mean and biased variance in ``.train()``, the running statistics in ``.eval()``) and ``y = leaky(bn(z)) [+ residual]``
@@ -14,6 +17,8 @@ One ``torch.autograd.Function`` covers the whole network: it takes the input and
 ``state_dict`` order without the buffers) and keeps z, y and the statistics of every layer for the backward.  Backward stops at the
 first layer whose inputs need no gradient, e.g. at the backbone/head boundary when the backbone is frozen.  In ``.train()``
 the running statistics move as nn.BatchNorm2d moves them (momentum, unbiased variance, ``num_batches_tracked``)."""
+import numbers
+
 import torch
 import torch.nn as nn
 
@@ -75,11 +80,32 @@ def _f32(t, what):
     return t.detach()
 
 
+def _round8(c):
+    return (c + 7) & ~7
+
+
+def backprop_math(net):
+    """net.backprop_math, checked: F32 or BF16, else Yv3Error (YV3_EINVAL)."""
+    m = getattr(net, "backprop_math", _ffi.F32)
+    if not isinstance(m, numbers.Integral) or isinstance(m, bool) or m not in (_ffi.F32, _ffi.BF16):
+        err = _ffi.Yv3Error("net.backprop_math must be yolo_v3_amd.F32 or yolo_v3_amd.BF16, got %r" % (m,))
+        err.code = _ffi.EINVAL
+        raise err
+    return int(m)
+
+
+def _bf16(lib, s, t, rows, C, ld, what):
+    """A bf16 copy (int16 storage) of the fp32 tensor t seen as rows x C, padded with zero channels to ld."""
+    out = torch.empty(rows * ld, device=t.device, dtype=torch.int16)
+    _ffi.check(lib.yv3_train_to_bf16(t.data_ptr(), out.data_ptr(), rows, C, ld, s), "yv3_train_to_bf16 (%s)" % what)
+    return out
+
+
 class _Run:
     """Forward state of one training step: what the backward needs."""
 
-    def __init__(self, net, x, target):
-        self.net, self.x, self.target = net, x, target
+    def __init__(self, net, x, target, math=_ffi.F32):
+        self.net, self.x, self.target, self.math = net, x, target, math
         self.ops = graph(net)
         self.saved = {}            # op index -> dict of tensors
         self.shape = {}            # buffer -> (B, H, W, C)
@@ -100,6 +126,8 @@ def forward(run, want_grad):
     B, _, H, W = x.shape
     dev = x.device
     bufs = {"x": x}
+    bf = run.math == _ffi.BF16
+    bufs_b = {"x": _bf16(lib, s, x, x.numel(), 1, 1, "x")} if bf else None      # bf16 copies of the conv inputs (BF16)
     run.shape["x"] = (B, H, W, 3)
     run.need["x"] = False
     logits = [None] * 3
@@ -115,16 +143,26 @@ def forward(run, want_grad):
         run.need[op.out] = any(p.requires_grad for p in params) or run.need[op.src] or \
             (op.src2 is not None and run.need[op.src2]) or (op.res is not None and run.need[op.res])
         sv = {}
-        wf = torch.empty(cout * cin * k * k, device=dev, dtype=torch.float32)
-        wd = torch.empty_like(wf) if want_grad else None
-        _ffi.check(lib.yv3_train_pack_weight(wt.data_ptr(), wf.data_ptr(), wd.data_ptr() if wd is not None else None,
-                                             cout, cin, k, s), "yv3_train_pack_weight")
         z = torch.empty((b_, ho, wo, cout), device=dev, dtype=torch.float32)
         bias = _f32(c.bias, "bias of " + op.out) if op.head else None
-        x2 = bufs[op.src2] if op.src2 is not None else None
-        _ffi.check(lib.yv3_train_conv_fwd(bufs[op.src].data_ptr(), x2.data_ptr() if x2 is not None else None, wf.data_ptr(),
-                                          bias.data_ptr() if bias is not None else None, z.data_ptr(), b_, h, w, cin, op.cin_up,
-                                          cout, k, st, int(op.src == "x"), s), "yv3_train_conv_fwd")
+        if bf:
+            wf = torch.empty(_round8(cout) * cin * k * k, device=dev, dtype=torch.int16)
+            wd = torch.empty_like(wf) if want_grad else None
+            _ffi.check(lib.yv3_train_pack_weight_bf16(wt.data_ptr(), wf.data_ptr(), wd.data_ptr() if wd is not None else None,
+                                                      cout, cin, k, s), "yv3_train_pack_weight_bf16")
+            x2 = bufs_b[op.src2] if op.src2 is not None else None
+            _ffi.check(lib.yv3_train_conv_fwd_bf16(bufs_b[op.src].data_ptr(), x2.data_ptr() if x2 is not None else None, wf.data_ptr(),
+                                                   bias.data_ptr() if bias is not None else None, z.data_ptr(), b_, h, w, cin,
+                                                   op.cin_up, cout, k, st, int(op.src == "x"), s), "yv3_train_conv_fwd_bf16")
+        else:
+            wf = torch.empty(cout * cin * k * k, device=dev, dtype=torch.float32)
+            wd = torch.empty_like(wf) if want_grad else None
+            _ffi.check(lib.yv3_train_pack_weight(wt.data_ptr(), wf.data_ptr(), wd.data_ptr() if wd is not None else None,
+                                                 cout, cin, k, s), "yv3_train_pack_weight")
+            x2 = bufs[op.src2] if op.src2 is not None else None
+            _ffi.check(lib.yv3_train_conv_fwd(bufs[op.src].data_ptr(), x2.data_ptr() if x2 is not None else None, wf.data_ptr(),
+                                              bias.data_ptr() if bias is not None else None, z.data_ptr(), b_, h, w, cin, op.cin_up,
+                                              cout, k, st, int(op.src == "x"), s), "yv3_train_conv_fwd")
         run.shape[op.out] = (b_, ho, wo, cout)
         sv.update(wd=wd, geo=(b_, h, w, cin, cout, k, st))
         if op.head:
@@ -159,10 +197,13 @@ def forward(run, want_grad):
                                                 res.data_ptr() if res is not None else None, y.data_ptr(), P, cout, s),
                        "yv3_train_bn_act_fwd")
             bufs[op.out] = y
+            if bf:                             # (every conv_bn_relu output is some conv's input)
+                bufs_b[op.out] = _bf16(lib, s, y, P, cout, cout, op.out)
             sv.update(z=z, mean=mean, invstd=invstd, gamma=g, beta=bt, train=int(bn.training))
         run.saved[i] = sv
     if want_grad:
         run.bufs = bufs
+        run.bufs_b = bufs_b
     # the loss of the three heads (as YoloNet._loss), with dL/dlogits when a backward will follow
     heads = (net.yolo1, net.yolo2, net.yolo3)
     t = _yl.loss_target(run.target, B, dev)
@@ -181,6 +222,7 @@ def backward(run, grad_output):
     """dL/dparameter for every parameter that requires grad, as {id(param): tensor}, for dL/dloss = grad_output."""
     lib, s = _ffi.lib(), _ffi.stream_ptr()
     dev = run.x.device
+    bf = run.math == _ffi.BF16
     g = grad_output.detach().to(device=dev, dtype=torch.float32).reshape(()).contiguous()
     grads = {}                 # buffer -> dL/dbuffer (NHWC fp32)
     pg = {}
@@ -221,29 +263,46 @@ def backward(run, grad_output):
             pg[id(op.bn.weight)], pg[id(op.bn.bias)] = dgam, dbet
             if op.res is not None and run.need[op.res]:
                 give(op.res, dy)            # y = act(...) + res: dres = dy (dy is not read again)
-        if c.weight.requires_grad:
-            nw = lib.yv3_train_conv_wgrad_workspace_bytes(b_, h, w, cin, cout, k, st)
-            wsw = _ws(nw, dev)
-            dw = torch.empty_like(c.weight, dtype=torch.float32, memory_format=torch.contiguous_format)
-            x2 = run.bufs[op.src2] if op.src2 is not None else None
-            _ffi.check(lib.yv3_train_conv_wgrad(run.bufs[op.src].data_ptr(), x2.data_ptr() if x2 is not None else None, dz.data_ptr(),
-                                                dw.data_ptr(), b_, h, w, cin, op.cin_up, cout, k, st, int(op.src == "x"),
-                                                wsw.data_ptr(), nw, s), "yv3_train_conv_wgrad")
-            pg[id(c.weight)] = dw
         need_src = run.need[op.src]
         need_src2 = op.src2 is not None and run.need[op.src2]
+        if bf:
+            dzb = _bf16(lib, s, dz, P, cout, _round8(cout), "dz of " + op.out)
+        if c.weight.requires_grad:
+            dw = torch.empty_like(c.weight, dtype=torch.float32, memory_format=torch.contiguous_format)
+            if bf:
+                nw = lib.yv3_train_conv_wgrad_bf16_workspace_bytes(b_, h, w, cin, cout, k, st)
+                wsw = _ws(nw, dev)
+                x2 = run.bufs_b[op.src2] if op.src2 is not None else None
+                _ffi.check(lib.yv3_train_conv_wgrad_bf16(run.bufs_b[op.src].data_ptr(), x2.data_ptr() if x2 is not None else None,
+                                                         dzb.data_ptr(), dw.data_ptr(), b_, h, w, cin, op.cin_up, cout, k, st,
+                                                         int(op.src == "x"), wsw.data_ptr(), nw, s), "yv3_train_conv_wgrad_bf16")
+            else:
+                nw = lib.yv3_train_conv_wgrad_workspace_bytes(b_, h, w, cin, cout, k, st)
+                wsw = _ws(nw, dev)
+                x2 = run.bufs[op.src2] if op.src2 is not None else None
+                _ffi.check(lib.yv3_train_conv_wgrad(run.bufs[op.src].data_ptr(), x2.data_ptr() if x2 is not None else None,
+                                                    dz.data_ptr(), dw.data_ptr(), b_, h, w, cin, op.cin_up, cout, k, st,
+                                                    int(op.src == "x"), wsw.data_ptr(), nw, s), "yv3_train_conv_wgrad")
+            pg[id(c.weight)] = dw
         if not (need_src or need_src2):
             continue
+
+        def dgrad(dx, acc):
+            if bf:
+                _ffi.check(lib.yv3_train_conv_dgrad_bf16(dzb.data_ptr(), sv["wd"].data_ptr(), dx.data_ptr(), b_, h, w, cin, cout, k, st,
+                                                         int(acc), s), "yv3_train_conv_dgrad_bf16")
+            else:
+                _ffi.check(lib.yv3_train_conv_dgrad(dz.data_ptr(), sv["wd"].data_ptr(), dx.data_ptr(), b_, h, w, cin, cout, k, st,
+                                                    int(acc), s), "yv3_train_conv_dgrad")
+
         if op.cin_up == 0:
             acc = op.src in grads
             dx = grads[op.src] if acc else torch.empty((b_, h, w, cin), device=dev, dtype=torch.float32)
-            _ffi.check(lib.yv3_train_conv_dgrad(dz.data_ptr(), sv["wd"].data_ptr(), dx.data_ptr(), b_, h, w, cin, cout, k, st,
-                                                int(acc), s), "yv3_train_conv_dgrad")
+            dgrad(dx, acc)
             grads[op.src] = dx
         else:
             dcat = torch.empty((b_, h, w, cin), device=dev, dtype=torch.float32)
-            _ffi.check(lib.yv3_train_conv_dgrad(dz.data_ptr(), sv["wd"].data_ptr(), dcat.data_ptr(), b_, h, w, cin, cout, k, st, 0, s),
-                       "yv3_train_conv_dgrad")
+            dgrad(dcat, False)
             ct = cin - op.cin_up
             dlow = dtail = None
             acc_low = acc_tail = 0
@@ -287,6 +346,7 @@ class _TrainStep(torch.autograd.Function):
 
 def loss(net, x, target):
     """net(x, target) with net.backprop = True (see the module docstring)."""
+    math = backprop_math(net)
     if not x.is_cuda:
         raise _ffi.GpuOnlyError("input images must live on the GPU: this package runs only on MI355X (HIP kernels), "
                                 "there is no CPU path")
@@ -299,7 +359,7 @@ def loss(net, x, target):
     x = x.detach().float().contiguous()
     params = list(net.parameters())
     with torch.cuda.device(x.device):
-        run = _Run(net, x, target)
+        run = _Run(net, x, target, math)
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
             return _TrainStep.apply(run, x, *params)
         with torch.no_grad():

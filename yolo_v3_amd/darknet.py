@@ -13,7 +13,8 @@ loss and fills ``self.stats`` like the reference; the targets, masks and loss te
 GPU (csrc/yololoss.hip) on the head logits of a plan that materialises them.  By default the loss
 does not require grad.  With ``net.backprop = True`` it is a training step (yolo_v3_amd/backprop.py,
 csrc/train.hip): BatchNorm in the module's mode (batch statistics and running-stat updates in
-``.train()``), exact fp32 whatever ``math_mode`` says, and ``loss.backward()`` fills ``.grad`` of
+``.train()``), exact fp32 whatever ``math_mode`` says (``net.backprop_math = BF16``: bf16 convolution operands with fp32
+accumulation, csrc/train_bf16.hip), and ``loss.backward()`` fills ``.grad`` of
 every parameter that requires grad.  ``YoloLayer`` gives the loss's gradient with respect to its
 head logits.
 """
@@ -282,6 +283,8 @@ class YoloNet(nn.Module):
         self.math_mode = DEFAULT_MATH_MODE
         # net(x, target) as a differentiable training step (yolo_v3_amd/backprop.py): False keeps the no-grad loss
         self.backprop = False
+        # arithmetic of the training step's convolutions: F32 (exact fp32) or BF16 (bf16 operands, fp32 accumulation)
+        self.backprop_math = _ffi.F32
 
     # ---- HIP execution
     def engine(self, dtype=None):
