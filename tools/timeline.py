@@ -8,6 +8,7 @@ kernels (tools/timelines/<name>.py holds what differs: the descriptor setup that
   roll       rolling loop (fp16 planes)                   roll_bf16  the bf16 192x256 / 256x256 rolling tiles
   w4         four-wave 192x128 tile, 2 workgroups per CU  wino    Winograd F(2x2,3x3) stage of the plane kernels
   probe      the bare DMA / read / MFMA probe loop        front / front_f32   the fused first-two-layers kernels
+  fused_f32  the exact-fp32 fused front and first residual block (conv_front_f32.hip, conv_res64_f32.hip)
 The exact-fp32 F(4x4,3x3) stage (round 6) prints its split through tools/wino4_ab.py (TL=1, -DW4F_TIMELINE=<workgroup>)."""
 import os
 import runpy

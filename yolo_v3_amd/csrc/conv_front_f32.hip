@@ -1,23 +1,26 @@
-// The first two layers of Darknet-53 as ONE kernel, EXACT-fp32 mode (YV3_F32) -- the fp32 twin of conv_front.hip (round 5):
+// The first two layers of Darknet-53 as ONE kernel, EXACT-fp32 mode (YV3_F32) -- the fp32 twin of conv_front.hip:
 //     feature.mlist.0  conv_bn_relu(3 -> 32, 3x3, s1)   reference darknet.py:76, :43-44
 //     feature.mlist.1  conv_bn_relu(32 -> 64, 3x3, s2)  reference darknet.py:68-70 (make_res_stack's down-sampling conv)
 // Unfused, the first layer writes a [B,H,W,32] fp32 activation (1.42 GB at 416x416 bs=64) that the second immediately re-reads:
 // 0.68 + 1.04 ms of the mode's 26.5 ms step.  Here it never leaves the CU: a persistent workgroup walks 8x16-pixel tiles of the
-// SECOND layer's output and for each tile
+// SECOND layer's output, two barriers per tile, and for each tile
 //   1. stages the 19 x 35 x 3 input patch (NCHW fp32, zero halo) in LDS                  (prefetched one tile ahead in registers)
-//   2. computes the 17 x 33 first-layer pixels the tile needs on the vector ALUs -- conv0.hip's conv0_kernel<0> chain, fma for fma:
-//      acc = fma(x, w, acc) over (c, kh, kw), then BN + LeakyReLU.  Wave = (pixel block, channel octet): the octet's weights are
-//      wave-uniform (scalar loads), a lane owns one pixel x 8 channels (v_pk_fma_f32), 9 passes of 64 pixels per SIMD.  Written to
-//      an LDS-resident fp32 image, zero where the pixel lies outside the picture (the second conv's padding), stored by column
-//      parity [parity][17 rows][18] so that the stride-2 taps read CONSECUTIVE 128-byte rows, XOR-swizzled by the half-column
-//      (slot ^ (colh >> 1) & 7): conflict-free ds_read_b128 for all nine taps;
-//   3. runs the second conv (M = 128 pixels, N = 64, K = 9 taps x 32; v_mfma_f32_32x32x2_f32) entirely out of LDS: its weights
-//      (72 KB of fp32) are DMA-ed once per workgroup and stay resident -- no global traffic, no barrier inside;
-//   4. BN + LeakyReLU -> per-wave LDS transpose -> 32-byte row segments per lane.
+//   2. computes the 17 x 33 first-layer pixels the tile needs on the matrix cores: 36 blocks of 16 pixels x 2 blocks of 16 channels,
+//      K = 27 taps (c, kh, kw) + one zero slot in FRONT = 7 x v_mfma_f32_16x16x4_f32, the weights as the A operand (in registers), the
+//      B fragments gathered from the patch (im2col by LDS address).  An f32 MFMA is a k-ordered fmaf chain, so this is conv0.hip's
+//      conv0_kernel<0> chain fma for fma: acc = fma(x, w, acc) over (c, kh, kw) from +0 (the zero slot leaves the +0 start a +0).
+//      BN + LeakyReLU, one ds_write_b128 of 4 channels per block into an LDS-resident fp32 image, zero where the pixel lies outside
+//      the picture (the second conv's padding), stored by column parity [parity][17 rows][18] so that the stride-2 taps read
+//      CONSECUTIVE 128-byte rows, XOR-swizzled by the half-column (slot ^ (colh >> 1) & 7): conflict-free ds_read_b128 for all nine taps;
+//   3. runs the second conv (M = 64 channels, N = 128 pixels, K = 9 taps x 32; v_mfma_f32_32x32x2_f32, weights as the A operand)
+//      entirely out of LDS: its weights (72 KB of fp32) are DMA-ed once per workgroup and stay resident -- no global traffic, no barrier;
+//   4. BN + LeakyReLU straight from the accumulators (a lane holds 4 groups of 4 consecutive channels of one pixel) -> 16-byte stores,
+//      DEFERRED into the next tile's step 2: waves 0-3 run it behind their first-layer blocks, waves 4-7 (their SIMD partners) in front,
+//      so that on every SIMD one wave has matrix work while the other stores.  The last tile's epilogue runs after the loop.
 // Same operations in the same order as yv3_conv0(YV3_F32) followed by yv3_conv2d(YV3_F32) (k pairs 8 kk + t / 8 kk + 4 + t per
 // MFMA, as conv_igemm_f32_kernel): BIT-IDENTICAL to the two launches (tests/test_gpu_kernels.py::
 // test_fused_front_f32_equals_two_launches_bitwise).  HBM traffic: 12 B in + 256 B out per second-layer pixel.
-// LDS: 78 336 (image, re-used by the epilogue transposes) + 73 728 (weights) + 8 208 (patch) = 160 272 B: one workgroup per CU.
+// LDS: 78 336 (image) + 73 728 (weights) + 8 208 (patch) = 160 272 B: one workgroup per CU.
 #include "yv3_common.h"
 
 namespace {
@@ -25,20 +28,18 @@ namespace {
 constexpr int GT_R = 8, GT_C = 16;                        // output tile of the second conv (rows x cols)
 constexpr int GR_COLS = 2 * GT_C + 1;                     // first-layer region: 17 rows x 33 cols
 constexpr int GR_PX = (2 * GT_R + 1) * GR_COLS;           // 561
+constexpr int GR_BLK = (GR_PX + 15) / 16;                 // 36 blocks of 16 pixels
 constexpr int GP_ROWS = 2 * GT_R + 3, GP_COLS = 2 * GT_C + 3;   // input patch 19 x 35
 constexpr int GP_PITCH = 36, GP_CH = GP_ROWS * GP_PITCH;  // floats
 constexpr int GA_RP = 18, GA_PB = (2 * GT_R + 1) * GA_RP; // image row pitch (pixels), parity block (306 pixels; even)
 constexpr int G_ROWB = 32 * 4;                            // bytes per image pixel / per weight row (32 fp32)
 constexpr int GA_BYTES = 2 * GA_PB * G_ROWB;              // 78 336
 constexpr int GW_BYTES = 9 * 64 * G_ROWB;                 // 73 728: [tap][64 channel rows][32 k]
-constexpr int G_EP = 36;                                  // floats per row of a wave's epilogue transpose tile
 constexpr int G_A_OFF = 0, G_W_OFF = GA_BYTES, G_P_OFF = G_W_OFF + GW_BYTES, G_LDS = G_P_OFF + 3 * GP_CH * 4;     // 160 272
-static_assert(8 * 32 * G_EP * 4 <= GA_BYTES && G_LDS <= 160 * 1024, "LDS budget");
+static_assert(G_LDS <= 160 * 1024, "LDS budget");
 
 #define GGPTR(p) ((const __attribute__((address_space(1))) void*)(p))
 #define GLPTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-typedef float gf32x2 __attribute__((ext_vector_type(2)));
 
 struct FrontF32Params {
     const float* x;          // [B,3,H,W] fp32
@@ -50,15 +51,14 @@ struct FrontF32Params {
     int H, W, B, tiles_x, tiles_y, total;
 };
 
-// (w0 is a __restrict__ kernel argument of its own: only then are the wave-uniform weight reads provably unclobbered -> scalar loads)
 __global__ __launch_bounds__(512) void conv_front_f32_kernel(const FrontF32Params p, const float* __restrict__ w0) {
+#pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     float* const patch = reinterpret_cast<float*>(lds + G_P_OFF);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);                // 8 waves: two per SIMD
-    const int l31 = lane & 31, lhi = lane >> 5;
-    const int wm = wid >> 1, wn = wid & 1;                // second conv: wave tile 32 pixels (tile rows 2wm, 2wm+1) x 32 channels
-    const int pb = wid >> 2, cq = wid & 3;                // first layer: pixel block (of 64) within a pass of 128, channel octet
+    const int l31 = lane & 31, lhi = lane >> 5, l15 = lane & 15, q4 = lane >> 4;
+    const int wm = wid >> 1, wn = wid & 1;                // second conv: wave tile 32 channels (wn) x 32 pixels (tile rows 2wm, 2wm+1)
     const int Ho = p.H >> 1, Wo = p.W >> 1;
 
     // ---- second-layer weights: resident in LDS for the launch.  72 wave instructions of 8 rows x 128 B; lane -> (row, physical slot)
@@ -68,11 +68,47 @@ __global__ __launch_bounds__(512) void conv_front_f32_kernel(const FrontF32Param
         const int ls = (lane & 7) ^ ((n >> 1) & 7);       // logical 16-byte slot this lane carries
         __builtin_amdgcn_global_load_lds(GGPTR(p.w1 + (long long)n * 288 + tap * 32 + ls * 4), GLPTR(lds + G_W_OFF + pc * 1024), 16, 0, 0);
     }
-    const float* const w0q = w0 + cq * 8;               // this wave's channel octet (wave-uniform: scalar loads)
-    float al0[8], be0[8];
+    // ---- first layer: k slot q4 of MFMA m carries tap k = 4 m + q4 - 1 (k = -1: the zero slot).  A operand: weight of channel
+    // 16 cb + l15; B operand: patch float at koff[m] from the pixel's corner
+    float w0a[2][7];
+    int koff[7];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { al0[j] = p.alpha0[cq * 8 + j]; be0[j] = p.beta0[cq * 8 + j]; }
-    const float al1 = p.alpha1[wn * 32 + l31], be1 = p.beta1[wn * 32 + l31];
+    for (int m = 0; m < 7; ++m) {
+        const int k = 4 * m + q4 - 1, kc = k < 0 ? 0 : k;
+        const int c = kc / 9, kh = (kc % 9) / 3, kw = kc % 3;
+        koff[m] = (c * GP_CH + kh * GP_PITCH + kw) * 4;
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) w0a[cb][m] = k < 0 ? 0.f : w0[k * 32 + cb * 16 + l15];
+    }
+    const bool kzero = q4 == 0;                           // this lane's slot of MFMA 0 is the zero slot
+    f32x4 al0[2], be0[2];                                 // D of block cb: channels 16 cb + 4 q4 + (0..3)
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) {
+        al0[cb] = *reinterpret_cast<const f32x4*>(p.alpha0 + cb * 16 + 4 * q4);
+        be0[cb] = *reinterpret_cast<const f32x4*>(p.beta0 + cb * 16 + 4 * q4);
+    }
+    f32x4 al1[4], be1[4];                                 // second conv epilogue: channels wn * 32 + 8 g + 4 lhi + (0..3)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        al1[g] = *reinterpret_cast<const f32x4*>(p.alpha1 + wn * 32 + 8 * g + 4 * lhi);
+        be1[g] = *reinterpret_cast<const f32x4*>(p.beta1 + wn * 32 + 8 * g + 4 * lhi);
+    }
+
+    // ---- first-layer blocks of this wave (pb = wid + 8 j; the fifth only for waves 0-3): the pixel's patch corner (LDS byte address),
+    // its image pixel (byte address, -1: no pixel; swizzle key (col >> 2) & 7), and (row << 8 | col) in the region -- tile-independent
+    constexpr int FJ = (GR_BLK + 7) / 8;                  // 5
+    static_assert(GR_BLK == 8 * (FJ - 1) + 4, "waves 0-3 take FJ blocks, waves 4-7 FJ - 1");
+    int fpo[FJ], fimg[FJ], fpos[FJ];
+#pragma unroll
+    for (int j = 0; j < FJ; ++j) {
+        const int idx = (wid + 8 * j) * 16 + l15;
+        const bool live = idx < GR_PX;
+        const int ii = live ? idx : 0;
+        const int row = ii / GR_COLS, col = ii - row * GR_COLS, colh = col >> 1;
+        fpo[j] = G_P_OFF + (row * GP_PITCH + col) * 4;
+        fimg[j] = live ? G_A_OFF + ((col & 1) * GA_PB + row * GA_RP + colh) * G_ROWB : -1;
+        fpos[j] = (row << 8) | col;
+    }
 
     // ---- fragment addresses of the second conv (constant over tiles).  Pixel side: lane -> (tile row, tile col) of its output pixel;
     // image pixel of tap (kh,kw): parity = kw&1, row 2r+kh, half-column c + (kw>>1); the swizzle key follows the half-column
@@ -110,6 +146,33 @@ __global__ __launch_bounds__(512) void conv_front_f32_kernel(const FrontF32Param
             pre[k] = v;
         }
     };
+
+    // ---- deferred epilogue of the previous tile: sums and the output offset of this lane's pixel (+ wn * 32 + 4 lhi)
+    f32x16 pacc;
+    long long pm = 0;
+    bool pend = false;
+    auto epilogue = [&]() {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            f32x4 v;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float t = fmaf(pacc[4 * g + i], al1[g][i], be1[g][i]);
+                v[i] = t > 0.f ? t : 0.1f * t;
+            }
+            *reinterpret_cast<f32x4*>(p.y + pm + 8 * g) = v;
+        }
+    };
+
+#if defined(YV3_MEASURE) && defined(YV3_TIMELINE)        // cycle split of workgroup 17 -> the first floats of y (results INVALID)
+    unsigned long long tl_s[5] = {0, 0, 0, 0, 0}, tl_t = 0;   // [top barrier (+ waits), deferred epilogue, first layer, mid barrier, 3x3]
+    int tl_n = 0;
+#define FR_MARK(i_) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); tl_s[i_] += t_ - tl_t; tl_t = t_; } while (0)
+    const unsigned long long tl_entry = __builtin_amdgcn_s_memtime();
+    tl_t = tl_entry;
+#else
+#define FR_MARK(i_) do {} while (0)
+#endif
     if ((int)blockIdx.x < p.total) patch_fetch(blockIdx.x);
 
     for (int tile = blockIdx.x; tile < p.total; tile += gridDim.x) {
@@ -118,56 +181,68 @@ __global__ __launch_bounds__(512) void conv_front_f32_kernel(const FrontF32Param
         const int ty = rem / p.tiles_x, tx = rem - ty * p.tiles_x;
         const int r0 = GT_R * ty, c0 = GT_C * tx;
 
-        // ---- 1. patch -> LDS.  Every wave is past the previous tile's epilogue here.
+        // ---- 1. patch -> LDS.  Every wave is past the previous tile's first layer here (its patch reads are done).
 #pragma unroll
         for (int k = 0; k < PK; ++k)
             if (plds[k] >= 0) patch[plds[k]] = pre[k];
         if (tile == (int)blockIdx.x) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // my share of the weight DMA has landed
-        __syncthreads();
-        if (tile + (int)gridDim.x < p.total) patch_fetch(tile + gridDim.x);       // lands during steps 2-4
+        __syncthreads();                                          // patch complete; every wave is past its reads of the image
+        if (tile + (int)gridDim.x < p.total) patch_fetch(tile + gridDim.x);       // lands during steps 2-3
+        FR_MARK(0);
 
-        // ---- 2. first layer for the 561 region pixels: passes of 128 pixels (this wave: 64 of them, 8 channels each)
-#pragma unroll 1
-        for (int ps = 0; ps < (GR_PX + 127) / 128; ++ps) {
-            const int base = ps * 128 + pb * 64;
-            if (base >= GR_PX) break;                                           // (wave-uniform)
-            const int idx = base + lane;
-            const bool live = idx < GR_PX;
-            const int ii = live ? idx : 0;
-            const int row = ii / GR_COLS, col = ii - row * GR_COLS;
-            const float* p0 = patch + row * GP_PITCH + col;
-            gf32x2 acc[4];
+        // ---- 2. first layer for the 561 region pixels: blocks pb = wid + 8 j (waves 0-3: five, 4-7: four), in two batches (j < 3,
+        // j >= 3): a batch's fragment reads up front, then 7 rounds of independent MFMAs, then BN + LeakyReLU + image writes; the pending
+        // epilogue behind (waves 0-3) or in front (4-7) of them
+        if (wid >= 4 && pend) { epilogue(); FR_MARK(1); }
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = gf32x2{0.f, 0.f};
+        for (int h = 0; h < 2; ++h) {
+            constexpr int NB = 3;
+            const int j0 = h ? NB : 0, nj = h ? FJ - NB : NB;
+            float xv[NB][7];
+            f32x4 acc[NB][2];
 #pragma unroll
-            for (int c = 0; c < 3; ++c)
+            for (int jj = 0; jj < NB; ++jj) {
+                const int j = j0 + jj;
+                if (jj < nj && (j < FJ - 1 || wid < 4)) {                      // (compile-time / wave-uniform)
 #pragma unroll
-                for (int kh = 0; kh < 3; ++kh)
+                    for (int m = 0; m < 7; ++m) xv[jj][m] = *reinterpret_cast<const float*>(lds + fpo[j] + koff[m]);
+                    if (kzero) xv[jj][0] = 0.f;
 #pragma unroll
-                    for (int kw = 0; kw < 3; ++kw) {
-                        const float v = p0[c * GP_CH + kh * GP_PITCH + kw];
-                        const float* wr = w0q + ((c * 3 + kh) * 3 + kw) * 32;       // wave-uniform -> s_load
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            acc[j] = __builtin_elementwise_fma(gf32x2{v, v}, gf32x2{wr[2 * j], wr[2 * j + 1]}, acc[j]);
-                    }
-            const int gy = 2 * r0 - 1 + row, gx = 2 * c0 - 1 + col;
-            const bool inimg = (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
-            f32x4 o[2];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float v = fmaf(acc[j >> 1][j & 1], al0[j], be0[j]);
-                v = v > 0.f ? v : 0.1f * v;                                      // (conv0_kernel's form of LeakyReLU(0.1))
-                o[j >> 2][j & 3] = inimg ? v : 0.f;                             // outside the picture: the second conv's zero padding
+                    for (int cb = 0; cb < 2; ++cb) acc[jj][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
             }
-            if (live) {
-                const int colh = col >> 1, key = (colh >> 1) & 7;
-                unsigned char* d = lds + G_A_OFF + ((col & 1) * GA_PB + row * GA_RP + colh) * G_ROWB;
-                *reinterpret_cast<f32x4*>(d + (((2 * cq) ^ key) * 16)) = o[0];
-                *reinterpret_cast<f32x4*>(d + (((2 * cq + 1) ^ key) * 16)) = o[1];
+#pragma unroll
+            for (int m = 0; m < 7; ++m)
+#pragma unroll
+                for (int jj = 0; jj < NB; ++jj)
+                    if (jj < nj && (j0 + jj < FJ - 1 || wid < 4))
+#pragma unroll
+                        for (int cb = 0; cb < 2; ++cb)
+                            acc[jj][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0a[cb][m], xv[jj][m], acc[jj][cb], 0, 0, 0);
+#pragma unroll
+            for (int jj = 0; jj < NB; ++jj) {
+                const int j = j0 + jj;
+                if (jj < nj && (j < FJ - 1 || wid < 4) && fimg[j] >= 0) {
+                    const int gy = 2 * r0 - 1 + (fpos[j] >> 8), gx = 2 * c0 - 1 + (fpos[j] & 255);
+                    const bool inimg = (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
+#pragma unroll
+                    for (int cb = 0; cb < 2; ++cb) {
+                        f32x4 o;
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            float v = fmaf(acc[jj][cb][i], al0[cb][i], be0[cb][i]);
+                            v = v > 0.f ? v : 0.1f * v;                          // (conv0_kernel's form of LeakyReLU(0.1))
+                            o[i] = inimg ? v : 0.f;                             // outside the picture: the second conv's zero padding
+                        }
+                        *reinterpret_cast<f32x4*>(lds + fimg[j] + (((4 * cb + q4) ^ ((fpos[j] >> 2) & 7)) * 16)) = o;
+                    }
+                }
             }
         }
-        __syncthreads();
+        FR_MARK(2);
+        if (wid < 4 && pend) { epilogue(); FR_MARK(1); }
+        __syncthreads();                                                          // image complete
+        FR_MARK(3);
 
         // ---- 3. second conv out of LDS: 9 taps x 4 groups of 8 k, K order (kh, kw, c)
         f32x16 acc2;
@@ -179,35 +254,30 @@ __global__ __launch_bounds__(512) void conv_front_f32_kernel(const FrontF32Param
             const int aoff = ((kw & 1) * GA_PB + kh * GA_RP) * G_ROWB;
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
-                const f32x4 af = *reinterpret_cast<const f32x4*>(lds + xa[kw >> 1] + aoff + (((kk * 2 + lhi) ^ xsw[kw >> 1]) * 16));
-                const f32x4 bf = *reinterpret_cast<const f32x4*>(lds + wa + tap * (64 * G_ROWB) + (((kk * 2 + lhi) ^ wsw) * 16));
+                const f32x4 xf = *reinterpret_cast<const f32x4*>(lds + xa[kw >> 1] + aoff + (((kk * 2 + lhi) ^ xsw[kw >> 1]) * 16));
+                const f32x4 wf = *reinterpret_cast<const f32x4*>(lds + wa + tap * (64 * G_ROWB) + (((kk * 2 + lhi) ^ wsw) * 16));
 #pragma unroll
-                for (int t = 0; t < 4; ++t) acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(af[t], bf[t], acc2, 0, 0, 0);
+                for (int t = 0; t < 4; ++t) acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[t], xf[t], acc2, 0, 0, 0);
             }
         }
-        __syncthreads();                                                              // the image is dead: its LDS becomes the transpose tiles
-
-        // ---- 4. epilogue: BN + LeakyReLU -> per-wave LDS transpose -> 32-byte row segments
-        float* tl = reinterpret_cast<float*>(lds + G_A_OFF) + wid * (32 * G_EP);
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            float v = fmaf(acc2[e], al1, be1);
-            v = v > 0.f ? v : 0.1f * v;
-            tl[((e & 3) + 8 * (e >> 2) + 4 * lhi) * G_EP + l31] = v;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const int r = s * 16 + (lane >> 2), cg = (lane & 3) * 8;
-            const int t = wm * 32 + r;                                                // pixel of the 8 x 16 tile
-            const long long m = ((long long)b * Ho + r0 + (t >> 4)) * Wo + c0 + (t & 15);
-            float* yo = p.y + m * 64 + wn * 32 + cg;
-            *reinterpret_cast<f32x4*>(yo) = *reinterpret_cast<const f32x4*>(tl + r * G_EP + cg);
-            *reinterpret_cast<f32x4*>(yo + 4) = *reinterpret_cast<const f32x4*>(tl + r * G_EP + cg + 4);
-        }
+        pacc = acc2;
+        pm = (((long long)b * Ho + r0 + 2 * wm + pr) * Wo + c0 + pcx) * 64 + wn * 32 + 4 * lhi;
+        pend = true;
+        FR_MARK(4);
+#if defined(YV3_MEASURE) && defined(YV3_TIMELINE)
+        ++tl_n;
+#endif
     }
+    if (pend) { epilogue(); FR_MARK(1); }                             // the last tile's epilogue
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#if defined(YV3_MEASURE) && defined(YV3_TIMELINE)
+    if (blockIdx.x == 17 && lane == 0) {
+        float* dbg = p.y + wid * 8;
+        for (int i = 0; i < 5; ++i) dbg[i] = (float)tl_s[i] / (tl_n > 0 ? tl_n : 1);
+        dbg[5] = (float)(tl_t - tl_entry); dbg[6] = (float)tl_n;
+    }
+#endif
+#undef FR_MARK
 }
 
 }  // namespace
