@@ -111,6 +111,9 @@ class _Run:
         self.shape = {}            # buffer -> (B, H, W, C)
         self.need = {}             # buffer -> some parameter upstream of it needs a gradient
         self.loss = None
+        # None: nothing extra.  A dict: backward() stores, per op index, clones of dy, dz, the parameter gradients and every
+        # destination of a dgrad / upcat_bwd / add before and after the call (tests/test_gpu_train_local.py checks each op on them)
+        self.trace = None
 
 
 def _ws(nbytes, dev):
@@ -226,13 +229,20 @@ def backward(run, grad_output):
     g = grad_output.detach().to(device=dev, dtype=torch.float32).reshape(()).contiguous()
     grads = {}                 # buffer -> dL/dbuffer (NHWC fp32)
     pg = {}
+    trace = run.trace
 
-    def give(buf, t):
+    def rec(i, **tensors):
+        if trace is not None:
+            trace.setdefault(i, {}).update({k: t.clone() for k, t in tensors.items() if t is not None})
+
+    def give(i, buf, t):
         """Add t into the gradient of buf (takes ownership of t when buf has none yet)."""
         if buf in grads:
+            rec(i, res_before=grads[buf])
             _ffi.check(lib.yv3_train_add(t.data_ptr(), grads[buf].data_ptr(), t.numel(), s), "yv3_train_add")
         else:
             grads[buf] = t
+        rec(i, res_after=grads[buf])
 
     head_ops = {op.head_idx: op for op in run.ops if op.head}
     for kk in range(3):
@@ -242,6 +252,7 @@ def backward(run, grad_output):
         dy = grads.pop(op.out, None)
         if dy is None or not run.need[op.out]:
             continue
+        rec(i, dy=dy)
         b_, h, w, cin, cout, k, st = sv["geo"]
         _, ho, wo, _ = run.shape[op.out]
         P = b_ * ho * wo
@@ -254,6 +265,7 @@ def backward(run, grad_output):
             _ffi.check(lib.yv3_train_bias_bwd(dy.data_ptr(), g.data_ptr(), dz.data_ptr(), db.data_ptr(), P, cout, ws.data_ptr(), nb, s),
                        "yv3_train_bias_bwd")
             pg[id(c.bias)] = db
+            rec(i, dz=dz, dbias=db)
         else:
             dgam = torch.empty(cout, device=dev, dtype=torch.float32)
             dbet = torch.empty_like(dgam)
@@ -261,8 +273,9 @@ def backward(run, grad_output):
                                                 sv["gamma"].data_ptr(), sv["beta"].data_ptr(), dz.data_ptr(), dgam.data_ptr(),
                                                 dbet.data_ptr(), P, cout, sv["train"], ws.data_ptr(), nb, s), "yv3_train_bn_act_bwd")
             pg[id(op.bn.weight)], pg[id(op.bn.bias)] = dgam, dbet
+            rec(i, dz=dz, dgamma=dgam, dbeta=dbet)
             if op.res is not None and run.need[op.res]:
-                give(op.res, dy)            # y = act(...) + res: dres = dy (dy is not read again)
+                give(i, op.res, dy)         # y = act(...) + res: dres = dy (dy is not read again)
         need_src = run.need[op.src]
         need_src2 = op.src2 is not None and run.need[op.src2]
         if bf:
@@ -284,6 +297,7 @@ def backward(run, grad_output):
                                                     dz.data_ptr(), dw.data_ptr(), b_, h, w, cin, op.cin_up, cout, k, st,
                                                     int(op.src == "x"), wsw.data_ptr(), nw, s), "yv3_train_conv_wgrad")
             pg[id(c.weight)] = dw
+            rec(i, dw=dw)
         if not (need_src or need_src2):
             continue
 
@@ -298,8 +312,10 @@ def backward(run, grad_output):
         if op.cin_up == 0:
             acc = op.src in grads
             dx = grads[op.src] if acc else torch.empty((b_, h, w, cin), device=dev, dtype=torch.float32)
+            rec(i, dx_before=dx if acc else None)
             dgrad(dx, acc)
             grads[op.src] = dx
+            rec(i, dx_after=dx)
         else:
             dcat = torch.empty((b_, h, w, cin), device=dev, dtype=torch.float32)
             dgrad(dcat, False)
@@ -314,9 +330,11 @@ def backward(run, grad_output):
                 acc_tail = int(op.src in grads)
                 dtail = grads[op.src] if acc_tail else torch.empty((b_, h, w, ct), device=dev, dtype=torch.float32)
                 grads[op.src] = dtail
+            rec(i, dcat=dcat, dlow_before=dlow if acc_low else None, dtail_before=dtail if acc_tail else None)
             _ffi.check(lib.yv3_train_upcat_bwd(dcat.data_ptr(), dlow.data_ptr() if dlow is not None else None,
                                                dtail.data_ptr() if dtail is not None else None, b_, h, w, op.cin_up, ct,
                                                acc_low, acc_tail, s), "yv3_train_upcat_bwd")
+            rec(i, dlow_after=dlow, dtail_after=dtail)
     return pg
 
 
