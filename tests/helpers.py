@@ -101,6 +101,16 @@ def trained_like_stream(num_class=80, seed=20260935, b_obj=-2.0, b_cls=-2.0, hea
 
 
 # ----------------------------------------------------------------------------- layer-by-layer ("teacher-forced") runs
+def desc_inputs_by_pointer(plan):
+    """``names(d) -> (x, x2, residual)``: the producing layer's name (or None) of each input pointer of a descriptor of `plan`.  `Plan` gives
+    every conv its own output buffer (``plan.layer_out[name]``, never reused), so a pointer identifies its producer."""
+    ptr2name = {buf.data_ptr(): name for name, buf in plan.layer_out.items()}
+
+    def names(d):
+        return tuple(ptr2name[ptr] if ptr else None for ptr in (d.x, d.x2, d.residual))
+    return names
+
+
 def teacher_forced_layers(net, mode, x, taps):
     """Run every one of the 75 convolutions of `net` ALONE through the C-ABI in math mode `mode`, each fed the
     ORACLE's activations (``taps`` = [(name, NCHW fp32 tensor)] from oracle_cpu.head_logits) instead of the previous
@@ -118,12 +128,11 @@ def teacher_forced_layers(net, mode, x, taps):
         with torch.cuda.device(eng.device):
             plan = eng.plan(B, H, W)
             tapd = dict(taps)
-            ptr2name = {buf.data_ptr(): name for name, buf in plan.layer_out.items()}
+            names = desc_inputs_by_pointer(plan)
 
-            def put(ptr):
-                if not ptr:
+            def put(name):
+                if name is None:
                     return
-                name = ptr2name[ptr]
                 buf = plan.layer_out[name]
                 buf.copy_(_engine.to_planes(tapd[name].permute(0, 2, 3, 1).contiguous().cuda(), mode))
 
@@ -135,8 +144,8 @@ def teacher_forced_layers(net, mode, x, taps):
             for j in range(plan.n_desc):
                 d = plan.descs[j]
                 name = eng.specs[plan.desc_spec[j]].name          # (a layer may be two launches over batch slices)
-                for ptr in (d.x, d.x2, d.residual):
-                    put(ptr)
+                for src in names(d):
+                    put(src)
                 _ffi.check(_ffi.lib().yv3_conv2d(ctypes.byref(d), _ffi.stream_ptr()), "yv3_conv2d " + name)
                 out[name] = (get(name), tapd[name])
             torch.cuda.synchronize()

@@ -7,6 +7,10 @@ lane count and the CU count (csrc/conv_planes.hip: yv3_conv2d_planes_form), so "
   * the headline workload of bench.py (416x416 bs=64, the 64 scenes ``scenes(64, 416, 1000)``, default math mode) through
     `Detector` with automatic lanes AND with both lane counts forced, all 64 images vs the oracle, with the plan's forms
     asserted through ``yv3_conv2d_form`` (reference path: test.py:35-36);
+  * the same in the arithmetic the benchmark's headline is timed in since round 6 -- exact fp32 (``dtype=F32``): two lanes of 32 with 31
+    Winograd F(4x4,3x3) launches each, the plain 1x1 layers on the persistent GEMM with its whole-rounds / rest split -- and the other
+    exact-fp32 plans bench.py times: the dense 608x608 bs=8 config, eval mode at the reference's thresholds, one image as a HIP graph
+    (every launch of these plans against float64: tests/test_gpu_plan_local.py);
   * the whole network with the Winograd form FORCED on every eligible layer (``net.winograd = "always"``), both
     Winograd-capable math modes, vs the oracle and the reference's golden boxes;
   * BASELINE configs[3] at its full size, functionally: 4 ranks (gloo; they time-share the one GPU), global batch 256,
@@ -24,7 +28,7 @@ import torch
 from oracle import oracle_cpu as oc
 from oracle.boxdelta import boxes_delta
 from yolo_v3_amd import synth, detect, Detector, _ffi, arch
-from tests.helpers import TOL, assert_close_rel, match_boxes, load_sw1_net
+from tests.helpers import TOL, assert_close_rel, match_boxes, load_sw1_net, detector_dets
 
 pytestmark = pytest.mark.gpu
 
@@ -62,30 +66,99 @@ def _form_counts(plan):
     return out
 
 
-@pytest.mark.parametrize("lanes", [None, 2, 1])
-def test_headline_plan_vs_oracle(sw1_stream, headline, lanes):
+def _num_cu():
+    n = torch.cuda.get_device_properties(0).multi_processor_count
+    return n & ~7 if n >= 8 else 256
+
+
+def _gemm_split_launches(d, ncu):
+    """Kernel launches of a plain exact-fp32 1x1 descriptor by the documented rule: the persistent GEMM takes
+    the layer when its tiles (128x128; 256x64 for 64 output channels) fill at least one round of the chip; whole rounds run there, and a
+    last partial round of at most half the CUs runs on the small tiles instead -- a second launch."""
+    M = d.B * d.H * d.W
+    bm, bn = (128, 128) if d.cout % 128 == 0 else (256, 64)
+    ntn, mt = d.cout // bn, -(-M // bm)
+    tiles = mt * ntn
+    if tiles < ncu:
+        return 1
+    rounds, rest = tiles // ncu, tiles % ncu
+    here = rounds * ncu // ntn if (rest > 0 and 2 * rest <= ncu) else mt
+    return 2 if here * bm < M else 1
+
+
+ONE_LANE_F4 = 31           # F(4x4,3x3) launches of the one-lane exact-fp32 plan of 64 images on 256 CUs: every eligible layer, as with two lanes (first read on the GPU, then pinned)
+
+
+def _assert_f32_plan(plan, lanes):
+    """The exact-fp32 plan the benchmark times, through ``plan.forms()`` / ``plan.launches()``.  Returns (F(4x4) launches, 1x1 launches split
+    between GEMM and tiles, per-shape table)."""
+    specs = arch.conv_specs()
+    forms, nl = plan.forms(), plan.launches()
+    ncu = _num_cu()
+    table, n_f4, n_split = {}, 0, 0
+    for j, ((si, f), n) in enumerate(zip(forms, nl), plan.first_desc):
+        sp, d = specs[si], plan.descs[j]
+        key = "%d->%d k%d s%d @%dx%d" % (sp.cin, sp.cout, sp.k, sp.stride, d.H, d.W)
+        row = table.setdefault(key, {"launches": 0, "F(4x4)": 0, "kernels": []})
+        row["launches"] += 1
+        row["kernels"].append(n)
+        assert f != 1, "an F(2x2,3x3) launch in the exact-fp32 plan: %s" % key
+        if f == 2:
+            assert sp.k == 3 and sp.stride == 1 and sp.cin >= 64, key
+            assert n == 2, key
+            row["F(4x4)"] += 1
+            n_f4 += 1
+        elif sp.k == 1 and sp.bn and not d.residual and not d.cin_up:
+            want = _gemm_split_launches(d, ncu)
+            assert n == want and n in (1, 2), "plain 1x1 %s: yv3_conv2d_launches %d, the rest rule gives %d on %d CUs" % (key, n, want, ncu)
+            n_split += n == 2
+        else:
+            assert n == 1, key
+    if lanes == 2:
+        assert plan.B == 32 and n_f4 == 31, table            # README, BENCH_r06: every stride-1 3x3 layer with cin >= 64
+    elif ncu == 256 and ONE_LANE_F4 is not None:
+        assert plan.B == 64 and n_f4 == ONE_LANE_F4, table
+    return n_f4, n_split, table
+
+
+@pytest.mark.parametrize("lanes,dtype", [(None, None), (2, None), (1, None), (None, _ffi.F32), (2, _ffi.F32), (1, _ffi.F32)],
+                         ids=["None", "2", "1", "None-F32", "2-F32", "1-F32"])
+def test_headline_plan_vs_oracle(sw1_stream, headline, lanes, dtype):
     """bench.py's timed step, as bench.py builds it (`Workload`: ``Detector(net, 64, 416, 416, 0.5, 0.4, lanes=None)``), on
     bench.py's 64 scenes: every detection value of all 64 images within 1e-4 * max(1,|ref|) of the oracle, final boxes
     set-wise (class + IOU >= 0.999; random scenes are not margin-selected) with matched boxes within 1e-4 and <= 0.2 %
     unmatched (measured in rounds 3-4: 0 of 5102).  The plan is asserted, not assumed: with two lanes of 32 images every 256->512 @26x26 and 512->1024 @13x13
     layer (18 launches per lane) must take the Winograd form; with one lane of 64 the seven 13x13 layers.  lanes=None is
-    the automatic choice the benchmark runs (two lanes at this batch size wherever a concurrent stream pair exists)."""
+    the automatic choice the benchmark runs (two lanes at this batch size wherever a concurrent stream pair exists).
+
+    ``dtype=F32`` -- the arithmetic of the benchmark's headline since round 6 -- (``_assert_f32_plan``): no F(2x2) launch; every F(4x4,3x3)
+    launch is a 3x3 stride-1 layer with cin >= 64 and two kernels; two lanes: 32 images and 31 F(4x4) launches per lane; one lane of 64:
+    ONE_LANE_F4; every plain 1x1 layer reports the kernel count of the GEMM's rest rule (1, or 2 = whole rounds on the GEMM + the rest on
+    tiles), every other launch one kernel."""
     x, ref, want = headline
     net = load_sw1_net(sw1_stream).cuda()
-    det = Detector(net, 64, 416, 416, 0.5, 0.4, lanes=lanes)
+    det = Detector(net, 64, 416, 416, 0.5, 0.4, lanes=lanes, dtype=dtype)
     if lanes is not None:
         assert det.lanes == lanes
     with torch.no_grad():
         res = det(x.cuda())
     forms = [_form_counts(p) for p in det.lane_plans]
-    c26, c13 = (256, 512, 3, 1, 26), (512, 1024, 3, 1, 13)
-    for fc in forms:
-        assert fc[c26][0] == 11 and fc[c13][0] == 7
-        if det.lanes == 2:
-            assert det.lane_plans[0].B == 32 and fc[c26][1] == 11 and fc[c13][1] == 7, fc
-        else:
-            assert fc[c26][1] == 0 and fc[c13][1] == 7, fc
-        assert sum(v[1] for k, v in fc.items() if k not in (c26, c13)) == 0
+    if dtype == _ffi.F32:
+        for i, p in enumerate(det.lane_plans):
+            n_f4, n_split, table = _assert_f32_plan(p, det.lanes)
+            print("headline exact fp32, lanes=%s -> %d, lane %d (B=%d): %d F(4x4,3x3) launches, %d plain 1x1 launches split GEMM + tiles"
+                  % (lanes, det.lanes, i, p.B, n_f4, n_split))
+            for key, row in table.items():
+                print("    %-28s launches %2d  F(4x4) %2d  kernels per launch %s" % (key, row["launches"], row["F(4x4)"], sorted(set(row["kernels"]))))
+    else:
+        c26, c13 = (256, 512, 3, 1, 26), (512, 1024, 3, 1, 13)
+        for fc in forms:
+            assert fc[c26][0] == 11 and fc[c13][0] == 7
+            if det.lanes == 2:
+                assert det.lane_plans[0].B == 32 and fc[c26][1] == 11 and fc[c13][1] == 7, fc
+            else:
+                assert fc[c26][1] == 0 and fc[c13][1] == 7, fc
+            assert sum(v[1] for k, v in fc.items() if k not in (c26, c13)) == 0
     err = assert_close_rel(det.dets.cpu(), ref, TOL, "headline detections (lanes=%s)" % det.lanes)
     d = boxes_delta(res, want, 64)
     print("headline plan lanes=%s -> %d: winograd launches per lane %s; max det err %.3g; boxes %s"
@@ -99,6 +172,81 @@ def test_headline_plan_vs_oracle(sw1_stream, headline, lanes):
     assert len(res) == len(exact)
     for a, b in zip(res, exact):
         assert tuple(a.shape) == tuple(b.shape) and torch.equal(a, b)
+
+
+def test_dense_config_exact_fp32_vs_oracle():
+    """tests/test_gpu_configs.py::test_config5_dense_full_network_vs_oracle in the arithmetic bench.py times the config in
+    (``net.math_mode = F32``): 608x608 bs=8 on SW-dense, detections within 1e-4, >= 5000 candidates per image, boxes set-wise with <= 1 %
+    unmatched and matched boxes within 1e-4, decisions on the detector's own detections bit-equal to the oracle's."""
+    stream = synth.dense_weight_stream()
+    net = load_sw1_net(stream, 608).cuda()
+    net.math_mode = _ffi.F32
+    sd, _ = oc.state_dict_from_stream(stream)
+    x = torch.from_numpy(synth.images(8, 608, 4))
+    with torch.no_grad():
+        ref = torch.cat(oc.yolonet_forward(sd, x), 1)
+        got = net.forward_cat(x.cuda()).cpu()
+    assert net.engine().dtype == _ffi.F32
+    assert_close_rel(got, ref, TOL, "dense config, exact fp32: detections")
+    ncand = ((got[..., 5:] * got[..., 4:5]).amax(-1) > 0.5).sum(1)
+    assert int(ncand.min()) >= 5000, ncand.tolist()
+    res = detect(net, x.cuda(), 80, 0.5, 0.4)
+    assert detector_dets(net).dtype == torch.float32 and list(net._detectors.values())[-1].engine.dtype == _ffi.F32
+    exact = oc.postprocess(detector_dets(net).cpu(), 80, 0.5, 0.4)
+    assert len(res) == len(exact) == 8
+    for a, b in zip(res, exact):
+        assert tuple(a.shape) == tuple(b.shape) and torch.equal(a, b)
+    d = boxes_delta(res, oc.postprocess(ref, 80, 0.5, 0.4), 8)
+    print("dense config, exact fp32: candidates/img %s; boxes %s" % (ncand.tolist(), d))
+    assert d["ref_boxes"] > 8 * 2000
+    assert d["max_rel_err_coords"] <= TOL and d["max_abs_err_score"] <= TOL
+    print("dense config, exact fp32: unmatched_frac %.5f (bound 0.01)" % d["unmatched_frac"])
+    assert d["unmatched_frac"] <= 0.01, d
+
+
+def test_eval_mode_exact_fp32_at_reference_thresholds(golden_dir):
+    """tests/test_gpu_configs.py::test_eval_mode_at_reference_thresholds' case as bench.py times it: ``Detector(..., 0.005, 0.45,
+    is_eval=True, max_cand=8192, dtype=F32)`` on SW-eval: detections within 1e-4 of the reference's own (tests/golden/e2e_eval.npz),
+    decisions on the detector's own detections bit-equal to the oracle's, boxes vs the REFERENCE's set-wise with <= 0.2 % unmatched."""
+    g = np.load(os.path.join(golden_dir, "e2e_eval.npz"))
+    B, size, seed = [int(v) for v in g["in_cfg"]]
+    net = load_sw1_net(synth.eval_weight_stream(), size).cuda()
+    x = torch.from_numpy(synth.images(B, size, seed))
+    det = Detector(net, B, size, size, 0.005, 0.45, is_eval=True, max_cand=8192, dtype=_ffi.F32)
+    with torch.no_grad():
+        res = det(x.cuda())
+    assert det.engine.dtype == _ffi.F32 and not any(f == 1 for p in det.lane_plans for _, f in p.forms())
+    assert_close_rel(det.dets[:, g["rows"]].cpu(), g["dets_rows"], TOL, "SW-eval detections, exact fp32")
+    exact = oc.postprocess(det.dets.cpu(), 80, 0.005, 0.45, True, True)
+    assert len(res) == len(exact) == B
+    for a, b in zip(res, exact):
+        assert tuple(a.shape) == tuple(b.shape) and torch.equal(a, b)
+    d = boxes_delta(res, [torch.from_numpy(g["boxes%d" % i]) for i in range(B)], B)
+    print("eval mode 0.005/0.45, exact fp32, vs reference:", d)
+    assert d["ref_boxes"] > 1000 and d["unmatched_frac"] <= 0.002
+    assert d["max_rel_err_coords"] <= TOL and d["max_abs_err_score"] <= TOL
+
+
+def test_one_image_graph_replay_exact_fp32_equals_eager(sw1_stream):
+    """bench.py's one-image HIP-graph config in exact fp32: ``Detector(net, 1, 416, 416, 0.5, 0.4, dtype=F32, graph=True)`` called three
+    times equals the eager detector bit for bit -- boxes and the detections tensor.  (One lane: a captured graph without parallel
+    branches.  At bs=1 every F(4x4) launch runs the even schedule, whose hand-over flags must be left clean for the next replay.)"""
+    net = load_sw1_net(sw1_stream).cuda()
+    x = torch.from_numpy(synth.images(1, 416, 1000)).cuda()
+    eager = Detector(net, 1, 416, 416, 0.5, 0.4, dtype=_ffi.F32, lanes=1)
+    with torch.no_grad():
+        want = eager(x)
+    want_dets = eager.dets.clone()
+    assert sum(f == 2 for _, f in eager.plan.forms()) > 0
+    gdet = Detector(net, 1, 416, 416, 0.5, 0.4, dtype=_ffi.F32, graph=True, lanes=1)
+    assert gdet.lanes == 1
+    for i in range(3):
+        gdet.dets.fill_(float("nan"))
+        with torch.no_grad():
+            got = gdet(x)
+        assert gdet._graph is not None
+        assert len(got) == len(want) and all(torch.equal(a, b) for a, b in zip(got, want)), "replay %d" % i
+        assert torch.equal(gdet.dets, want_dets), "replay %d: detections differ from the eager run" % i
 
 
 @pytest.mark.parametrize("B,size,sk", [(4, 416, True), (9, 416, True), (10, 416, False), (4, 608, True), (5, 608, False)])
