@@ -12,7 +12,12 @@ Plain host torch, no GPU.  Tensors are NHWC as the kernels see them (already rou
 caller passes the values the planes hold); the weight is OIHW fp32.  Results are float64 rows [M, cout] (M = B*Ho*Wo, NHWC order),
 or only the rows named in ``pixels`` -- computed by an explicit gather of their input patches, so that shapes of hundreds of 128-row
 blocks stay cheap on the CPU.
+
+The BF16 kernels' bar lives here too (``bf16_report`` / ``assert_bf16``): a stored bf16 output may differ from the float64 result of the
+same operands only by the fp32 summation round-off and ONE round-to-nearest-even to bf16 (oracle/oracle_cpu.py, prec="bf16").
 """
+import math
+
 import torch
 import torch.nn.functional as F
 
@@ -102,3 +107,70 @@ def sample_rows(B, Ho, Wo, seed=0, n_random=2048, last=256):
     parts = [border, firsts, firsts + Ho * Wo - 1, torch.arange(max(0, M - last), M),
              torch.randint(0, M, (n_random,), generator=torch.Generator().manual_seed(seed))]
     return torch.unique(torch.cat(parts))
+
+
+# ----------------------------------------------------------------------------- the BF16 kernels' bar
+# A stored bf16 output `got`, the float64 result `ref` of the same descriptor on the same (bf16-held) operands: a bf16 x bf16 product is
+# exact in fp32, so got = bf16(ref + fp32 summation and epilogue round-off).  With the project's forward bound for an fp32-accumulated
+# dot product (tests/test_gpu_configs.py::test_hostile_conv_level_all_fp32_modes, c = 4)
+#       eps = (sqrt(K) + 4) * 2^-24 * mag,    K = k*k*cin,    mag = |alpha| * sum|w||x| + |beta| + |residual|
+#   A  every element:  bf16(ref - eps) <= got <= bf16(ref + eps)        (bf16() is monotone: any value within eps of ref rounds into it)
+#   B  the share of elements with got != bf16(ref) is at most BF16_SHARE_CAP -- a flip needs ref within eps of a rounding boundary,
+#      and eps is ~1e-4 of the spacing of those; torch fp32 on the CPU gives 2e-5 .. 2.8e-4 (tests/test_conv_ref_host.py), the mildest faulty epilogue
+#      there (LeakyReLU slope rounded to bf16) 9e-2.  A condition, not a measurement.
+# fp32 outputs of a BF16 conv (the heads) are not rounded at all: F32_BAR * max(1, |ref|), the fp32 modes' bar.
+BF16_SHARE_CAP = 5e-3
+F32_BAR = 2e-5
+
+
+def round_bf16_f64(t):
+    """float64 -> the nearest bfloat16 value (ties to even), as float64: ONE rounding, where .float().bfloat16() would round twice.
+    (frexp: |m| in [0.5, 1), so m * 2^8 has the format's 8 significant bits in front of the point; torch.round is half-to-even.)
+    Normal range only, which is all these tests produce."""
+    t = t.double()
+    m, e = torch.frexp(t)
+    return torch.ldexp(torch.round(m * 256.0), e - 8)
+
+
+def conv_desc_mag(x, w, beta, alpha=None, residual=None, x2=None, cin_up=0, stride=1, pixels=None):
+    """|alpha| * sum|w||x| + |beta| + |residual|: conv_desc_ref on the absolute values of every operand, linear."""
+    ab = lambda t: t.abs() if t is not None else None
+    return conv_desc_ref(ab(x), ab(w), ab(beta), ab(alpha), ab(residual), ab(x2), cin_up, stride, ACT_LINEAR, pixels)
+
+
+def bf16_eps(K, mag):
+    return (math.sqrt(K) + 4.0) * 2.0 ** -24 * mag
+
+
+def bf16_report(got, ref, mag, K):
+    """Criteria A and B for stored bf16 values `got` [M, cout] against float64 `ref`, `mag` (same shape).  Returns a dict:
+    worst = max |got - ref| / eps, share = fraction of got != bf16(ref), outside = number of elements outside their interval,
+    first = (row, channel) of the first of those or None, a_ok, b_ok."""
+    got, ref = got.double(), ref.double()
+    assert got.shape == ref.shape == mag.shape and got.dim() == 2 and bool(torch.isfinite(got).all())
+    eps = bf16_eps(K, mag.double())
+    out = (got < round_bf16_f64(ref - eps)) | (got > round_bf16_f64(ref + eps))
+    n_out = int(out.sum())
+    first = divmod(int(out.reshape(-1).nonzero()[0]), got.shape[1]) if n_out else None
+    share = float((got != round_bf16_f64(ref)).double().mean())
+    worst = float(((got - ref).abs() / eps.clamp(min=1e-300)).max())
+    return dict(worst=worst, share=share, outside=n_out, first=first, a_ok=n_out == 0, b_ok=share <= BF16_SHARE_CAP)
+
+
+def assert_bf16(got, ref, mag, K, what=""):
+    """Assert A and B; the message carries the worst |got - ref| / eps, the share and the first element outside its interval."""
+    r = bf16_report(got, ref, mag, K)
+    msg = "%s: worst |got - ref| / eps = %.4g (eps = (sqrt(%d) + 4) * 2^-24 * mag), share of got != bf16(ref) = %.3g (cap %.1g), " \
+          "%d elements outside [bf16(ref - eps), bf16(ref + eps)], the first at row/channel %s" % (
+              what, r["worst"], K, r["share"], BF16_SHARE_CAP, r["outside"], r["first"])
+    assert r["a_ok"], "criterion A: " + msg
+    assert r["b_ok"], "criterion B: " + msg
+    return r
+
+
+def assert_f32_bar(got, ref, what=""):
+    """fp32 output of a BF16 conv: |got - ref| <= F32_BAR * max(1, |ref|)."""
+    err = (got.double() - ref).abs() / ref.abs().clamp(min=1.0)
+    assert float(err.max()) <= F32_BAR, "%s: max normalised error %.3g > %.1g at row/channel %s" % (
+        what, float(err.max()), F32_BAR, divmod(int(err.argmax()), ref.shape[1]))
+    return float(err.max())

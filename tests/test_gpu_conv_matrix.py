@@ -3,10 +3,11 @@
 Every descriptor is built here directly (ctypes yv3_conv_desc), so that features the engine never combines -- alpha == NULL in a plane
 mode, forced tiles with cin_up, fused decode with y == NULL, batch slices -- run too.  Every output buffer is NaN-filled with a NaN canary
 behind it; after each launch: every output element written, nothing past the end, status word 0 (unless the case saturates on purpose),
-and the result within the mode's bar of the reference -- 2e-5 * max(1,|ref|) for F32 / F32X3 / F32H2, 2e-2 * max(1,|ref|) for BF16
-against a reference fed the bf16-rounded operands.  Where the code documents the same K order (the F32 tiles among themselves, the plane
-tile codes among themselves) the forced paths must also equal the library's default choice bit for bit.  Shapes with hundreds of
-128-row blocks are compared on conv_ref.sample_rows only."""
+and the result within the mode's bar of the reference -- 2e-5 * max(1,|ref|) for F32 / F32X3 / F32H2 and for the fp32 head outputs of a
+BF16 conv; for the bf16 outputs of BF16, against a reference fed the bf16-rounded operands, ONE bf16 rounding of float64 plus the fp32
+summation round-off (conv_ref.assert_bf16: criteria A and B), next to the old 2e-2 * max(1,|ref|).  Where the code documents the same K
+order (the F32 tiles among themselves, the plane tile codes among themselves) the forced paths must also equal the library's default
+choice bit for bit.  Shapes with hundreds of 128-row blocks are compared on conv_ref.sample_rows only."""
 import ctypes
 import types
 
@@ -69,6 +70,7 @@ class Conv:
         self.cout_pad = cout_pad if cout_pad is not None else (cout + 31) // 32 * 32
         self.Ho, self.Wo = cr.out_hw(H, W, k, stride)
         self.M = B * self.Ho * self.Wo
+        self._mag = None                # (pixels, conv_ref.conv_desc_mag on them): the BF16 bar's magnitude, computed once per row set
         g = torch.Generator().manual_seed(1000 + seed)
         if cin_up:
             self.x, self.x_ref = _held(_rand((B, H // 2, W // 2, cin_up), g), mode)
@@ -95,8 +97,10 @@ class Conv:
 
     def set_residual(self, r_nhwc):
         self.res, self.res_ref = _held(r_nhwc, self.mode)
+        self._mag = None
 
     def set_beta(self, beta):
+        self._mag = None
         self.beta_ref = beta.clone()
         self.beta = beta.cuda()
 
@@ -137,8 +141,16 @@ class Conv:
         return cr.conv_desc_ref(self.x_ref, self.w_ref, self.beta_ref, self.alpha_ref, self.res_ref, self.x2_ref, self.cin_up,
                                 self.stride, self.act, pixels)
 
+    def mag(self, pixels=None):
+        """|alpha| * sum|w||x| + |beta| + |residual| of the same rows as ref(pixels)."""
+        if self._mag is None or self._mag[0] is not pixels:
+            self._mag = (pixels, cr.conv_desc_mag(self.x_ref, self.w_ref, self.beta_ref, self.alpha_ref, self.res_ref, self.x2_ref,
+                                                  self.cin_up, self.stride, pixels))
+        return self._mag[1]
+
     def check(self, y, ref, pixels=None, what="", flag=0):
-        """Canary intact, every element written, status word == flag, values within the bar (on `pixels` only, if given)."""
+        """Canary intact, every element written, status word == flag, values within the bar (on `pixels` only, if given).  BF16: the
+        old 2e-2 bar AND conv_ref's -- A + B for a bf16 output, 2e-5 * max(1,|ref|) for an fp32 one."""
         torch.cuda.synchronize()
         n = self.y_elems()
         assert bool(torch.isnan(y[n:]).all()), "%s: wrote past the end of y" % what
@@ -153,6 +165,12 @@ class Conv:
         bar = BAR[self.mode]
         assert float(err.max()) <= bar, "%s: max normalised error %.3g > %.1g at row/channel %s" % (
             what, float(err.max()), bar, divmod(int(err.argmax()), self.cout))
+        if self.mode == BF16 and self.out_dtype == F32:
+            e = cr.assert_f32_bar(got, ref, what)
+            print("bf16 bar | %s | fp32 out | max normalised error %.3g" % (what, e))
+        elif self.mode == BF16:
+            r = cr.assert_bf16(got, ref, self.mag(pixels), self.k * self.k * self.cin, what)
+            print("bf16 bar | %s | worst |d|/eps %.4g | share %.3g" % (what, r["worst"], r["share"]))
         return got
 
 
@@ -276,6 +294,79 @@ def test_plane_paths_vs_fp64(mode, name, kw):
     _run_paths(conv, paths, bitwise, what="%s mode %d" % (name, mode))
     if mode == F32H2:
         assert int(ws[-4 * 512:].view(torch.int32).abs().sum()) == 0          # every stream-K hand-over flag consumed
+
+
+# ----------------------------------------------------------------------------- BF16: the tiles the rules pick on large launches
+def _num_cu():
+    n = torch.cuda.get_device_properties(0).multi_processor_count
+    return n & ~7 if n >= 8 else 256
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def _bf16_tile_rule(M, cout_pad, k3, out_f32, ncu):
+    """The tile yv3_conv2d_planes (conv_planes.hip) takes for a one-plane (BF16) descriptor with cout_pad % 128 == 0, no forced code
+    and no tune bits, and the tile counts the rule looks at."""
+    assert cout_pad % 128 == 0
+    blocks256 = _cdiv(M, 256) * (cout_pad // 128)
+    counts = {"blocks256": blocks256}
+    if k3 and not out_f32 and cout_pad % 256 == 0:
+        t256, t192 = _cdiv(M, 256) * (cout_pad // 256), _cdiv(M, 192) * (cout_pad // 256)
+        r256, r192 = _cdiv(t256, ncu) * ncu, _cdiv(t192, ncu) * ncu
+        counts.update(t256=t256, t192=t192)
+        if t192 * 100 >= 85 * r192 and t256 * 100 < 80 * r256:
+            return "192x256 ping-pong", counts
+        if (t256 * 10 >= 6 * ncu) if t256 <= ncu else (t256 * 10 >= 8 * r256):
+            return "256x256 ping-pong", counts
+    if blocks256 >= 256 and not out_f32:
+        return ("256x128 four waves, rolling" if k3 else "256x128 four waves, plain"), counts
+    if blocks256 >= 128:
+        return "256x128 eight waves, 6-deep", counts
+    return "128x128", counts
+
+
+# name, the tile the rule must pick, Conv kwargs without B: the smallest B at which the rule picks that tile is searched at run time from
+# the device's CU count (on 256 CUs: 58, 62, 7, 25, 96, 96)
+BF16_RULE_CASES = [
+    ("i 128-1024 k3 @13", "256x256 ping-pong", dict(cin=128, cout=1024, k=3, H=13, W=13, res=True)),
+    ("ii 512-1024 k3 @13", "192x256 ping-pong", dict(cin=512, cout=1024, k=3, H=13, W=13)),
+    ("iii 64-128 k3 @104", "256x128 four waves, rolling", dict(cin=64, cout=128, k=3, H=104, W=104, res=True)),
+    ("iv 256-128 1x1 @52", "256x128 four waves, plain", dict(cin=256, cout=128, k=1, H=52, W=52)),
+    ("v 512-256 1x1 @13", "256x128 eight waves, 6-deep", dict(cin=512, cout=256, k=1, H=13, W=13, res=True)),
+    ("v head255 @13", "256x128 eight waves, 6-deep", dict(cin=256, cout=255, cout_pad=256, k=1, H=13, W=13, alpha_none=True, out_f32=True,
+                                                          act=cr.ACT_LINEAR)),
+]
+
+
+@pytest.mark.parametrize("name,tile,kw", BF16_RULE_CASES, ids=[c[0] for c in BF16_RULE_CASES])
+def test_bf16_rule_tiles_vs_fp64_sampled(name, tile, kw):
+    """The BF16 tiles that only large launches reach -- 256x256 and 192x256 ping-pong, the four-wave 256x128 tile with the rolling (3x3)
+    and the plain (1x1) loop, the eight-wave 6-deep 256x128 tile (a 1x1 layer and an fp32 head) -- each at the smallest batch at which
+    the selection rule picks it on this device, against float64 on conv_ref.sample_rows with the BF16 bar (A + B; the head: the fp32
+    bar), and bit for bit against forced code 7 (the four-wave rolling tile: same K order)."""
+    ncu = _num_cu()
+    cout_pad = kw.get("cout_pad", kw["cout"])
+    Ho, Wo = cr.out_hw(kw["H"], kw["W"], kw["k"], 1)
+    rule = lambda b: _bf16_tile_rule(b * Ho * Wo, cout_pad, kw["k"] == 3, kw.get("out_f32", False), ncu)
+    B = next((b for b in range(1, 513) if rule(b)[0] == tile), None)
+    assert B is not None, "%s: no batch up to 512 makes the rule pick the %s tile on %d CUs" % (name, tile, ncu)
+    picked, counts = rule(B)
+    print("bf16 rule | %s | %d CUs | B = %d | %s | %s" % (name, ncu, B, picked, counts))
+    # the tile counts this case relies on
+    if tile == "256x256 ping-pong":
+        assert counts["t256"] * 10 >= 6 * ncu and counts["t256"] <= ncu
+        assert not (counts["t192"] * 100 >= 85 * _cdiv(counts["t192"], ncu) * ncu and counts["t256"] * 100 < 80 * ncu)
+    elif tile == "192x256 ping-pong":
+        assert counts["t192"] * 100 >= 85 * _cdiv(counts["t192"], ncu) * ncu and counts["t256"] * 100 < 80 * _cdiv(counts["t256"], ncu) * ncu
+    elif tile.startswith("256x128 four waves"):
+        assert counts["blocks256"] >= 256 and cout_pad % 256 != 0
+    else:
+        assert 128 <= counts["blocks256"] and (kw.get("out_f32", False) or counts["blocks256"] < 256)
+    conv = Conv(BF16, B=B, seed=300 + len(name), **kw)
+    rows = cr.sample_rows(conv.B, conv.Ho, conv.Wo, seed=5)
+    _run_paths(conv, [("default", 0, 0, None), ("code 7", _tile(7), 0, None)], ["code 7"], pixels=rows, what=name)
 
 
 # ----------------------------------------------------------------------------- fused decode

@@ -18,6 +18,7 @@ from yolo_v3_amd import _ffi, arch, synth, engine
 from yolo_v3_amd import YoloLayer, postprocessing, iou_vectorized, bbox_iou, bbox_cxcywh_to_x1y1x2y2
 from yolo_v3_amd.darknet import conv_bn_relu, res_layer, UpsampleGroup, PreDetectionConvGroup
 from tests.helpers import assert_close_rel, check_result_convention, rel_err
+from tests import conv_ref as cr, plan_ref
 
 pytestmark = pytest.mark.gpu
 ANCHOR_PAIRS = [(10, 13), (16, 30), (33, 23), (30, 61), (62, 45), (59, 119), (116, 90), (156, 198), (373, 326)]
@@ -336,6 +337,52 @@ def _ref_cbr(m, x):
     return F.leaky_relu(y, 0.1)
 
 
+def _rows(t_nchw):
+    return t_nchw.permute(0, 2, 3, 1).reshape(-1, t_nchw.shape[1])
+
+
+def _assert_bf16_cbr(out_nchw, m, x_nchw, what, round_w=True):
+    """The BF16 bar (tests/conv_ref.py: one bf16 rounding of float64 + fp32 summation round-off, criteria A and B) for the bf16 output
+    of conv_bn_relu `m` (on the CPU) on the input the kernel was fed: the reference gets the bf16-rounded weights (`round_w`; the
+    3-channel first layer keeps fp32 weights) and BatchNorm folded in float64, as plan_ref.fold_params folds it."""
+    w = m.conv.weight.detach().float()
+    w = oc.round_bf16(w) if round_w else w
+    alpha = m.bn.weight.detach().double() / torch.sqrt(m.bn.running_var.double() + float(m.bn.eps))
+    beta = m.bn.bias.detach().double() - m.bn.running_mean.double() * alpha
+    x = x_nchw.permute(0, 2, 3, 1).contiguous()
+    s, k = m.conv.stride[0], w.shape[2]
+    ref = cr.conv_desc_ref(x, w, beta, alpha, stride=s)
+    mag = cr.conv_desc_mag(x, w, beta, alpha, stride=s)
+    r = cr.assert_bf16(_rows(out_nchw), ref, mag, k * k * w.shape[1], what)
+    print("bf16 bar | %s | worst |d|/eps %.4g | share %.3g" % (what, r["worst"], r["share"]))
+
+
+def _assert_bf16_plan_launch(net, plan, name, image_nchw, what):
+    """One launch of an un-fused BF16 plan against float64 on the tensors the GPU fed it (read back from the plan's buffers, so that a
+    rounding flip upstream does not compound): every row, the BF16 bar."""
+    node = next(n for n in plan_ref.network_graph() if n.name == name)
+    p = plan_ref.fold_params(net)[name]
+    if node.spec.cin != 3:
+        p = p._replace(w=oc.round_bf16(p.w))
+
+    def held(producer):
+        if producer is None:
+            return None
+        if producer == plan_ref.IMAGE:
+            return image_nchw.float().cpu().permute(0, 2, 3, 1).contiguous()
+        return engine.from_planes(plan.layer_out[producer], _ffi.BF16).cpu()
+
+    x, res = held(node.x), held(node.residual)
+    ref = plan_ref.launch_ref(node, p, x, residual=res)
+    mag = cr.conv_desc_mag(x, p.w, p.beta, p.alpha, res, stride=node.spec.stride)
+    got = engine.from_planes(plan.layer_out[name], _ffi.BF16).cpu().reshape(-1, node.spec.cout)
+    r = cr.assert_bf16(got, ref, mag, node.spec.k ** 2 * node.spec.cin, what)
+    print("bf16 bar | %s | worst |d|/eps %.4g | share %.3g" % (what, r["worst"], r["share"]))
+
+
+BF16_LAUNCH_SHAPES = ((2, 96, 64), (5, 32, 32))       # where the fused-vs-two-launch tests also hold each of the two launches to float64
+
+
 def _run_mode(m, x_nchw, mode, residual_nchw=None):
     """conv_bn_relu `m` (already on the GPU) on NCHW fp32 input through the C-ABI in math mode `mode`."""
     sp = m._spec()
@@ -431,13 +478,14 @@ def test_conv_stream_k_schedule(cin, cout, k, s, B, H, W):
     assert torch.equal(y, first)
 
 
-@pytest.mark.parametrize("mode", [_ffi.F32, _ffi.F32X3, _ffi.F32H2])
+@pytest.mark.parametrize("mode", [_ffi.F32, _ffi.F32X3, _ffi.F32H2, _ffi.BF16])
 @pytest.mark.parametrize("B,H,W", [(2, 40, 56), (1, 9, 131), (3, 64, 32), (1, 33, 260)])
 def test_first_layer_all_modes_vs_fp64(B, H, W, mode):
     """yv3_conv0 (darknet.py:76): direct VALU kernel (fp32 / bf16x3 outputs) and the matrix-core kernel of the
     fp16-plane mode (K = 27 padded to 32, permuted channel rows, LDS-staged patch) on shapes with row / column
     tails and partial 128-column workgroup tiles; fp32-class tolerance 2e-5 * max(1,|ref|), and the un-split planes
-    reproduce the value exactly as stored."""
+    reproduce the value exactly as stored.  YV3_BF16: the same matrix-core kernel with ONE bf16 plane out -- image and weights stay
+    fp32, only the output is rounded: the BF16 bar (conv_ref.assert_bf16, K = 27)."""
     m = _rand_cbr(3, 32, 3, 1, seed=5)
     x = torch.rand(B, 3, H, W, generator=torch.Generator().manual_seed(3))
     ref = _ref_cbr(m, x)
@@ -449,7 +497,10 @@ def test_first_layer_all_modes_vs_fp64(B, H, W, mode):
     _ffi.check(_ffi.lib().yv3_conv0(xg.data_ptr(), pc.w.data_ptr(), pc.alpha.data_ptr(), pc.beta.data_ptr(), y.data_ptr(),
                                     B, H, W, mode, flags.data_ptr(), _ffi.stream_ptr()))
     out = engine.from_planes(y, mode).permute(0, 3, 1, 2).cpu()
-    assert_close_rel(out, ref, 2e-5, "first layer mode %d" % mode)
+    if mode == _ffi.BF16:
+        _assert_bf16_cbr(out, m.cpu(), x, "yv3_conv0 bf16 out %s" % ((B, H, W),), round_w=False)
+    else:
+        assert_close_rel(out, ref, 2e-5, "first layer mode %d" % mode)
     assert int(flags.item()) == 0
     if mode == _ffi.F32H2:                      # inputs beyond the scaled fp16 range are reported, not silently wrong
         xg[0, 1, 3, 4] = 5000.0
@@ -462,13 +513,15 @@ def test_first_layer_all_modes_vs_fp64(B, H, W, mode):
                                                  (256, 128, 1, 1, 64, 26, 26), (512, 1024, 3, 1, 24, 13, 13)])
 def test_conv_bf16_mode_vs_fp64(cin, cout, k, s, B, H, W):
     """YV3_BF16 (BASELINE config 3: bf16 convs): bf16 tensors + weights, fp32 accumulate and epilogue.
-    NOT a 1e-4 mode: operands carry 2^-9 relative rounding, so the tolerance is 2e-2 * max(1,|ref|)
-    against an fp64 reference fed the same bf16-rounded input."""
+    NOT a 1e-4 mode against the fp32 weights: operands carry 2^-9 relative rounding, so that tolerance is 2e-2 * max(1,|ref|)
+    against an fp64 reference fed the same bf16-rounded input.  Against the reference fed the bf16-rounded WEIGHTS as well, BatchNorm
+    folded in float64, the output is held to one bf16 rounding + fp32 summation round-off (conv_ref.assert_bf16)."""
     m = _rand_cbr(cin, cout, k, s, seed=cin + cout + k)
     x = (torch.rand(B, cin, H, W, generator=torch.Generator().manual_seed(1)) * 2 - 0.5).bfloat16().float()
     ref = _ref_cbr(m, x)
     out = _run_mode(m.cuda(), x, _ffi.BF16)
     assert_close_rel(out, ref, 2e-2, "bf16 conv %s" % ((cin, cout, k, s),))
+    _assert_bf16_cbr(out, m.cpu(), x, "bf16 conv %s" % ((cin, cout, k, s, B, H, W),))
 
 
 @pytest.mark.parametrize("cin,cout,s,B,H,W,selected", [(256, 512, 1, 16, 38, 38, True), (128, 256, 1, 8, 76, 76, True), (256, 512, 2, 3, 37, 41, False),
@@ -478,7 +531,7 @@ def test_conv_bf16_tile_variants_agree_bitwise(cin, cout, s, B, H, W, selected):
     the 192-row tile stages 24 pixel rows per wave = one DMA piece and a half) only changes the schedule -- same K order, so every
     forced tile must equal the library's own choice BIT FOR BIT, M tails included (23104 = 120 x 192 + 64 rows; 3 x 19 x 21 rows);
     `selected`: shapes whose tile counts make the shipped rule take the 192-row tile (switching the rule off through tune[1] bit 4
-    must change nothing either).  One small shape is also checked against fp64 (same tolerance as test_conv_bf16_mode_vs_fp64)."""
+    must change nothing either).  One small shape is also checked against fp64 (same bars as test_conv_bf16_mode_vs_fp64)."""
     m = _rand_cbr(cin, cout, 3, s, seed=cin + cout + 3).cuda()
     sp = m._spec()
     pc = engine.pack_conv(m, sp, _ffi.BF16)
@@ -506,6 +559,7 @@ def test_conv_bf16_tile_variants_agree_bitwise(cin, cout, s, B, H, W, selected):
     if B * ho * wo <= 4096:
         out = engine.from_planes(outs[11], _ffi.BF16).permute(0, 3, 1, 2).cpu()
         assert_close_rel(out, _ref_cbr(m.cpu(), xn), 2e-2, "bf16 192-row tile %s" % ((cin, cout, s),))
+        _assert_bf16_cbr(out, m.cpu(), xn, "bf16 192-row tile %s" % ((cin, cout, s, B, H, W),))
 
 
 @pytest.mark.parametrize("cin,cout,k,s,B,H,W,res", [(128, 256, 3, 1, 64, 52, 52, True), (64, 128, 3, 1, 7, 104, 104, True), (256, 512, 3, 2, 9, 37, 41, False),
@@ -687,7 +741,9 @@ def test_plain_resize_vs_oracle():
 def test_fused_front_equals_two_launches_bitwise(B, H, W, mode):
     """csrc/conv_front.hip (feature.mlist.0 + feature.mlist.1 in one launch, the first layer's activation kept in LDS) writes
     BIT FOR BIT what yv3_conv0 followed by yv3_conv2d writes (same products, same order), on square / non-square / tiny
-    inputs incl. all four image borders; whole-net detections are therefore identical too; saturation is still reported."""
+    inputs incl. all four image borders; whole-net detections are therefore identical too; saturation is still reported.
+    BF16 at (2, 96, 64) and (5, 32, 32): each of the two launches is also held to the BF16 bar against float64 on the tensors it was fed
+    (conv_ref.assert_bf16), which the bitwise equality then carries over to the fused kernel."""
     from yolo_v3_amd import YoloNet, WeightManager
     stream = synth.weight_stream()
     net = YoloNet((W, H)).eval()
@@ -702,6 +758,9 @@ def test_fused_front_equals_two_launches_bitwise(B, H, W, mode):
         try:
             d, plan = eng.forward(x)
             assert plan.fused_front == fused
+            if not fused and mode == _ffi.BF16 and (B, H, W) in BF16_LAUNCH_SHAPES:       # each of the two launches against float64
+                _assert_bf16_plan_launch(net, plan, "feature.mlist.0", x, "yv3_conv0 %s" % ((B, H, W),))
+                _assert_bf16_plan_launch(net, plan, "feature.mlist.1", x, "feature.mlist.1 %s" % ((B, H, W),))
             outs.append(plan.layer_out["feature.mlist.1"].clone())
             dets.append(d.clone())
         finally:
@@ -719,7 +778,8 @@ def test_fused_front_equals_two_launches_bitwise(B, H, W, mode):
 @pytest.mark.parametrize("B,H,W", [(2, 416, 416), (1, 608, 608), (3, 320, 480), (2, 96, 64), (5, 32, 32)])
 def test_fused_res64_equals_two_launches_bitwise(B, H, W, mode):
     """csrc/conv_res64.hip (feature.mlist.2 = 1x1 64->32 + 3x3 32->64 + residual add in one launch, the 32-channel map kept
-    in LDS) writes BIT FOR BIT what the two yv3_conv2d launches write, incl. all image borders; whole-net detections equal."""
+    in LDS) writes BIT FOR BIT what the two yv3_conv2d launches write, incl. all image borders; whole-net detections equal.
+    BF16 at (2, 96, 64) and (5, 32, 32): each of the two launches is also held to the BF16 bar against float64 on the tensors it was fed."""
     from yolo_v3_amd import YoloNet, WeightManager
     stream = synth.weight_stream()
     net = YoloNet((W, H)).eval()
@@ -734,6 +794,9 @@ def test_fused_res64_equals_two_launches_bitwise(B, H, W, mode):
         try:
             d, plan = eng.forward(x)
             assert plan.fused_res64 == fused and plan.first_desc == (3 if fused else 1)
+            if not fused and mode == _ffi.BF16 and (B, H, W) in BF16_LAUNCH_SHAPES:       # each of the two launches against float64
+                _assert_bf16_plan_launch(net, plan, "feature.mlist.2.conv1", x, "feature.mlist.2.conv1 %s" % ((B, H, W),))
+                _assert_bf16_plan_launch(net, plan, "feature.mlist.2.conv2", x, "feature.mlist.2.conv2 %s" % ((B, H, W),))
             outs.append(plan.layer_out["feature.mlist.2.conv2"].clone())
             dets.append(d.clone())
         finally:
