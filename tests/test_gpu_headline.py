@@ -1,7 +1,7 @@
 """The plans the benchmark actually times, against the CPU oracle (-m gpu, through the C-ABI).
 
 The kernel FORM of a 3x3 layer (direct implicit GEMM or Winograd F(2x2,3x3)) is chosen per launch from the tile count, the
-lane count and the CU count (csrc/conv_planes.hip: yv3_conv2d_planes_form), so "bs=32 one lane is green" does not imply
+lane count and the CU count (csrc/conv_select.cpp: yv3_select_planes), so "bs=32 one lane is green" does not imply
 "bs=64 two lanes is green".  This file closes that gap:
 
   * the headline workload of bench.py (416x416 bs=64, the 64 scenes ``scenes(64, 416, 1000)``, default math mode) through

@@ -1,0 +1,32 @@
+"""Records tests/golden/conv_select_256cu.json: yv3_conv2d_form / yv3_conv2d_launches over the grid of tests/conv_select_grid.py.
+
+Runs on the host (nothing is launched; without a GPU the library counts 256 compute units).  The table pins the library's kernel-selection
+rules: regenerate it only together with a deliberate change of a rule, and say which rows moved.
+
+    python tools/make_golden_conv_select.py [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+from yolo_v3_amd import _ffi                      # noqa: E402
+from tests import conv_select_grid as grid        # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden", "conv_select_256cu.json"))
+    args = ap.parse_args()
+    table = grid.table(_ffi.lib())
+    with open(args.out, "w") as f:
+        json.dump(table, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("%s: %d layer rows, %d invalid descriptors" % (args.out, len(table["layers"]), len(table["errors"])))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,12 +1,6 @@
 // C-ABI glue: version / error strings and the dtype dispatch of the convolution entry points.
 #include "yv3_common.h"
 
-int yv3_conv2d_f32(const yv3_conv_desc* d, hipStream_t s);
-int yv3_conv2d_planes(const yv3_conv_desc* d, int np, hipStream_t s);
-int yv3_conv2d_f32_form(const yv3_conv_desc* d);
-int yv3_conv2d_f32_launches(const yv3_conv_desc* d);      // (direct form only)
-int yv3_conv2d_planes_form(const yv3_conv_desc* d, int np);
-
 extern "C" int yv3_version(void) { return YV3_VERSION; }
 
 extern "C" const char* yv3_error_string(int code) {
@@ -52,28 +46,24 @@ static int check_dtype(const yv3_conv_desc* d) {
     return YV3_EDTYPE;
 }
 
-extern "C" int yv3_conv2d(const yv3_conv_desc* d, void* stream) {
-    int rc = check_desc(d);
+// yv3_conv2d and its two queries: the argument checks, ONE CU-count query, ONE call of the selector (conv_select.cpp) -- then launch
+// its choice or report its form / its number of launches (or the YV3_E* code the launch would return)
+enum { CONV_LAUNCH, CONV_FORM, CONV_LAUNCHES };
+static int conv2d(const yv3_conv_desc* d, int what, hipStream_t s) {
+    int rc = check_desc(d, what == CONV_LAUNCH);    // (the queries: a fused-decode head may not have its output bound yet)
     if (!rc) rc = check_dtype(d);
     if (rc) return rc;
-    if (d->dtype == YV3_F32) return yv3_conv2d_f32(d, (hipStream_t)stream);
-    return yv3_conv2d_planes(d, plane_count(d->dtype), (hipStream_t)stream);
+    const int ncu = yv3_num_cu(), np = plane_count(d->dtype);
+    if (d->dtype == YV3_F32) {
+        const yv3_f32_choice c = yv3_select_f32(d, ncu);
+        return c.rc ? c.rc : what == CONV_FORM ? c.form : what == CONV_LAUNCHES ? c.launches : yv3_conv2d_f32(d, c, ncu, s);
+    }
+    const yv3_planes_choice c = yv3_select_planes(d, np, ncu);
+    return c.rc ? c.rc : what == CONV_FORM ? c.form : what == CONV_LAUNCHES ? c.launches : yv3_conv2d_planes(d, np, c, ncu, s);
 }
-
-extern "C" int yv3_conv2d_form(const yv3_conv_desc* d) {
-    int rc = check_desc(d, false);                  // (a fused-decode head may not have its output bound yet)
-    if (!rc) rc = check_dtype(d);
-    if (rc) return rc;
-    if (d->dtype == YV3_F32) return yv3_conv2d_f32_form(d);
-    return yv3_conv2d_planes_form(d, plane_count(d->dtype));
-}
-
-extern "C" int yv3_conv2d_launches(const yv3_conv_desc* d) {
-    const int form = yv3_conv2d_form(d);
-    if (form < 0) return form;
-    if (form != YV3_FORM_DIRECT) return 2;
-    return d->dtype == YV3_F32 ? yv3_conv2d_f32_launches(d) : 1;
-}
+extern "C" int yv3_conv2d(const yv3_conv_desc* d, void* stream) { return conv2d(d, CONV_LAUNCH, (hipStream_t)stream); }
+extern "C" int yv3_conv2d_form(const yv3_conv_desc* d) { return conv2d(d, CONV_FORM, nullptr); }
+extern "C" int yv3_conv2d_launches(const yv3_conv_desc* d) { return conv2d(d, CONV_LAUNCHES, nullptr); }
 
 extern "C" int yv3_conv2d_sequence(const yv3_conv_desc* descs, int n, void* stream) {
     if (!descs || n < 0) return YV3_EINVAL;

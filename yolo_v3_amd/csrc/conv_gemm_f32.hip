@@ -284,72 +284,29 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_gemm1x1_f32_kernel(const
 
 }  // namespace
 
-// Does the persistent GEMM take this fp32 descriptor?  Plain 1x1 / stride-1 layers and 3x3 layers (any stride; the caller has ruled the
-// Winograd forms out) without residual or upsample operand whose tiles fill at least one round of the chip (tune[0] == 13: never, 14:
-// whenever the shape fits)
-static void gemm1_tiling(const yv3_conv_desc* d, int* bm, int* bn) { const bool wide = d->cout % 128 == 0; *bm = wide ? 128 : 256; *bn = wide ? 128 : 64; }
-bool yv3_gemm1x1_f32_takes(const yv3_conv_desc* d) {
-    // (3x3 layers: built, bit-identical and measured -- 113-122 TFLOP/s where the 128x128 eight-wave tiles give 116-124: the long K loops
-    // of these layers amortise a tile's prologue and epilogue anyway, profiles/r06ag_gemm_k3_stride2_ab.txt -- taken with tune[0] == 14 only)
-    const bool k1 = d->k == 1 && d->stride == 1, k3 = d->k == 3 && d->cout % 128 == 0 && d->tune[0] == 14;
-    if (!(k1 || k3) || d->cin_up || d->residual || d->cin % 32 || d->cout % 64 || d->cout > 1024 || d->cout_pad != d->cout || d->tune[0] == 13) return false;
-    const int pad = (d->k - 1) / 2;
-    const long long Ho = (d->H + 2 * pad - d->k) / d->stride + 1, Wo = (d->W + 2 * pad - d->k) / d->stride + 1;
-    const long long M = (long long)d->B * Ho * Wo;
-    if ((long long)d->B * d->H * d->W * d->cin * 4 > 0xfffffe00LL || M * d->cout * 4 > 0xffffffffLL || (long long)d->cout * d->cin * d->k * d->k * 4 > 0xffffffffLL) return false;
-    int bm, bn; gemm1_tiling(d, &bm, &bn);
-    const long long tiles = ((M + bm - 1) / bm) * (d->cout / bn);
-    return d->tune[0] == 14 || tiles >= (long long)yv3_num_cu();
-}
+static_assert(YV3_SEL_CHUNK == 32 && YV3_SEL_GEMM_WAVE_M == 64 && YV3_SEL_GEMM_WAVE_N == 32, "conv_select.cpp counts this kernel's chunks and 64 WM x 32 WN tiles");
 
-// Pixel-row tiles that run on the GEMM: whole rounds of the chip, plus the last partial round when it is more than half full (measured,
-// profiles/r06am_gemm1x1_ring_depth4_ab.txt: a rest of 0.28 / 0.33 rounds is cheaper on the small tiles, which fill the chip two to four to a
-// CU -- 0.109 vs 0.111 ms, 0.106 vs 0.125; a rest of 0.64 rounds is cheaper as one more round here: 0.100 vs 0.103, 0.054 vs 0.057)
-static long long gemm1_mtiles_here(const yv3_conv_desc* d, long long M, int bm, int bn) {
-    const int ncu = yv3_num_cu(), ntn = d->cout / bn;
-    const long long mt = (M + bm - 1) / bm;
-    if (d->tune[1] == 3) return mt;                                        // (every row here -- measurements)
-    const long long rounds = mt * ntn / ncu, rest = mt * ntn - rounds * ncu;
-    return rounds >= 1 && rest > 0 && 2 * rest <= ncu ? rounds * ncu / ntn : mt;
-}
-
-// Kernel launches of a descriptor yv3_gemm1x1_f32_takes says yes to (1, or 2 with rows left for the small tiles)
-int yv3_gemm1x1_f32_launches(const yv3_conv_desc* d) {
-    const int pad = (d->k - 1) / 2;
-    const long long Ho = (d->H + 2 * pad - d->k) / d->stride + 1, Wo = (d->W + 2 * pad - d->k) / d->stride + 1;
-    const long long M = (long long)d->B * Ho * Wo;
-    int bm, bn; gemm1_tiling(d, &bm, &bn);
-    return gemm1_mtiles_here(d, M, bm, bn) * bm < M ? 2 : 1;
-}
-
-// Launches the GEMM on output pixels [0, *rows_done): whole rounds of the chip (one tile per CU and round) -- plus the last, partial round when
-// it is more than half full.  The caller runs the remaining rows (< half a round of tiles) on conv_igemm_f32.hip's tiles, which fill
-// the chip two to four to a CU and finish in a fraction of a round here: 1352 tiles = 5.28 rounds would cost 6 (same K order: same bits).
-int yv3_conv2d_gemm1x1_f32(const yv3_conv_desc* d, hipStream_t s, long long* rows_done) {
+// Launches the GEMM on output pixels [0, c.gemm_rows): whole rounds of the chip (one tile per CU and round) -- plus the last, partial round when
+// it is more than half full (conv_select.cpp).  The caller runs the remaining rows on conv_igemm_f32.hip's tiles.
+int yv3_conv2d_gemm1x1_f32(const yv3_conv_desc* d, const yv3_f32_choice& c, int ncu, hipStream_t s) {
     Gemm1Params p;
     p.x = (const float*)d->x; p.w = (const float*)d->w; p.alpha = d->alpha; p.beta = d->beta; p.y = (float*)d->y;
-    const int pad = (d->k - 1) / 2;
     p.H = d->H; p.W = d->W; p.Cin = d->cin; p.stride = d->stride; p.cch = d->cin / 32;
-    p.Ho = (d->H + 2 * pad - d->k) / d->stride + 1; p.Wo = (d->W + 2 * pad - d->k) / d->stride + 1;
-    const long long M = (long long)d->B * p.Ho * p.Wo;
-    if (M > 0x7fffffffLL) return YV3_ESHAPE;
-    int bm, bn; gemm1_tiling(d, &bm, &bn);
-    const int ntn = d->cout / bn;
-    const int ncu = yv3_num_cu();
-    const long long mt_run = gemm1_mtiles_here(d, M, bm, bn);
-    const long long Mr = mt_run * bm < M ? mt_run * bm : M;
-    *rows_done = Mr;
+    p.Ho = c.Ho; p.Wo = c.Wo;
+    const bool wide = c.kernel != YV3_FK_GEMM_256x64;
+    const int bm = wide ? 128 : 256, bn = wide ? 128 : 64;
+    const long long Mr = c.gemm_rows;
     p.M = (int)Mr; p.K = d->k * d->k * d->cin; p.N = d->cout; p.nch = p.K / 32; p.act = d->act;
     p.x_bytes = (unsigned)((long long)d->B * d->H * d->W * d->cin * 4); p.y_bytes = (unsigned)(Mr * d->cout * 4);
     p.w_bytes = (unsigned)((long long)d->cout * p.K * 4);
-    p.ntn = ntn;
-    const long long tiles = mt_run * ntn;
+    p.ntn = c.ntiles;
+    const long long tiles = ((Mr + bm - 1) / bm) * p.ntn;
     p.ntiles = (int)tiles;
     const int grid = (int)(tiles < ncu ? (tiles + 7) / 8 * 8 : ncu);
     const size_t lds = (size_t)G1_NST * (bm + bn) * 128 + 2 * d->cout * sizeof(float);
-    if (d->k == 3)      hipLaunchKernelGGL((conv_gemm1x1_f32_kernel<2, 4, true>), dim3(grid), dim3(512), lds, s, p);
-    else if (bn == 128) hipLaunchKernelGGL((conv_gemm1x1_f32_kernel<2, 4, false>), dim3(grid), dim3(512), lds, s, p);
-    else                hipLaunchKernelGGL((conv_gemm1x1_f32_kernel<4, 2, false>), dim3(grid), dim3(512), lds, s, p);
+    if (c.kernel == YV3_FK_GEMM_K3)      hipLaunchKernelGGL((conv_gemm1x1_f32_kernel<2, 4, true>), dim3(grid), dim3(512), lds, s, p);
+    else if (wide)                       hipLaunchKernelGGL((conv_gemm1x1_f32_kernel<2, 4, false>), dim3(grid), dim3(512), lds, s, p);
+    else                                 hipLaunchKernelGGL((conv_gemm1x1_f32_kernel<4, 2, false>), dim3(grid), dim3(512), lds, s, p);
     YV3_CHECK_LAUNCH();
     return 0;
 }

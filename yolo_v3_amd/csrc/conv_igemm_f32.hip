@@ -375,14 +375,25 @@ int launch(const ConvParams& p, bool k3, bool dual, hipStream_t s, bool pin) {
 }  // namespace
 
 int yv3_wino_input_transform_f32(const float* x, float* v, int B, int H, int W, int C, hipStream_t s);
+int yv3_conv2d_wino4_f32(const yv3_conv_desc* d, const yv3_f32_choice& c, hipStream_t s);                   // csrc/conv_wino4_f32.hip
+int yv3_conv2d_gemm1x1_f32(const yv3_conv_desc* d, const yv3_f32_choice& c, int ncu, hipStream_t s);        // csrc/conv_gemm_f32.hip: persistent DMA-fed GEMM
 
-// Winograd F(2x2,3x3) form of a 3x3 / stride-1 fp32 layer: fp32 MFMA throughout, 2.25x fewer matrix instructions; differs from
-// the direct kernel (an fmaf chain in K order) by fp32 round-off of the re-associated sums.
-static int launch_wino_f32(const yv3_conv_desc* d, ConvParams p, hipStream_t s) {
+static_assert(BK == YV3_SEL_CHUNK, "conv_select.cpp counts K chunks of BK elements");
+
+// Winograd F(2x2,3x3) form of a 3x3 / stride-1 fp32 layer: input transform (winograd.hip) + the 16-position GEMM stage on the 128x128
+// eight-wave tile or (half) the 64x128 four-wave tile, two workgroups per CU (the rule: conv_select.cpp)
+template <int BM, int WM, int MINW>
+static void launch_wino_stage(const ConvParams& p, long long T, bool pin, hipStream_t s) {
+    constexpr int BN = 128, WN = 2;
+    const dim3 grid((unsigned)(((T + BM - 1) / BM) * p.ntiles));
+    const size_t pipe = (size_t)2 * (BM + BN) * LDS_LD * sizeof(float);
+    const size_t epi = (size_t)WM * WN * (BM / WM) * (BN / WN + 4) * sizeof(float);
+    if (pin) hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WM, WN, false, false, true, MINW, true>), grid, dim3(64 * WM * WN), pipe > epi ? pipe : epi, s, p);
+    else hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WM, WN, false, false, true, MINW>), grid, dim3(64 * WM * WN), pipe > epi ? pipe : epi, s, p);
+}
+static int launch_wino_f32(const yv3_conv_desc* d, ConvParams p, bool half, bool pin, hipStream_t s) {
     const int th = (d->H + 1) / 2, tw = (d->W + 1) / 2;
     const long long T = (long long)d->B * th * tw;
-    if (T > 0x7fffffffLL || d->cout % 128 || d->cout_pad != d->cout || d->cin % 32) return YV3_ESHAPE;
-    if (!d->wino_ws || d->wino_ws_bytes < (size_t)16 * T * d->cin * sizeof(float)) return YV3_EWORKSPACE;
     float* v = (float*)d->wino_ws;
     const int rc = yv3_wino_input_transform_f32(p.x, v, d->B, d->H, d->W, d->cin, s);
     if (rc) return rc;
@@ -391,124 +402,41 @@ static int launch_wino_f32(const yv3_conv_desc* d, ConvParams p, hipStream_t s) 
     p.wH = d->H; p.wW = d->W; p.wth = th; p.wtw = tw;
     p.H = 1; p.W = (int)T; p.Ho = 1; p.Wo = (int)T; p.M = (int)T; p.stride = 1;
     p.K = 16 * d->cin; p.nk = p.K / BK;
-    p.ntiles = d->cout / 128;
-    // Round 5: the stage keeps five accumulator sets (216 registers): its 128x128 eight-wave tile runs ONE workgroup per CU, and a launch whose
-    // tiles fill e.g. 1.33 rounds of the chip (256->512 @26x26 bs=64: 340 tiles on 256 CUs) spends a whole second tile time on 84 tiles.  The
-    // same wave tiles (32x64) as a 64x128 tile on FOUR waves, two workgroups per CU (2 x 55 KB of LDS), halve the scheduling quantum: the last
-    // round's half-size tiles spread over more CUs.  Same K order per accumulator: bit-identical.  Chosen when the 128-row tiles leave the last
-    // round at most two thirds full beyond the first round, or fill at most half of the chip (then twice as many CUs work).  Same box,
-    // alternating (tools/wino_f32_tile_ab.py, profiles/r05t_f32_wino_four_wave_tile_ab.txt): 256->512 @26 bs=64 (340 tiles) 0.615 -> 0.515 ms,
-    // 128->256 @52 bs=32 (338) 0.362 -> 0.308, 512->1024 @13 bs=32 (104) 0.549 -> 0.349, @19 bs=16 (104) 0.549 -> 0.349; 200 / 172 / 184 tiles
-    // (0.67-0.78 of a round): 2-3 % slower, kept on the eight-wave tile.  (tune[0] == 8 / 9: force the four-wave / the eight-wave tile.)
-    const long long t128 = ((T + 127) / 128) * p.ntiles;
-    const long long ncu = yv3_num_cu();
-    const long long last = t128 % ncu;
-    const bool pin = !(d->options & YV3_OPT_TWO_LANES);
-    const bool half = d->tune[0] == 8 || (d->tune[0] != 9 && ((t128 > ncu && last > 0 && 3 * last <= 2 * ncu) || 2 * t128 <= ncu));
-    if (half) {
-        constexpr int BM = 64, BN = 128, WM = 2, WN = 2;
-        const dim3 grid((unsigned)(((T + BM - 1) / BM) * p.ntiles));
-        const size_t pipe = (size_t)2 * (BM + BN) * LDS_LD * sizeof(float);
-        const size_t epi = (size_t)WM * WN * (BM / WM) * (BN / WN + 4) * sizeof(float);
-        if (pin) hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WM, WN, false, false, true, 2, true>), grid, dim3(64 * WM * WN), pipe > epi ? pipe : epi, s, p);
-        else hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WM, WN, false, false, true, 2>), grid, dim3(64 * WM * WN), pipe > epi ? pipe : epi, s, p);
-    } else {
-        constexpr int BM = 128, BN = 128, WM = 4, WN = 2;
-        const dim3 grid((unsigned)(((T + BM - 1) / BM) * p.ntiles));
-        const size_t pipe = (size_t)2 * (BM + BN) * LDS_LD * sizeof(float);
-        const size_t epi = (size_t)WM * WN * (BM / WM) * (BN / WN + 4) * sizeof(float);
-        if (pin) hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WM, WN, false, false, true, 1, true>), grid, dim3(64 * WM * WN), pipe > epi ? pipe : epi, s, p);
-        else hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WM, WN, false, false, true>), grid, dim3(64 * WM * WN), pipe > epi ? pipe : epi, s, p);
-    }
+    if (half) launch_wino_stage<64, 2, 2>(p, T, pin, s);
+    else launch_wino_stage<128, 4, 1>(p, T, pin, s);
     YV3_CHECK_LAUNCH();
     return 0;
 }
 
-int yv3_conv2d_wino4_f32(const yv3_conv_desc* d, hipStream_t s);
-int yv3_conv2d_gemm1x1_f32(const yv3_conv_desc* d, hipStream_t s, long long* rows_done);      // csrc/conv_gemm_f32.hip: plain 1x1 layers, persistent DMA-fed GEMM
-bool yv3_gemm1x1_f32_takes(const yv3_conv_desc* d);
-int yv3_gemm1x1_f32_launches(const yv3_conv_desc* d);
-long long yv3_wino4_f32_workgroups(const yv3_conv_desc* d);
-bool yv3_wino4_f32_pays(const yv3_conv_desc* d);
-
-// Which form does this fp32 descriptor take: direct (0), Winograd F(2x2,3x3) (1) or F(4x4,3x3) (2)?  (exported through yv3_conv2d_form)
-int yv3_conv2d_f32_form(const yv3_conv_desc* d) {
-    const bool k3 = d->k == 3, dual = d->cin_up > 0;
-    {   // the shape error yv3_conv2d_f32 reports before it launches anything (the form query returns what the launch would)
-        const int pad = (d->k - 1) / 2;
-        const long long Ho = (d->H + 2 * pad - d->k) / d->stride + 1, Wo = (d->W + 2 * pad - d->k) / d->stride + 1;
-        if ((long long)d->B * Ho * Wo > 0x7fffffffLL) return YV3_ESHAPE;
-    }
-    // F(4x4,3x3) (csrc/conv_wino4_f32.hip): 4x fewer matrix instructions than direct.  Its workgroups are 64 channels x 32 tiles of 4x4 pixels,
-    // two per CU: taken by yv3_wino4_f32_pays (tune[0] == 10: never, 11: whenever the filters are there).  Round 6, one item per workgroup, same box,
-    // direct / F(2x2) / F(4x4) (profiles/r06o_wino4_forms_by_batch.txt): it is the fastest form of every eligible layer from 8 images of
-    // 416x416 up (bs=8: 128->256 @52 0.139 / 0.117 / 0.070 ms, 256->512 @26 0.136 / 0.185 / 0.105; 64 workgroups: 0.187 / 0.337 / 0.182);
-    // at 88 workgroups (bs=4 @52) 0.072 / 0.110 / 0.065, at 56 (bs=4 @26) 0.096 / 0.184 / 0.103 -- the crossover
-    if (d->w_wino4 && d->wino_ws && k3 && d->stride == 1 && !dual && d->cout % 64 == 0 && (d->cin == 64 || d->cin % 128 == 0) && d->cout_pad == d->cout && d->alpha && d->tune[0] != 10) {
-        if ((d->options & YV3_OPT_WINO_ALWAYS) || d->tune[0] == 11 || yv3_wino4_f32_pays(d))
-            return d->wino_ws_bytes < yv3_wino4_workspace_bytes(d->B, d->H, d->W, d->cin) ? YV3_EWORKSPACE : YV3_FORM_WINOGRAD4;
-    }
-    if (!(d->w_wino && d->alpha_wino && k3 && d->stride == 1 && !dual && d->cout % 128 == 0 && d->cout_pad == d->cout)) return 0;
-    // fp32 MFMA runs at the vector rate, so this layer is matrix-bound whatever its shape: Winograd whenever the 128x128 tiles
-    // (a quarter of the direct kernel's rows) still fill a good part of the chip, or YV3_OPT_WINO_ALWAYS
-    const long long T2 = (long long)d->B * ((d->H + 1) / 2) * ((d->W + 1) / 2);
-    const long long tiles = ((T2 + 127) / 128) * (d->cout / 128);
-    if (!((d->options & YV3_OPT_WINO_ALWAYS) || tiles * 100 >= 40 * yv3_num_cu())) return 0;
-    return (!d->wino_ws || d->wino_ws_bytes < (size_t)16 * T2 * d->cin * sizeof(float)) ? YV3_EWORKSPACE : YV3_FORM_WINOGRAD;
-}
-
-// kernel launches of a descriptor that takes the direct form (exported through yv3_conv2d_launches)
-int yv3_conv2d_f32_launches(const yv3_conv_desc* d) { return yv3_gemm1x1_f32_takes(d) ? yv3_gemm1x1_f32_launches(d) : 1; }
-
-int yv3_conv2d_f32(const yv3_conv_desc* d, hipStream_t s) {
+// Launches what the selector chose (conv_select.cpp: yv3_select_f32) for a descriptor that passed its checks.
+int yv3_conv2d_f32(const yv3_conv_desc* d, const yv3_f32_choice& c, int ncu, hipStream_t s) {
+    if (c.kernel == YV3_FK_WINO4) return yv3_conv2d_wino4_f32(d, c, s);
     ConvParams p;
     p.x = (const float*)d->x; p.x2 = (const float*)d->x2; p.w = (const float*)d->w;
     p.alpha = d->alpha; p.beta = d->beta; p.res = (const float*)d->residual; p.y = (float*)d->y;
     p.H = d->H; p.W = d->W; p.Cin = d->cin; p.Cup = d->cin_up; p.Cout = d->cout;
     p.stride = d->stride; p.act = d->act; p.m_base = 0;
-    const int pad = (d->k - 1) / 2;
-    p.Ho = (d->H + 2 * pad - d->k) / d->stride + 1;
-    p.Wo = (d->W + 2 * pad - d->k) / d->stride + 1;
-    const long long M = (long long)d->B * p.Ho * p.Wo;
-    if (M > 0x7fffffffLL) return YV3_ESHAPE;
-    p.M = (int)M;
+    p.Ho = c.Ho; p.Wo = c.Wo; p.M = c.M;
     p.K = d->k * d->k * d->cin;
     p.cchunks = d->cin / BK;
     p.nk = p.K / BK;
+    p.ntiles = c.ntiles;
     const bool k3 = d->k == 3, dual = d->cin_up > 0;
-    const bool pin = !(d->options & YV3_OPT_TWO_LANES);           // (see PIN)
-    const int form = yv3_conv2d_f32_form(d);
-    if (form < 0) return form;
-    if (form == YV3_FORM_WINOGRAD4) return yv3_conv2d_wino4_f32(d, s);
-    if (form == YV3_FORM_WINOGRAD) return launch_wino_f32(d, p, s);
-    if (yv3_gemm1x1_f32_takes(d)) {
-        // plain 1x1 / 3x3 layer: whole rounds of the chip on the persistent GEMM, the rest (< half a round of its tiles) on the tiles below
-        // (same K order per output element: same bits whoever computes a row)
-        long long done = 0;
-        const int rc = yv3_conv2d_gemm1x1_f32(d, s, &done);
-        if (rc || done >= M) return rc;
-        p.m_base = (int)done;
-        const int np1 = d->cout_pad;
-        if (k3) { p.ntiles = np1 / 128; return launch<128, 128, 4, 2>(p, true, false, s, pin); }
-        p.ntiles = np1 / 64;
-        return np1 % 128 == 0 ? launch<64, 64, 2, 2>(p, false, false, s, pin) : launch<128, 64, 2, 2>(p, false, false, s, pin);
+    yv3_f32_kernel kernel = c.kernel;
+    if (kernel == YV3_FK_GEMM_128x128 || kernel == YV3_FK_GEMM_256x64 || kernel == YV3_FK_GEMM_K3) {
+        // whole rounds of the chip on the persistent GEMM, the rest (< half a round of its tiles) on the tiles below
+        const int rc = yv3_conv2d_gemm1x1_f32(d, c, ncu, s);
+        if (rc || c.rest == YV3_FK_NONE) return rc;
+        p.m_base = c.gemm_rows; p.ntiles = c.rest_ntiles;
+        kernel = c.rest;
     }
-
-    // Tile selection: widest N tile the layer fills; for launches that would leave most of the
-    // 256 CUs idle (small batch at 13x13 / 26x26) fall back to 64x64 tiles for 4x the blocks.
-    const int np = d->cout_pad;
-    if (np % 128 == 0) {
-        const long long blocks128 = ((M + 127) / 128) * (np / 128);
-        // (tune[0]: kernel-selection override for A/B measurements -- 6 four-wave 128x128, 2 64x64 tiles)
-        if (blocks128 >= 384 && d->tune[0] == 6) { p.ntiles = np / 128; return launch<128, 128, 2, 2>(p, k3, dual, s, pin); }
-        // eight waves (4 x 2 of 32x64) per 128x128 tile, two workgroups per CU: four waves per SIMD hide each other's fragment
-        // reads / barriers better than two (13x13 3x3 layer at bs=64: 80 -> 102 TFLOP/s, whole network +5 %)
-        // 1x1 layers (K <= 1024: 8-32 chunks per tile) run better on 64x64 tiles, four workgroups per CU: 512->256 @26x26 at bs=64
-        // 82 -> 103 TFLOP/s, 256->128 @52x52 95 -> 98 (tune[0] == 7: 128x128 tiles for them too)
-        if (blocks128 >= 384 && d->tune[0] != 2 && (k3 || d->tune[0] == 7)) { p.ntiles = np / 128; return launch<128, 128, 4, 2>(p, k3, dual, s, pin); }
-        p.ntiles = np / 64; return launch<64, 64, 2, 2>(p, k3, dual, s, pin);
+    switch (kernel) {
+        case YV3_FK_WINO2:      return launch_wino_f32(d, p, c.wino2_half, c.pin, s);
+        case YV3_FK_128x128_W8: return launch<128, 128, 4, 2>(p, k3, dual, s, c.pin);
+        case YV3_FK_128x128_W4: return launch<128, 128, 2, 2>(p, k3, dual, s, c.pin);
+        case YV3_FK_64x64:      return launch<64, 64, 2, 2>(p, k3, dual, s, c.pin);
+        case YV3_FK_128x64:     return launch<128, 64, 2, 2>(p, k3, dual, s, c.pin);
+        case YV3_FK_128x32:     return launch<128, 32, 4, 1>(p, k3, dual, s, c.pin);
+        default:                return YV3_EINVAL;
     }
-    if (np % 64 == 0) { p.ntiles = np / 64; return launch<128, 64, 2, 2>(p, k3, dual, s, pin); }
-    p.ntiles = np / 32;
-    return launch<128, 32, 4, 1>(p, k3, dual, s, pin);
 }

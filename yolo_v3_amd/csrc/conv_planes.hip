@@ -41,11 +41,7 @@ template <int N> __device__ __forceinline__ void wait_lgkmcnt() { __builtin_amdg
                               defined(YV3_EXP_BF16MFMA) || defined(YV3_AB_NO_TWO_LANES_RULE))
 #error "measurement switches need -DYV3_MEASURE (make measure / tools/build_variant.sh); the shipped library has none"
 #endif
-// Measurement switches.  Run time (yv3_conv_desc.tune[], set by tools/ through YV3_TUNE=a,b,c,d; 0 = the shipped behaviour):
-//   tune[1] bit 0  no two-workgroup tile for the short-K 1x1 layers      bit 1  Winograd stage: rolling instead of ping-pong main loop      bit 4  bf16: no 192-row variant of the 256x256 tile
-//           bit 3  bf16: round-3 tile selection (no rolling loop, no 256x256 tile)
-//   tune[2]        bf16: threshold (256x128 tiles) from which the four-wave tile is used
-//   tune[3] (measurement builds, -DYV3_MEASURE, only) bit 0  epilogue without its stores   bit 1  without its residual loads   (results INVALID)
+// Measurement switches.  Run time: yv3_conv_desc.tune[] (conv_select.h names the codes; tune[3], measurement builds only: epilogue IO ablations).
 // Compile time (A/B builds through tools/build_variant.sh):
 // YV3_WABL (timing ablations of the Winograd GEMM stage's ping-pong loop, results INVALID; tools/timeline.py --kernel wino):
 //   1 no DMA pieces in the compute segment   2 both k-steps' fragments read in the load segment (no SPLIT)
@@ -768,7 +764,7 @@ __global__ __launch_bounds__(64 * WM * WN, MINW) void conv_planes_kernel(const C
 }
 
 template <int NP, int BM, int BN, int WM, int WN, int NSTAGE, int MINW = 1, int MTG = 0, bool ROLL = false>
-int launch_cfg(const ConvParamsP& p, bool k3, bool dual, bool out_f32, bool use_pp, hipStream_t s) {
+int launch_cfg(const ConvParamsP& p, bool k3, bool dual, bool out_f32, bool use_pp, int num_cu, hipStream_t s) {
     const int mtiles = (p.M + BM - 1) / BM;
     const dim3 grid((unsigned)(mtiles * p.ntiles));
     const dim3 block(64 * WM * WN);
@@ -776,7 +772,7 @@ int launch_cfg(const ConvParamsP& p, bool k3, bool dual, bool out_f32, bool use_
     const size_t epi = (size_t)WM * WN * (MTG ? MTG * 32 : BM / WM) * (BN / WN + 4) * 4;   // WM*WN waves x rows per round x (BN/WN + 4) floats
     const size_t lds = pipe > epi ? pipe : epi;
     const bool use_sk = true;                                      // stream-K persistent schedule iff the caller gave a workspace
-    const int num_cu = yv3_num_cu();                               // of the CURRENT device; multiple of 8: equal workgroups per XCD
+    // (num_cu: of the CURRENT device; multiple of 8: equal workgroups per XCD)
     ConvParamsP q = p;
     q.total = (int)grid.x;
     // stream-K: opt-in (the caller passes yv3_conv_desc.workspace): a split tile is summed as head + middle.. + tail, so its rounding
@@ -902,17 +898,15 @@ extern "C" int yv3_merge_planes(const void* in, float* out, long long n, int np,
     return 0;
 }
 
-int yv3_conv2d_planes_k3s1(const ConvParamsP* pp, int np, int npad, long long M, hipStream_t s);
-int yv3_conv2d_planes_w4(const ConvParamsP* pp, int np, int npad, hipStream_t s);
+int yv3_conv2d_planes_k3s1(const ConvParamsP& p, int np, yv3_planes_kernel kernel, hipStream_t s);
+int yv3_conv2d_planes_w4(const ConvParamsP& p, hipStream_t s);
 int yv3_wino_input_transform(const u16* x, long long xs, u16* v, int B, int H, int W, int C, hipStream_t s);
 
 // Winograd F(2x2,3x3) form of a 3x3 / stride-1 fp16-plane layer: input transform (winograd.hip) + the 16-position GEMM with the
 // output transform folded into the main loop.  `p` = the direct launch's parameters (x, res, y, strides, Cout, act, flags).
-static int launch_wino(const yv3_conv_desc* d, ConvParamsP p, hipStream_t s) {
+static int launch_wino(const yv3_conv_desc* d, ConvParamsP p, yv3_planes_kernel kernel, int num_cu, hipStream_t s) {
     const int th = (d->H + 1) / 2, tw = (d->W + 1) / 2;
     const long long T = (long long)d->B * th * tw;
-    if (T > 0x7fffffffLL || d->cout_pad % 128 || d->cin % 32) return YV3_ESHAPE;
-    if (!d->wino_ws || d->wino_ws_bytes < (size_t)2 * 16 * T * d->cin * sizeof(u16)) return YV3_EWORKSPACE;
     u16* v = (u16*)d->wino_ws;
     int rc = yv3_wino_input_transform(p.x, p.xs, v, d->B, d->H, d->W, d->cin, s);
     if (rc) return rc;
@@ -921,36 +915,24 @@ static int launch_wino(const yv3_conv_desc* d, ConvParamsP p, hipStream_t s) {
     p.wH = d->H; p.wW = d->W; p.wth = th; p.wtw = tw;
     p.H = 1; p.W = (int)T; p.Ho = 1; p.Wo = (int)T; p.M = (int)T; p.stride = 1;
     p.K = 16 * d->cin; p.nk = p.K / PBK;
-    p.tb = 128; p.ntiles = d->cout_pad / 128;
+    p.tb = 128;
     constexpr int BM = 128, BN = 128, NS = 4;
     const dim3 grid((unsigned)(((T + BM - 1) / BM) * p.ntiles));
     p.total = (int)grid.x;
     const size_t pipe = (size_t)NS * 2 * (BM + BN) * ROWB, epi = (size_t)8 * 32 * (BN / 2 + 4) * 4;
     const size_t lds = pipe > epi ? pipe : epi;
-    // Schedules.  Default: one 128x128 tile (all 16 positions, 16 x Cin/32 chunks) per workgroup -- bitwise independent of the
-    // batch composition.  YV3_OPT_WINO_EVEN: stream-K over transform positions -- one persistent workgroup per CU takes an equal,
-    // contiguous range of (tile, position) units of its XCD and hands partial outputs over inside the XCD's L2 (see the
-    // kernel); a split tile is summed head + tail.  Measured (tools/wino_ab.py, profiles/r03_wino_ab2.log): it only wins below
-    // half a round of tiles (512->1024 @19x19 bs=16: 0.176 vs 0.202 ms) and loses 3...30 % above (256 KB of partial outputs per
-    // split, no dynamic tile dispatch, and a partly filled round simply clocks higher on this power-limited chip): opt-in.
-    const int num_cu = yv3_num_cu();
-    const size_t vbytes = (size_t)2 * 16 * T * d->cin * sizeof(u16);
-    const bool even = (d->options & YV3_OPT_WINO_EVEN) && num_cu <= YV3_WINO_SK_MAX_WG && (long long)p.total * 16 >= num_cu &&
-                      p.total % num_cu != 0 && d->wino_ws_bytes >= vbytes + yv3_wino_sk_bytes();
-    if (even) {
+    if (kernel == YV3_PK_WINO_EVEN) {
+        const size_t vbytes = (size_t)2 * 16 * T * d->cin * sizeof(u16);
         p.ws = (float*)((char*)d->wino_ws + ((vbytes + 255) & ~(size_t)255));
         p.wsflags = (int*)((char*)p.ws + (size_t)YV3_WINO_SK_MAX_WG * YV3_WINO_SK_PART_BYTES);
         p.ws_bytes = yv3_wino_sk_bytes();
         hipLaunchKernelGGL((conv_planes_kernel<2, BM, BN, 4, 2, NS, false, false, false, true, true, 1, 0, true>), dim3((unsigned)num_cu), dim3(512), lds, s, p);
     } else {
         p.ws = nullptr; p.wsflags = nullptr; p.ws_bytes = 0;
-        // two-group ping-pong loop (default) or the rolling single-phase loop (one barrier per chunk, fragment reads spread under the
-        // MFMAs; tune[1] bit 1: A/B measurements -- bit-identical, equal speed: profiles/r04d_wino_roll_vs_pingpong_ab.log; the same stage
-        // on FOUR waves with 64x64 wave tiles and the rolling loop was 1.4x slower, profiles/r04f_wino_4waves_roll_ab.log)
 #ifndef YV3_WINO_ROLL
-#define YV3_WINO_ROLL 0
+#define YV3_WINO_ROLL 0            // (A/B builds: 1 swaps the two loops' roles)
 #endif
-        if (((p.tune[1] >> 1) & 1) != YV3_WINO_ROLL)
+        if ((kernel == YV3_PK_WINO_ROLL) != YV3_WINO_ROLL)
             hipLaunchKernelGGL((conv_planes_kernel<2, BM, BN, 4, 2, NS, false, false, false, false, false, 1, 0, true, true>), grid, dim3(512), lds, s, p);
         else
             hipLaunchKernelGGL((conv_planes_kernel<2, BM, BN, 4, 2, NS, false, false, false, true, false, 1, 0, true>), grid, dim3(512), lds, s, p);
@@ -961,93 +943,24 @@ static int launch_wino(const yv3_conv_desc* d, ConvParamsP p, hipStream_t s) {
 
 extern "C" size_t yv3_conv_workspace_bytes(void) { return (size_t)YV3_SK_MAX_WG * (YV3_SK_PART_BYTES + sizeof(int)); }
 
-static int planes_wino_rule(const yv3_conv_desc* d, int np);
+static_assert(PBK == YV3_SEL_CHUNK, "conv_select.cpp counts K chunks of PBK elements");
 
-// The shape errors yv3_conv2d_planes reports before it launches anything: ONE function, called by the launch path and by the
-// form query, so that yv3_conv2d_form returns exactly "the YV3_E* code yv3_conv2d would return" (include/yv3.h).
-static int planes_shape_rc(const yv3_conv_desc* d) {
-    if (d->dec_out && (d->out_dtype != YV3_F32 || d->cout % 3 || d->dec_stride <= 0.f)) return YV3_ESHAPE;
-    const int pad = (d->k - 1) / 2;
-    const long long Ho = (d->H + 2 * pad - d->k) / d->stride + 1, Wo = (d->W + 2 * pad - d->k) / d->stride + 1;
-    if ((long long)d->B * Ho * Wo > 0x7fffffffLL) return YV3_ESHAPE;
-    if (d->out_dtype != YV3_F32 && (d->cout % 8)) return YV3_ESHAPE;
-    const int npad = d->cout_pad, tb = npad < 128 ? npad : 128;
-    if (tb <= 0 || npad % tb) return YV3_ESHAPE;
-    if (d->out_dtype == YV3_F32 && (d->k == 3 || d->cin_up > 0)) return YV3_ESHAPE;      // fp32 outputs are the 1x1 head convs
-    return 0;
-}
-
-// Does the opt-in kw-tap-reuse kernel (YV3_OPT_K3S1, conv_planes_k3s1.hip) take this launch?  It is dispatched BEFORE the Winograd rule.
-static bool k3s1_takes(const yv3_conv_desc* d) {
-    return d->k == 3 && d->stride == 1 && d->out_dtype != YV3_F32 && (d->options & YV3_OPT_K3S1) && d->cin % PBK == 0 &&
-           (d->cout_pad % 128 == 0 || d->cout_pad % 64 == 0);
-}
-
-// Which form does this descriptor take?  (The per-launch rule of the fp16-plane mode; also exported through yv3_conv2d_form so
-// that callers -- tests, bench.py's executed-FLOP accounting -- see the choice the library makes.)  Mirrors yv3_conv2d_planes'
-// dispatch order: shape errors, the opt-in k3s1 kernel (direct form), the Winograd rule (+ launch_wino's own errors).
-int yv3_conv2d_planes_form(const yv3_conv_desc* d, int np) {
-    const int src = planes_shape_rc(d);
-    if (src) return src;
-    if (k3s1_takes(d)) return YV3_FORM_DIRECT;
-    const int w = planes_wino_rule(d, np);
-    if (w == 1) {
-        const long long T = (long long)d->B * ((d->H + 1) / 2) * ((d->W + 1) / 2);
-        if (T > 0x7fffffffLL || d->cout_pad % 128 || d->cin % 32) return YV3_ESHAPE;
-        if (!d->wino_ws || d->wino_ws_bytes < (size_t)2 * 16 * T * d->cin * sizeof(u16)) return YV3_EWORKSPACE;
-    }
-    return w;
-}
-
-static int planes_wino_rule(const yv3_conv_desc* d, int np) {
-    const int npad = d->cout_pad;
-    const bool k3 = d->k == 3, dual = d->cin_up > 0, out_f32 = d->out_dtype == YV3_F32;
-    if (!(d->w_wino && np == 2 && k3 && d->stride == 1 && !out_f32 && !dual && d->alpha_wino && npad % 128 == 0 &&
-          d->x_plane_stride <= 0 && d->y_plane_stride <= 0)) return 0;
-    // Winograd F(2x2,3x3) when its 128x128 tiles (a quarter of the direct kernel's row count) fill 0.55 ... 1.05 rounds of
-    // the chip: same-box A/B against the direct kernel (tools/wino_ab.py): 256->512 @26x26 bs=32 (172 tiles) x1.28,
-    // 512->1024 @13x13 bs=64 (200) x1.36, 256->512 @38x38 bs=16 (184) x1.26; but 340 tiles (1.33 rounds: @26x26 bs=64) x0.96,
-    // 104 tiles (@13x13 bs=32, @19x19 bs=16) x0.78...0.80, and the 128-channel 52x52 layers x0.93 (input transform HBM-bound)
-    const long long tiles = (((long long)d->B * ((d->H + 1) / 2) * ((d->W + 1) / 2) + 127) / 128) * (npad / 128);
-    const long long ncu = yv3_num_cu();
-    // Round 3, later (tools/wino_ab.py over bs = 48 ... 256, profiles/r03x_wino_rounds_map.log): what decides is how full the LAST
-    // round of tiles is.  r = tiles / CUs: 0.59 x0.89, 0.78 x1.38, 0.97 x1.27, 1.00 x1.15 | 1.16 x0.85, 1.33 x0.94, 1.53 x1.06, 1.66 x1.16,
-    // 1.94 x1.29, 2.31 x1.01, 2.64 x1.14, 3.06 x1.07, 3.97 x1.13, 5.28 x1.09.  Rule for a launch that has the chip to itself:
-    // up to one round r >= 0.62; beyond, r / ceil(r) >= 0.75.  Under two concurrent lanes (YV3_OPT_TWO_LANES) the other lane's
-    // launch fills the idle part of a round: r >= 0.27 (the 13x13 layers at 32 images per lane, 104 tiles, run x0.78 alone but the
-    // two-lane step gains 2.6-3.8 % with them; at 64 / 128 images per lane the 1.33-round 26x26 layers gain too: bs=128 +2.9 %, bs=256
-    // +5.5 %, profiles/r03y_wino_two_lanes_rule_ab.txt, r03x_wino_big_batch.txt)
-    if (d->options & YV3_OPT_WINO_ALWAYS) return 1;
-#ifndef YV3_AB_NO_TWO_LANES_RULE
-    if (d->options & YV3_OPT_TWO_LANES) return tiles * 100 >= 27 * ncu;
-#endif
-    if (tiles * 100 <= 105 * ncu) return tiles * 100 >= 62 * ncu;
-    return tiles * 100 >= 75 * ((tiles + ncu - 1) / ncu) * ncu;
-}
-
-int yv3_conv2d_planes(const yv3_conv_desc* d, int np, hipStream_t s) {
-    const int src = planes_shape_rc(d);
-    if (src) return src;
+// Launches what the selector chose (conv_select.cpp: yv3_select_planes) for a descriptor that passed its checks.
+int yv3_conv2d_planes(const yv3_conv_desc* d, int np, const yv3_planes_choice& c, int ncu, hipStream_t s) {
     ConvParamsP p;
     p.x = (const u16*)d->x; p.x2 = (const u16*)d->x2; p.w = (const u16*)d->w;
     p.alpha = d->alpha; p.beta = d->beta; p.res = (const u16*)d->residual; p.y = d->y;
     p.H = d->H; p.W = d->W; p.Cin = d->cin; p.Cup = d->cin_up; p.Cout = d->cout;
     p.stride = d->stride; p.act = d->act; p.flags = d->flags;
-    for (int i = 0; i < 4; ++i) p.tune[i] = d->tune[i];
+    for (int i = 0; i < 4; ++i) p.tune[i] = d->tune[i];            // (the measurement builds' hooks inside the kernels)
     p.dec_out = nullptr;
     if (d->dec_out) {
-        if (d->out_dtype != YV3_F32 || d->cout % 3 || d->dec_stride <= 0.f) return YV3_ESHAPE;
         p.dec_out = d->dec_out; p.dec_bs = d->dec_out_batch_stride; p.dec_stride = d->dec_stride;
         for (int i = 0; i < 6; ++i) p.dec_an[i] = d->dec_anchors[i] / d->dec_stride;     // float32 division, as torch does
     }
     p.ws = (float*)d->workspace; p.ws_bytes = d->workspace ? d->workspace_bytes : 0;
     p.wsflags = d->workspace ? (int*)((char*)d->workspace + (size_t)YV3_SK_MAX_WG * YV3_SK_PART_BYTES) : nullptr;
-    const int pad = (d->k - 1) / 2;
-    p.Ho = (d->H + 2 * pad - d->k) / d->stride + 1;
-    p.Wo = (d->W + 2 * pad - d->k) / d->stride + 1;
-    const long long M = (long long)d->B * p.Ho * p.Wo;
-    if (M > 0x7fffffffLL) return YV3_ESHAPE;
-    p.M = (int)M;
+    p.Ho = c.Ho; p.Wo = c.Wo; p.M = c.M;
     p.K = d->k * d->k * d->cin;
     p.nk = p.K / PBK;
     if (d->cin_up) {
@@ -1057,155 +970,39 @@ int yv3_conv2d_planes(const yv3_conv_desc* d, int np, hipStream_t s) {
         p.xs = (long long)d->B * d->H * d->W * d->cin;
         p.x2s = 0;
     }
-    p.ys = M * d->cout;
+    p.ys = (long long)c.M * d->cout;
     if (d->x_plane_stride > 0) p.xs = d->x_plane_stride;            // batch slices of larger plane tensors
     if (d->x2_plane_stride > 0) p.x2s = d->x2_plane_stride;
     if (d->y_plane_stride > 0) p.ys = d->y_plane_stride;
-    const bool out_f32 = d->out_dtype == YV3_F32;
-    if (!out_f32 && (d->cout % 8)) return YV3_ESHAPE;
-    const int npad = d->cout_pad;
-    p.tb = npad < 128 ? npad : 128;
-    if (npad % p.tb) return YV3_ESHAPE;
-    const bool k3 = d->k == 3, dual = d->cin_up > 0;
-    // kw-tap reuse kernel (conv_planes_k3s1.hip): 44 % less L2->LDS traffic, same results, but no faster on
-    // MI355X because this MFMA stream is power-limited -- opt-in until that changes.
-    if (k3s1_takes(d)) {
-        const int rc = yv3_conv2d_planes_k3s1(&p, np, npad, M, s);
-        if (rc != -100) return rc;
+    p.tb = d->cout_pad < 128 ? d->cout_pad : 128;
+    p.ntiles = c.ntiles;
+    const bool k3 = d->k == 3, dual = d->cin_up > 0, out_f32 = d->out_dtype == YV3_F32;
+    const bool use_pp = c.pingpong;
+#define YV3_CFG(BM_, BN_, WM_, WN_, NS_) (np == 3 ? launch_cfg<3, BM_, BN_, WM_, WN_, NS_>(p, k3, dual, out_f32, use_pp, ncu, s) : \
+                                         np == 2 ? launch_cfg<2, BM_, BN_, WM_, WN_, (NS_) + 1>(p, k3, dual, out_f32, use_pp, ncu, s) : \
+                                                   launch_cfg<1, BM_, BN_, WM_, WN_, NS_>(p, k3, dual, out_f32, false, ncu, s))
+    switch (c.kernel) {
+        case YV3_PK_K3S1_256x128: case YV3_PK_K3S1_128x128: case YV3_PK_K3S1_128x64: return yv3_conv2d_planes_k3s1(p, np, c.kernel, s);
+        case YV3_PK_WINO_PINGPONG: case YV3_PK_WINO_ROLL: case YV3_PK_WINO_EVEN: return launch_wino(d, p, c.kernel, ncu, s);
+        case YV3_PK_W4_192x128:     return yv3_conv2d_planes_w4(p, s);
+        case YV3_PK_256x128_W8:     return YV3_CFG(256, 128, 4, 2, 2);
+        case YV3_PK_128x128_W8:     return YV3_CFG(128, 128, 4, 2, 3);
+        case YV3_PK_128x128_W4:     return np == 2 ? launch_cfg<2, 128, 128, 2, 2, 2, 2>(p, k3, dual, out_f32, false, ncu, s)
+                                                   : launch_cfg<1, 128, 128, 2, 2, 2, 2>(p, k3, dual, out_f32, false, ncu, s);
+        case YV3_PK_128x64:         return np == 2 ? launch_cfg<2, 128, 64, 2, 2, 2>(p, k3, dual, out_f32, false, ncu, s) : YV3_CFG(128, 64, 2, 2, 2);
+        case YV3_PK_128x32:         return np == 2 ? launch_cfg<2, 128, 32, 4, 1, 2>(p, k3, dual, out_f32, false, ncu, s) : YV3_CFG(128, 32, 4, 1, 2);
+        case YV3_PK_256x128_W8_PP6: return launch_cfg<1, 256, 128, 4, 2, 6>(p, k3, dual, out_f32, true, ncu, s);
+        case YV3_PK_256x128_W4:     return launch_cfg<1, 256, 128, 2, 2, 3, 2, 2>(p, k3, dual, out_f32, false, ncu, s);
+        case YV3_PK_256x128_W4_ROLL: return launch_cfg<1, 256, 128, 2, 2, 3, 2, 2, true>(p, k3, dual, out_f32, false, ncu, s);
+        case YV3_PK_256x256:        return launch_cfg<1, 256, 256, 2, 4, 3, 1, 1>(p, k3, dual, out_f32, false, ncu, s);
+        case YV3_PK_256x256_ROLL:   return launch_cfg<1, 256, 256, 2, 4, 3, 1, 1, true>(p, k3, dual, out_f32, false, ncu, s);
+        case YV3_PK_256x256_ROLL4:  return launch_cfg<1, 256, 256, 2, 4, 4, 1, 1, true>(p, k3, dual, out_f32, false, ncu, s);
+        case YV3_PK_256x256_PP3:    return launch_cfg<1, 256, 256, 2, 4, 3, 1, 1>(p, k3, dual, out_f32, true, ncu, s);
+        case YV3_PK_256x256_PP4:    return launch_cfg<1, 256, 256, 2, 4, 4, 1, 1>(p, k3, dual, out_f32, true, ncu, s);
+        case YV3_PK_192x256_ROLL:   return launch_cfg<1, 192, 256, 2, 4, 3, 1, 1, true>(p, k3, dual, out_f32, false, ncu, s);
+        case YV3_PK_192x256_PP3:    return launch_cfg<1, 192, 256, 2, 4, 3, 1, 1>(p, k3, dual, out_f32, true, ncu, s);
+        case YV3_PK_192x256_PP4:    return launch_cfg<1, 192, 256, 2, 4, 4, 1, 1>(p, k3, dual, out_f32, true, ncu, s);
     }
-    if (planes_wino_rule(d, np) == 1) return launch_wino(d, p, s);
-    const bool use_pp = !(d->options & YV3_OPT_NO_PINGPONG);       // ping-pong main loop (fp16x2, 8-wave tiles) unless disabled
-#define YV3_CFG(BM_, BN_, WM_, WN_, NS_) (np == 3 ? launch_cfg<3, BM_, BN_, WM_, WN_, NS_>(p, k3, dual, out_f32, use_pp, s) : \
-                                         np == 2 ? launch_cfg<2, BM_, BN_, WM_, WN_, (NS_) + 1>(p, k3, dual, out_f32, use_pp, s) : \
-                                                   launch_cfg<1, BM_, BN_, WM_, WN_, NS_>(p, k3, dual, out_f32, false, s))
-    if (npad % 128 == 0) {
-        // 256x128 tiles (8 waves, 144 KB LDS; 64x64 per wave) from half a round of tiles upwards, else 128x128 tiles
-        // (8 waves of 32x64).  Measured at bs=64: the 13x13 layers have 172 / 344 big tiles (0.7 / 1.3 rounds) and are
-        // still 5 % (3x3) to 26 % (1x1) faster than with 340 / 680 small ones -- the big tile does 1/3 less LDS
-        // traffic per MFMA, and a partly filled round simply clocks higher on this power-limited kernel.
-        const long long blocks256 = ((M + 255) / 256) * (npad / 128);
-        p.ntiles = npad / 128;
-        // (with the stream-K schedule every CU gets the same share whatever the tile count: one tile per CU suffices)
-        const bool sk_ok = np == 2 && p.ws && use_pp;
-        const int big_min = d->big_tile_min > 0 ? d->big_tile_min : 128;
-        const int force = (int)((d->options >> YV3_OPT_TILE_SHIFT) & 0xffu);
-        // (code 12: the four-wave 256x128 tile with 16-deep chunks, two workgroups per CU -- conv_planes_w4.hip)
-        if (np == 2 && force == 12 && !out_f32 && !dual) {
-            const int rc = yv3_conv2d_planes_w4(&p, np, npad, s);
-            if (rc != -100) return rc;
-        }
-        if (np == 2 && force == 3) return launch_cfg<2, 128, 128, 2, 2, 2, 2>(p, k3, dual, out_f32, false, s);
-        if (np == 1 && force == 3) return launch_cfg<1, 128, 128, 2, 2, 2, 2>(p, k3, dual, out_f32, false, s);
-        // 256x128 tile on FOUR waves (128x64 wave tiles: 6 fragment reads per 8 MFMAs instead of 4 per 4), two workgroups per CU
-        if (np == 1 && force == 5) return launch_cfg<1, 256, 128, 2, 2, 3, 2, 2>(p, k3, dual, out_f32, false, s);
-        // 256x256 tile on eight waves (128x64 wave tiles), one workgroup per CU, single-phase loop
-        if (np == 1 && force == 6 && npad % 256 == 0 && !out_f32) { p.ntiles = npad / 256; return launch_cfg<1, 256, 256, 2, 4, 3, 1, 1>(p, k3, dual, out_f32, false, s); }
-        // (code 8: the 256x256 tile with the rolling loop; code 9: 4-deep ring)
-        if (np == 1 && force == 8 && npad % 256 == 0 && !out_f32) { p.ntiles = npad / 256; return launch_cfg<1, 256, 256, 2, 4, 3, 1, 1, true>(p, k3, dual, out_f32, false, s); }
-        if (np == 1 && force == 9 && npad % 256 == 0 && !out_f32) { p.ntiles = npad / 256; return launch_cfg<1, 256, 256, 2, 4, 4, 1, 1, true>(p, k3, dual, out_f32, false, s); }
-        // (code 11: the 192-row variant of the 256x256 rolling tile -- 96x64 wave tiles; also measured and dropped: 192x128 on four waves
-        // and 128x256 on eight, profiles/r04aa_bf16_192row_tiles_ab.log)
-        // (codes 13 / 14: the 256x256 tile with the eight-wave PING-PONG loop, 128x64 wave tiles, 3- / 4-deep ring; 14 is what the rule below ships)
-        if (np == 1 && force == 13 && npad % 256 == 0 && !out_f32) { p.ntiles = npad / 256; return launch_cfg<1, 256, 256, 2, 4, 3, 1, 1>(p, k3, dual, out_f32, true, s); }
-        if (np == 1 && force == 14 && npad % 256 == 0 && !out_f32) { p.ntiles = npad / 256; return launch_cfg<1, 256, 256, 2, 4, 4, 1, 1>(p, k3, dual, out_f32, true, s); }
-        // (code 15: the 192-row variant with the ping-pong loop)
-        if (np == 1 && force == 15 && npad % 256 == 0 && !out_f32) { p.ntiles = npad / 256; return launch_cfg<1, 192, 256, 2, 4, 3, 1, 1>(p, k3, dual, out_f32, true, s); }
-        // (code 16: ... with a 4-deep ring: one more chunk of prefetch lead)
-        if (np == 1 && force == 16 && npad % 256 == 0 && !out_f32) { p.ntiles = npad / 256; return launch_cfg<1, 192, 256, 2, 4, 4, 1, 1>(p, k3, dual, out_f32, true, s); }
-        if (np == 1 && force == 11 && npad % 256 == 0 && !out_f32) { p.ntiles = npad / 256; return launch_cfg<1, 192, 256, 2, 4, 3, 1, 1, true>(p, k3, dual, out_f32, false, s); }
-        if (np == 2 && force == 4) { p.ntiles = npad / 64; return launch_cfg<2, 128, 64, 2, 2, 2>(p, k3, dual, out_f32, false, s); }
-        // Round 5: the four-wave 192x128 tile, TWO workgroups per CU (conv_planes_w4.hip): one workgroup's prologue / epilogue / launch gap
-        // under the other's main loop; bit-identical to the eight-wave tile (same K order).  Same-box A/B, bs=64 (profiles/r05e_w4_192x128_ab.txt):
-        // 128->256 @52 +4 %, 64->128 @104 +5 %, 512->256 1x1 @26 +12 %, 256->128 1x1 @52 +6 %, 512->1024 s2 @13 +11 %; at bs=32 256->512 @26
-        // +16 %, 512->1024 @13 +9 % (192-row tiles fill the chip's last round better); 256->512 @26 bs=64 -3 %, long K (512->256 3x3 @52) -5 %.
-        // (tune[1] bit 5: off, bit 6: off for 1x1 layers, bit 7: off for 3x3 layers -- A/B measurements)
-        // End to end (profiles/r05h_w4_end_to_end_ab_other_batches.txt, r05j_*): 416x416 bs=16 +7.7 %, bs=32 +3.8 %, bs=8 +2.3 %, 608x608 bs=16 +4 %,
-        // dense 608x608 bs=8 +3.4 %, bs=64 on one lane +0.8 % (the chip is power-limited there: 16 % more tile rows per CU-cycle by the kernel's own
-        // timeline, profiles/r05f_w4_timeline.txt, buy 4 % in isolation and ~1 % in the network).  Under TWO concurrent lanes the 3x3 layers lose
-        // with it (bs=64: -1.2 %; three alternating passes) while the 1x1 layers still gain (+0.2 %): there only the 1x1 layers take it.
-        const bool w4_lanes_ok = !(d->options & YV3_OPT_TWO_LANES) || !k3 || (p.tune[1] & 256);
-        if (np == 2 && force == 0 && !out_f32 && !dual && !(p.tune[1] & 32) && (k3 || p.nk >= 8) && !(p.tune[1] & (k3 ? 128 : 64)) && w4_lanes_ok) {
-            const long long t192 = ((M + 191) / 192) * (npad / 128);
-            // from three quarters of a workgroup per CU upwards (512->1024 @19x19 bs=8: 128 tiles on 256 CUs, one four-wave workgroup on
-            // every other CU, 219 instead of 292 TFLOP/s; 232 tiles @13x13 bs=32: +5 %; profiles/r05i_w4_layers_*.txt)
-            if (t192 * 4 >= 3 * yv3_num_cu()) {
-                const int rc = yv3_conv2d_planes_w4(&p, np, npad, s);
-                if (rc != -100) return rc;
-            }
-        }
-        // short-K 1x1 layers (K <= 512: 8-16 chunks per tile, mostly prologue / epilogue): two independent 4-wave workgroups
-        // per CU (128x128 tiles, 2-deep ring) hide each other's IO -- in the network at bs=64 the step gains 0.8 %
-        // (13.31 -> 13.20 ms, same box, alternating; K = 1024 does not gain); same K order, same bits
-        // (the head convs at 52x52 / 26x26 included: +0.2...0.7 %; the 104x104 3x3 layers, K = 576, lose 1 % on it)
-        if (np == 2 && !k3 && p.nk <= 16 && force == 0 && blocks256 >= big_min && !(p.tune[1] & 1))
-            return launch_cfg<2, 128, 128, 2, 2, 2, 2>(p, k3, dual, out_f32, false, s);
-        if (force == 1) return YV3_CFG(256, 128, 4, 2, 2);
-        if (force == 2) return YV3_CFG(128, 128, 4, 2, 3);
-        // one bf16 plane (YV3_BF16): the same ping-pong loop with one MFMA per unit -- 608x608 bs=16: 2727 -> 3155
-        // images/s on one lane (two 4-wave workgroups per CU instead: 2953)
-        // (6-deep ring, 147 KB: with 8 MFMAs per chunk and wave a DMA piece needs several chunk times to land; 3-deep 3690, 4-deep
-        // 3830, 6-deep 3870 images/s at 608x608 bs=16)
-        // ... and from one tile per CU upwards the same 256x128 tile on FOUR waves (128x64 wave tiles: 6 fragment reads per 8 MFMAs
-        // instead of 4 per 4, half the DMA pieces per MFMA and wave), two independent workgroups per CU (72 KB of LDS each, <= 256
-        // registers), single-phase loop, epilogue in two rounds of 64 rows: same K order, bit-identical.  Same-box A/B
-        // (tools/tile_ab.py, profiles/r03_bf16_tile_ab*.log), 608x608 bs=16: 128->256 @76 665 -> 772 TFLOP/s, 256->512 @38 670 -> 811,
-        // 64->128 @152 559 -> 691, the stride-2 layers +11...18 %, 256->128 1x1 @76 +12 %; 416x416 bs=64: @52 663 -> 831, @26 825 -> 901,
-        // @13 702 -> 846.  Below one tile per CU (512->1024 @19 at bs=16: 184 tiles, 1x1 layers at 38 / 19) the 8-wave ping-pong
-        // tile wins by 7...30 % (twice the waves per tile).  A 256x256 / 8-wave tile (code 6) loses to both at these sizes.
-        // (tune[2] > 0: threshold override for A/B measurements)
-        // (code 7: the same tile with the rolling loop -- barrier between the k-steps, next chunk's first fragments read under the MFMAs)
-        if (np == 1 && force == 7) return launch_cfg<1, 256, 128, 2, 2, 3, 2, 2, true>(p, k3, dual, out_f32, false, s);
-        // Round 4 (tools/tile_ab.py, profiles/r04d_bf16_roll_ab.log, r04j_bf16_tiles_ab.log): the 3x3 layers take the ROLLING loop on that
-        // tile (+2...6 %; the 1x1 layers lose 1-3 % on it and keep the plain loop) -- and a 256x256 tile on eight waves (128x64 wave tiles,
-        // one workgroup per CU, rolling loop: 32 KB of DMA per 128 MFMAs instead of 24 KB per 64 -- the L2 -> LDS path delivers 62 B/clk/CU,
-        // tools/probes/dma_rate.hip, and was the 256x128 tile's co-bottleneck) when its tile count fills the chip's last round:
-        // 676 tiles (128->256 @52x52 bs=64) +8 %, 172 (512->1024 @13x13 bs=64) +15 %, 182 (256->512 @38x38 bs=16) +14 %; but 338
-        // (1.32 rounds) -7 %, 361 -6 %, 92 -28 %.  Rule: r = tiles / CUs; r >= 0.6 up to one round, r / ceil(r) >= 0.8 beyond.
-        if (np == 1 && force == 0 && k3 && !out_f32 && npad % 256 == 0 && !(p.tune[1] & 8)) {
-            const long long t256 = ((M + 255) / 256) * (npad / 256);
-            const long long ncu = yv3_num_cu();
-            const bool fill = t256 <= ncu ? t256 * 10 >= 6 * ncu : t256 * 10 >= 8 * ((t256 + ncu - 1) / ncu) * ncu;
-            // ... and its 192-row variant (96x64 wave tiles; a wave stages 24 pixel rows = one DMA piece and a half) where that fills the
-            // last round to >= 85 % and 256 rows leave it below 80 %: 256->512 @38x38 bs=16 (182 -> 242 tiles) +6 %, 512->1024 @13x13 bs=64
-            // (172 -> 228) +5 %, 128->256 @76x76 bs=16 (361 -> 482) +2.6 %, @76x76 bs=8 +9 % (profiles/r04aa_bf16_192row_tiles_ab.log)
-            const long long t192 = ((M + 191) / 192) * (npad / 256);
-            const long long r256 = (t256 + ncu - 1) / ncu * ncu, r192 = (t192 + ncu - 1) / ncu * ncu;
-            // Round 5: both tiles run the eight-wave PING-PONG loop on a 4-deep ring instead of the rolling loop (tune[1] bit 9: the rolling loop,
-            // bit 10: ping-pong on the 3-deep ring -- A/B).  The rolling tile's eight waves leave their one barrier together, their fragment
-            // reads (96 KB per chunk and CU) queue behind each other and ~350 of a chunk's 1500 cycles are exposed LDS latency
-            // (tools/timeline.py --kernel roll_bf16, profiles/r05x_bf16_roll_timeline.txt); with one four-wave group reading while the other issues
-            // MFMAs the layers run bit-identical and +5...+14 % faster in isolation, on uniform random operands and on the network's own
-            // activations alike (profiles/r05y_bf16_pingpong_*_ab.txt, r05ad_*).  IN the network the 3-deep ring LOSES 2 % (its DMA lead is one
-            // compute segment, ~1000 cycles: fine for L2-hot repeats of one layer, too short for a layer's first touch of its weights and
-            // inputs); the 4-deep ring gains: conv kernel time 608x608 bs=16 3.17 -> 3.08 ms, 416x416 bs=64 5.21 -> 5.04 ms, step +2 %
-            // (profiles/r05ae_*, r05af_*; a per-layer A/B decides nothing by itself).
-            const bool roll = (p.tune[1] & 512) != 0, pp3 = (p.tune[1] & 1024) != 0;
-            if (!(p.tune[1] & 16) && t192 * 100 >= 85 * r192 && t256 * 100 < 80 * r256) {
-                p.ntiles = npad / 256;
-                if (roll) return launch_cfg<1, 192, 256, 2, 4, 3, 1, 1, true>(p, k3, dual, out_f32, false, s);
-                return pp3 ? launch_cfg<1, 192, 256, 2, 4, 3, 1, 1>(p, k3, dual, out_f32, true, s) : launch_cfg<1, 192, 256, 2, 4, 4, 1, 1>(p, k3, dual, out_f32, true, s);
-            }
-            if (fill) {
-                p.ntiles = npad / 256;
-                if (roll) return launch_cfg<1, 256, 256, 2, 4, 3, 1, 1, true>(p, k3, dual, out_f32, false, s);
-                return pp3 ? launch_cfg<1, 256, 256, 2, 4, 3, 1, 1>(p, k3, dual, out_f32, true, s) : launch_cfg<1, 256, 256, 2, 4, 4, 1, 1>(p, k3, dual, out_f32, true, s);
-            }
-        }
-        if (np == 1 && force == 0 && k3 && blocks256 >= (p.tune[2] > 0 ? p.tune[2] : 256) && !out_f32 && !(p.tune[1] & 8))
-            return launch_cfg<1, 256, 128, 2, 2, 3, 2, 2, true>(p, k3, dual, out_f32, false, s);
-        if (np == 1 && force == 0 && blocks256 >= (p.tune[2] > 0 ? p.tune[2] : 256) && !out_f32) return launch_cfg<1, 256, 128, 2, 2, 3, 2, 2>(p, k3, dual, out_f32, false, s);
-        if (np == 1 && use_pp && force == 0 && blocks256 >= big_min) return launch_cfg<1, 256, 128, 4, 2, 6>(p, k3, dual, out_f32, true, s);
-        if (blocks256 >= (sk_ok ? 256 : big_min)) return YV3_CFG(256, 128, 4, 2, 2);
-        return YV3_CFG(128, 128, 4, 2, 3);
-    }
-    if (npad % 64 == 0) {
-        p.ntiles = npad / 64;
-        // fp16 planes: 2-deep ring (49 KB) -> three workgroups per CU instead of two (+4 % on the 208x208 3x3 layer)
-        if (np == 2) return launch_cfg<2, 128, 64, 2, 2, 2>(p, k3, dual, out_f32, false, s);
-        return YV3_CFG(128, 64, 2, 2, 2);
-    }
-    p.ntiles = npad / 32;
-    if (np == 2) return launch_cfg<2, 128, 32, 4, 1, 2>(p, k3, dual, out_f32, false, s);     // (+6 % on the 208x208 1x1 layer)
-    return YV3_CFG(128, 32, 4, 1, 2);
 #undef YV3_CFG
+    return YV3_EINVAL;
 }

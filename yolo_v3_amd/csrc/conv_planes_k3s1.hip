@@ -238,19 +238,14 @@ int launch_k3s1(const ConvParamsP& p, hipStream_t s) {
 
 }  // namespace
 
-// Called by yv3_conv2d_planes for k=3, stride=1, no dual source, plane output.  Returns -100 when the shape is
-// not covered (the caller then uses the generic kernel).
-int yv3_conv2d_planes_k3s1(const ConvParamsP* pp, int np, int npad, long long M, hipStream_t s) {
-    ConvParamsP p = *pp;
-    if (p.Cin % PBK) return -100;
+// k = 3, stride 1, no dual source, plane output (conv_select.cpp); p = yv3_conv2d_planes' parameters
+int yv3_conv2d_planes_k3s1(const ConvParamsP& p, int np, yv3_planes_kernel kernel, hipStream_t s) {
 #define YV3_K3(BM_, BN_, WM_, WN_) (np == 3 ? launch_k3s1<3, BM_, BN_, WM_, WN_>(p, s) : np == 2 ? launch_k3s1<2, BM_, BN_, WM_, WN_>(p, s) : launch_k3s1<1, BM_, BN_, WM_, WN_>(p, s))
-    if (npad % 128 == 0) {
-        const long long blocks256 = ((M + 255) / 256) * (npad / 128);
-        p.ntiles = npad / 128;
-        if (blocks256 >= 512) return YV3_K3(256, 128, 4, 2);
-        return YV3_K3(128, 128, 4, 2);
+    switch (kernel) {
+        case YV3_PK_K3S1_256x128: return YV3_K3(256, 128, 4, 2);
+        case YV3_PK_K3S1_128x128: return YV3_K3(128, 128, 4, 2);
+        case YV3_PK_K3S1_128x64:  return YV3_K3(128, 64, 2, 2);
+        default: return YV3_EINVAL;
     }
-    if (npad % 64 == 0) { p.ntiles = npad / 64; return YV3_K3(128, 64, 2, 2); }
-    return -100;
 #undef YV3_K3
 }

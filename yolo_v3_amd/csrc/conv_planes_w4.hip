@@ -252,16 +252,12 @@ __global__ __launch_bounds__(256, 2) void conv_planes_w4_kernel(const ConvParams
 
 }  // namespace
 
-// 0: launched; -100: shape not taken (the caller falls through to conv_planes_kernel)
-int yv3_conv2d_planes_w4(const ConvParamsP* pp, int np, int npad, hipStream_t s) {
-    ConvParamsP p = *pp;
-    if (np != 2 || npad % 128 || p.Cin % PBK || p.Cup > 0 || p.dec_out || p.K % PBK) return -100;
+static_assert(W4_BM == YV3_SEL_W4_BM && W4_BN == YV3_SEL_W4_BN, "conv_select.cpp counts this kernel's tiles");
+
+// fp16 planes, plane output, no dual source, at least two K chunks (conv_select.cpp); p = yv3_conv2d_planes' parameters
+int yv3_conv2d_planes_w4(const ConvParamsP& p_, hipStream_t s) {
+    ConvParamsP p = p_;
     const bool k3 = p.K == 9 * p.Cin;
-    if (!k3 && p.K != p.Cin) return -100;
-    p.ntiles = npad / 128;
-    p.tb = 128;
-    p.nk = p.K / PBK;
-    if (p.nk < 2) return -100;
     const dim3 grid((unsigned)(((p.M + W4_BM - 1) / W4_BM) * p.ntiles));
     p.total = (int)grid.x;
     constexpr int MTG = 1;

@@ -546,73 +546,19 @@ extern "C" int yv3_pack_wino4_weight_f32(const float* u_oc66, float* packed, int
     return 0;
 }
 
-// bytes of yv3_conv_desc.wino_ws for a B x H x W x cin input: V + the hand-over area of the even schedule (parts + flags: the LAST
-// yv3_wino_sk_bytes() bytes of whatever buffer the caller passes, rounded down to 256 -- zero-filled once by the caller, like the
-// F(2x2) stage's)
-static size_t wino4_v_bytes(int B, int H, int W, int cin) { return (size_t)36 * B * ((H + 3) / 4) * ((W + 3) / 4) * cin * sizeof(float); }
+static_assert(BMT == YV3_SEL_WINO4_TILES && BNC == YV3_SEL_WINO4_CHANNELS && W4F_MAX_TAIL_WG == YV3_SEL_WINO4_MAX_TAIL_WG && ROWB == 4 * YV3_SEL_CHUNK,
+              "conv_select.cpp counts this kernel's items, tail workgroups and chunks");
+
 extern "C" size_t yv3_wino4_workspace_bytes(int B, int H, int W, int cin) {
     if (B <= 0 || H <= 0 || W <= 0 || cin <= 0) return 0;
-    return ((wino4_v_bytes(B, H, W, cin) + 255) & ~(size_t)255) + yv3_wino_sk_bytes();
+    return yv3_wino4_ws_bytes(B, H, W, cin);
 }
 
-// workgroups' worth of work of the GEMM stage = its items (the launch rule in conv_igemm_f32.hip counts them)
-long long yv3_wino4_f32_workgroups(const yv3_conv_desc* d) {
-    const long long T = (long long)d->B * ((d->H + 3) / 4) * ((d->W + 3) / 4);
-    return ((T + BMT - 1) / BMT) * (d->cout / BNC);
-}
-
-// The even schedule of a launch: n_full whole-item workgroups + the other items cut into `parts` ranges of 6 / parts patch rows (parts = 1:
-// one item per workgroup throughout).  Measured (tools/wino4_even_ab.py, profiles/r06w_wino4_even_parts_calibration.txt): cutting pays when
-// it puts otherwise idle CUs to work -- a tail of few items behind full rounds (520 items: 512 + 8 x 6: 0.259 -> 0.209 ms), small batches
-// (512->1024 @13x13, one image: 16 items, 0.173 -> 0.062 ms, where the direct kernel takes 0.111) -- and not when the tail already
-// covers most CUs once (784 items: 272 x 3 parts 0.355 against 0.360 ms; 1352 items of 128 channels: slower): lone workgroups run their
-// rows 2x faster than two per CU, and every part pays its ring fill, hand-over and flag.  The rule is that model, in chunk times:
-//   rows per part x chunks per row x (1 while the parts leave one workgroup per CU, 2 up to two, 2 x rounds beyond) + 29 + 5 parts
-// against the uncut tail; behind full rounds only cuts that stay at one workgroup per CU.  The smallest wins (checked against all 23
-// measured shapes).  Not under YV3_OPT_WINO4_TILES (callers that share the GPU with other work, net.stream_k = False: a range with
-// row 0 waits for its partners).  tune[1]: 1 never, 2 no full rounds (every item cut: measurements); tune[2]: parts forced.
-static long long wino4_tail_cost(long long tail, int P, int nkx, int ncu, bool lone_only) {
-    const long long W = tail * P;
-    if (P > 1 && (8 * ((tail + 7) / 8) * P > W4F_MAX_TAIL_WG || (lone_only && W > ncu))) return -1;
-    const long long f = W <= ncu ? 1 : W <= 2 * ncu ? 2 : 2 * ((W + 2 * ncu - 1) / (2 * ncu));
-    return (6 / P) * nkx * f + (P > 1 ? 29 + 5 * P : 0);
-}
-static void wino4_schedule(const yv3_conv_desc* d, long long items, int* n_full, int* parts) {
-    const int ncu = yv3_num_cu(), slots = 2 * ncu;
-    *n_full = (int)items; *parts = 1;
-    if ((d->options & YV3_OPT_WINO4_TILES) || d->tune[1] == 1 || items < 1) return;
-    const long long full = d->tune[1] == 2 ? 0 : (items / slots) * slots;
-    const long long tail = items - full;
-    if (tail == 0) return;
-    const int nkx = 6 * (d->cin / 32);
-    int best = 1; long long best_cost = wino4_tail_cost(tail, 1, nkx, ncu, false);
-    for (int P = 2; P <= 6; ++P) {
-        if (6 % P) continue;
-        const long long c = wino4_tail_cost(tail, P, nkx, ncu, full > 0);
-        if (c >= 0 && c < best_cost) { best = P; best_cost = c; }
-    }
-    if ((d->tune[2] == 2 || d->tune[2] == 3 || d->tune[2] == 6) && wino4_tail_cost(tail, d->tune[2], nkx, ncu, false) >= 0) best = d->tune[2];
-    if (best == 1) return;
-    *n_full = (int)full; *parts = best;
-}
-
-// Is the F(4x4) form the fastest one of this launch?  From a number of items on, which depends on the channels (the direct kernel's
-// competitiveness: it has 64 x 64 tiles for small launches) and on whether the even schedule may cut the items: >= 256 input channels:
-// always (one 13x13 image, 16 items: 0.062 ms against the direct kernel's 0.111; 26x26: 0.053 / 0.059); 128: from 0.17 items per CU
-// (44 items: 0.049 / 0.050; 24: 0.048 / 0.032); 64: from 0.39 (86 items: 0.044 / 0.039, 128: 0.044 / 0.048).  One item per workgroup
-// only (YV3_OPT_WINO4_TILES): from 0.3 items per CU, the round-6 crossover (profiles/r06o_wino4_forms_by_batch.txt).
-bool yv3_wino4_f32_pays(const yv3_conv_desc* d) {
-    const long long items = yv3_wino4_f32_workgroups(d), ncu = yv3_num_cu();
-    if ((d->options & YV3_OPT_WINO4_TILES) || d->tune[1] == 1) return items * 10 >= 3 * ncu;
-    return d->cin >= 256 ? true : d->cin == 128 ? items * 100 >= 17 * ncu : items * 100 >= 39 * ncu;
-}
-
-int yv3_conv2d_wino4_f32(const yv3_conv_desc* d, hipStream_t s) {
+// Input transform + the GEMM stage on the schedule the selector chose (conv_select.cpp: c.n_full whole-item workgroups, the other items
+// in c.parts ranges each)
+int yv3_conv2d_wino4_f32(const yv3_conv_desc* d, const yv3_f32_choice& c, hipStream_t s) {
     const int th = (d->H + 3) / 4, tw = (d->W + 3) / 4;
     const long long T = (long long)d->B * th * tw;
-    if (T > 0x7fffffffLL || d->cout % BNC || d->cout_pad != d->cout || (d->cin != 64 && d->cin % 128) || d->k != 3 || d->stride != 1 || d->cin_up) return YV3_ESHAPE;
-    if (!d->w_wino4) return YV3_EINVAL;
-    if (!d->wino_ws || d->wino_ws_bytes < yv3_wino4_workspace_bytes(d->B, d->H, d->W, d->cin)) return YV3_EWORKSPACE;
     float* v = (float*)d->wino_ws;
     {
         const long long n = T * (d->cin >> 2);
@@ -623,16 +569,12 @@ int yv3_conv2d_wino4_f32(const yv3_conv_desc* d, hipStream_t s) {
     p.v = v; p.u = (const float*)d->w_wino4;
     p.alpha = d->alpha; p.beta = d->beta; p.res = (const float*)d->residual; p.y = (float*)d->y;
     p.C = d->cin; p.Cout = d->cout; p.H = d->H; p.W = d->W; p.th = th; p.tw = tw; p.T = (int)T;
-    p.cchunks = d->cin / 32; p.nblk_n = d->cout / BNC; p.act = d->act;
+    p.cchunks = d->cin / 32; p.nblk_n = c.ntiles; p.act = d->act;
     p.pos_stride = T * d->cin;
-    if (!p.alpha) return YV3_EINVAL;
-    const unsigned long long vb = 36ull * T * d->cin * 4, ub = 36ull * d->cout * d->cin * 4;
-    if (vb > 0xffffffffull || ub > 0xffffffffull) return YV3_ESHAPE;        // (32-bit buffer offsets: V of at most 4 GB)
-    p.u_bytes = (unsigned)ub; p.v_bytes = (unsigned)vb;
+    p.u_bytes = (unsigned)(36ull * d->cout * d->cin * 4); p.v_bytes = (unsigned)(36ull * T * d->cin * 4);      // (32-bit buffer offsets: V of at most 4 GB)
     const long long items = ((T + BMT - 1) / BMT) * p.nblk_n;
-    if (items * 6 > 0x7fffffffLL) return YV3_ESHAPE;
     p.nitems = (int)items;
-    wino4_schedule(d, items, &p.n_full, &p.parts);
+    p.n_full = c.n_full; p.parts = c.parts;
     // hand-over area: the last yv3_wino_sk_bytes() of the buffer = 1024 parts of 128 KB; parts 0 .. 1022 are the tail workgroups', the last one
     // holds their flags
     char* area = (char*)d->wino_ws + ((d->wino_ws_bytes - yv3_wino_sk_bytes()) & ~(size_t)255);

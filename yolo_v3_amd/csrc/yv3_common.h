@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "yv3.h"
+#include "conv_select.h"
 
 #define YV3_CHECK_LAUNCH()                                   \
     do {                                                     \
@@ -27,12 +28,10 @@ static inline int yv3_num_cu() {
     return n >= 8 ? n & ~7 : 256;
 }
 
-// Hand-over area of the Winograd stages' even schedules (tail of yv3_conv_desc.wino_ws): YV3_WINO_SK_MAX_WG parts, then as many flags.
-// A part holds one workgroup's partial outputs: four output accumulator sets of a 512-thread workgroup (F(2x2), fp16 planes: 256 KB) or
-// the sixteen outputs of a 256-thread workgroup (F(4x4), exact fp32: 128 KB of it).
-#define YV3_WINO_SK_MAX_WG 512
-#define YV3_WINO_SK_PART_BYTES (512 * 128 * 4)
-static inline size_t yv3_wino_sk_bytes() { return (size_t)YV3_WINO_SK_MAX_WG * (YV3_WINO_SK_PART_BYTES + sizeof(int)) + 256; }
+// The convolution launchers behind yv3_conv2d (capi.hip): each fills its parameter struct from the descriptor and the selector's choice
+// (conv_select.h; the Winograd stages' hand-over area YV3_WINO_SK_* is there too) and returns only launch errors.
+int yv3_conv2d_planes(const yv3_conv_desc* d, int np, const yv3_planes_choice& c, int ncu, hipStream_t s);
+int yv3_conv2d_f32(const yv3_conv_desc* d, const yv3_f32_choice& c, int ncu, hipStream_t s);
 
 // float -> bf16 bits, round to nearest even (NaN kept quiet)
 __host__ __device__ static inline u16 yv3_f2bf(float f) {
