@@ -267,6 +267,13 @@ int yv3_conv2d_form(const yv3_conv_desc* desc);
  * small tiles.  Negative: the YV3_E* code yv3_conv2d would return.  Launches nothing; profiling tools use it to map a kernel trace to layers. */
 int yv3_conv2d_launches(const yv3_conv_desc* desc);
 
+/* Which kernel would yv3_conv2d run for this descriptor on the current device?  Writes one NUL-terminated line of at most 96 bytes into buf:
+ * the kernel instantiation's name and every part of the library's choice that is not a function of the descriptor alone -- channel tiles;
+ * plane modes: main loop, stream-K, persistent grid; YV3_F32: pin, the F(2x2) half tile, the F(4x4) schedule, the persistent GEMM's rows
+ * and grid, the kernel and tiles of the rest.  Returns 0, the YV3_E* code yv3_conv2d would return, or YV3_EINVAL when buf_bytes is too
+ * small.  Launches nothing; tests pin the selection rules with it.  The text is for people and tables, not a stable format. */
+int yv3_conv2d_kernel(const yv3_conv_desc* desc, char* buf, size_t buf_bytes);
+
 /* Run `n` convolutions back to back on `stream` (one host call for a whole network plan). */
 int yv3_conv2d_sequence(const yv3_conv_desc* descs, int n, void* stream);
 

@@ -340,6 +340,13 @@ BF16_RULE_CASES = [
 ]
 
 
+# _bf16_tile_rule's names -> the kernel and the loop yv3_conv2d_kernel names (csrc/conv_select.h: YV3_PK_* without the prefix, yv3_planes_loop)
+BF16_RULE_KERNEL = {"256x256 ping-pong": "256x256_PP4", "192x256 ping-pong": "192x256_PP4", "256x128 four waves, rolling": "256x128_W4_ROLL",
+                    "256x128 four waves, plain": "256x128_W4", "256x128 eight waves, 6-deep": "256x128_W8_PP6", "128x128": "128x128_W8"}
+BF16_RULE_LOOP = {"256x256 ping-pong": "pingpong", "192x256 ping-pong": "pingpong", "256x128 four waves, rolling": "rolling",
+                  "256x128 four waves, plain": "plain", "256x128 eight waves, 6-deep": "pingpong", "128x128": "plain"}
+
+
 @pytest.mark.parametrize("name,tile,kw", BF16_RULE_CASES, ids=[c[0] for c in BF16_RULE_CASES])
 def test_bf16_rule_tiles_vs_fp64_sampled(name, tile, kw):
     """The BF16 tiles that only large launches reach -- 256x256 and 192x256 ping-pong, the four-wave 256x128 tile with the rolling (3x3)
@@ -365,6 +372,10 @@ def test_bf16_rule_tiles_vs_fp64_sampled(name, tile, kw):
     else:
         assert 128 <= counts["blocks256"] and (kw.get("out_f32", False) or counts["blocks256"] < 256)
     conv = Conv(BF16, B=B, seed=300 + len(name), **kw)
+    # ... and the library itself names that tile for the descriptor the "default" path launches (yv3_conv2d_kernel)
+    line = _ffi.conv2d_kernel(conv.desc(None))
+    print("bf16 rule | %s | yv3_conv2d_kernel: %s" % (name, line))
+    assert line.split()[0] == BF16_RULE_KERNEL[tile] and line.split()[2] == BF16_RULE_LOOP[tile], (name, tile, line)
     rows = cr.sample_rows(conv.B, conv.Ho, conv.Wo, seed=5)
     _run_paths(conv, [("default", 0, 0, None), ("code 7", _tile(7), 0, None)], ["code 7"], pixels=rows, what=name)
 

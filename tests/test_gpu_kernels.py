@@ -453,7 +453,10 @@ def test_conv_stream_k_schedule(cin, cout, k, s, B, H, W):
     (a range shorter than a tile) when there are far fewer tiles than CUs; shapes outside the rule run the plain
     schedule with the workspace ignored.  Same fp32-class tolerance vs fp64 as the plain schedule,
     the hand-over flags are all cleared again, no scheduling error is flagged, and a second launch reproduces the
-    first bit for bit (the split points are a function of the shape only)."""
+    first bit for bit (the split points are a function of the shape only).  Which side of the rule a shape is on is asked of the library
+    (yv3_conv2d_kernel) and checked against the rule restated below; each case prints it.  On 256 CUs five shapes are inside (all on the
+    128x128 tile: 268 tiles = 1.05 rounds at 26x26 / stride 2, and the four small batches) and three outside: both 64-image 13x13 layers
+    and the 47-image one take the four-wave 192x128 tile, which has no stream-K schedule."""
     mode = _ffi.F32H2
     m = _rand_cbr(cin, cout, k, s, seed=cin + cout + k)
     x = torch.rand(B, cin, H, W, generator=torch.Generator().manual_seed(1)) * 2 - 0.5
@@ -468,6 +471,16 @@ def test_conv_stream_k_schedule(cin, cout, k, s, B, H, W):
     ws = torch.zeros(_ffi.lib().yv3_conv_workspace_bytes(), dtype=torch.uint8, device="cuda")
     flags = torch.zeros(1, dtype=torch.int32, device="cuda")
     d = engine.make_desc(pc, xp, y, B, H, W, rp, dtype=mode, flags=flags, workspace=ws)
+    # the rule (csrc/conv_select.cpp), restated from the device's CU count: 3x3 layers on the eight-wave ping-pong tile whose tiles fill 1-2
+    # rounds of the chip or at most 0.4, with at least one K chunk per CU -- and the library says the same for this descriptor
+    line = _ffi.conv2d_kernel(d).split()
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    ncu = ncu & ~7 if ncu >= 8 else 256
+    rows = {"256x128_W8": 256, "128x128_W8": 128}.get(line[0])
+    total = -(-B * ho * wo // rows) * int(line[1][3:]) if rows else 0
+    want = (rows is not None and k == 3 and (ncu <= total < 2 * ncu or 5 * total <= 2 * ncu) and total * (k * k * cin // 32) >= ncu and ncu <= 512)
+    print("stream-K rule | %s | %d CUs | %s | %d tiles | %s the rule" % ((cin, cout, k, s, B, H, W), ncu, " ".join(line), total, "inside" if want else "outside"))
+    assert ("sk" in line) == want and (("grid=%d" % ncu) in line) == want and (not want or "pingpong" in line)
     _ffi.check(_ffi.lib().yv3_conv2d(d, _ffi.stream_ptr()))
     out = engine.from_planes(y, mode).permute(0, 3, 1, 2).cpu()
     assert_close_rel(out, ref, 2e-5, "stream-K conv %s" % ((cin, cout, k, s, B),))

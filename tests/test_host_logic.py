@@ -124,6 +124,20 @@ def test_abi_exports_every_declared_symbol():
     assert lib.yv3_conv_workspace_bytes() > 0
 
 
+def test_ffi_names_the_measurement_codes_of_conv_select_h():
+    """_ffi's TILE_* / T0_* / T1_* / T1P_* == the enumerators of csrc/conv_select.h's four measurement-code enums, name by name."""
+    header = open(os.path.join(REPO, "yolo_v3_amd", "csrc", "conv_select.h")).read()
+    declared = {n: int(v) for n, v in re.findall(r"\bYV3_((?:TILE|T0|T1|T1P)_[A-Za-z0-9_]+)\s*=\s*(\d+)\s*,", header)}
+    assert len(declared) >= 38, "too few enumerators parsed"
+    bound = {n: v for n, v in vars(_ffi).items() if re.match(r"(TILE|T0|T1|T1P)_", n)}
+    assert sorted(bound) == sorted(declared)
+    for name, value in sorted(declared.items()):
+        assert bound[name] == value, name
+    shift = int(re.search(r"#define\s+YV3_OPT_TILE_SHIFT\s+(\d+)", open(os.path.join(REPO, "include", "yv3.h")).read()).group(1))
+    assert _ffi.OPT_TILE_SHIFT == shift
+    assert _ffi.KERNEL_LINE_BYTES == int(re.search(r"YV3_KERNEL_LINE_BYTES\s*=\s*(\d+)", header).group(1))
+
+
 def test_conv_desc_layout_matches_the_c_header(tmp_path):
     """struct yv3_conv_desc as ctypes sees it == as a C compiler sees include/yv3.h (size and every field offset)."""
     import subprocess

@@ -1,4 +1,6 @@
-"""Records tests/golden/conv_select_256cu.json: yv3_conv2d_form / yv3_conv2d_launches over the grid of tests/conv_select_grid.py.
+"""Records tests/golden/conv_select_256cu.json: yv3_conv2d_form / yv3_conv2d_launches / yv3_conv2d_kernel over the grid of
+tests/conv_select_grid.py.  The kernel lines already in the file keep their index, new ones are appended: a changed rule shows up as the
+tokens it moved.
 
 Runs on the host (nothing is launched; without a GPU the library counts 256 compute units).  The table pins the library's kernel-selection
 rules: regenerate it only together with a deliberate change of a rule, and say which rows moved.
@@ -21,11 +23,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden", "conv_select_256cu.json"))
     args = ap.parse_args()
-    table = grid.table(_ffi.lib())
+    old = []
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            old = json.load(f).get("kernels", [])
+    table = grid.table(_ffi.lib(), old)
     with open(args.out, "w") as f:
         json.dump(table, f, indent=0, sort_keys=True)
         f.write("\n")
-    print("%s: %d layer rows, %d invalid descriptors" % (args.out, len(table["layers"]), len(table["errors"])))
+    print("%s: %d layer rows, %d invalid descriptors, %d kernel lines (%d new)"
+          % (args.out, len(table["layers"]), len(table["errors"]), len(table["kernels"]), len(table["kernels"]) - len(old)))
 
 
 if __name__ == "__main__":

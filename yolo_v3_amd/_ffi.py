@@ -22,6 +22,25 @@ F32, BF16, F32X3, F32H2 = 0, 1, 2, 3
 ACT_LINEAR, ACT_LEAKY = 0, 1
 PP_EVAL, PP_PROB = 1, 2
 OPT_NO_PINGPONG, OPT_K3S1, OPT_WINO_EVEN, OPT_WINO_ALWAYS, OPT_TWO_LANES, OPT_WINO4_TILES = 1, 2, 4, 8, 16, 32
+OPT_TILE_SHIFT = 8
+# The measurement codes of yv3_conv_desc (csrc/conv_select.h's enums without their YV3_ prefix; tests/test_host_logic.py compares name by name):
+# forced tile (options bits 8..15), tune[0] and tune[1] of exact fp32, tune[1] of the plane kernels (a bit set)
+(TILE_AUTO, TILE_256x128_W8, TILE_128x128_W8, TILE_128x128_W4, TILE_128x64, TILE_256x128_W4, TILE_256x256, TILE_256x128_W4_ROLL,
+ TILE_256x256_ROLL, TILE_256x256_ROLL4) = range(10)
+TILE_192x256_ROLL, TILE_W4_192x128, TILE_256x256_PP3, TILE_256x256_PP4, TILE_192x256_PP3, TILE_192x256_PP4 = 11, 12, 13, 14, 15, 16
+T0_F32_TILE_64, T0_F32_TILE_128_W4, T0_F32_TILE_128_1X1, T0_WINO2_HALF, T0_WINO2_FULL = 2, 6, 7, 8, 9
+T0_WINO4_NEVER, T0_WINO4_ALWAYS, T0_GEMM_NEVER, T0_GEMM_ALWAYS = 10, 11, 13, 14
+T1_WINO4_NO_EVEN, T1_WINO4_NO_FULL, T1_GEMM_ALL_ROWS = 1, 2, 3
+T1P_NO_SHORT_K, T1P_WINO_OTHER_LOOP, T1P_BF16_ROUND3, T1P_BF16_NO_192, T1P_NO_W4 = 1, 2, 8, 16, 32
+T1P_NO_W4_1X1, T1P_NO_W4_3X3, T1P_W4_LANES_3X3, T1P_BF16_ROLL, T1P_BF16_PP3 = 64, 128, 256, 512, 1024
+KERNEL_LINE_BYTES = 96
+
+
+def conv2d_kernel(desc):
+    """yv3_conv2d_kernel's line for a ConvDesc (raises on the YV3_E* code yv3_conv2d would return)."""
+    buf = ctypes.create_string_buffer(KERNEL_LINE_BYTES)
+    check(lib().yv3_conv2d_kernel(ctypes.byref(desc), buf, KERNEL_LINE_BYTES), "yv3_conv2d_kernel")
+    return buf.value.decode()
 
 c_void_p, c_int, c_float, c_size_t, c_longlong = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
                                                   ctypes.c_size_t, ctypes.c_longlong)
@@ -92,6 +111,7 @@ _SIGNATURES = {
     "yv3_conv2d": (c_int, [ctypes.POINTER(ConvDesc), c_void_p]),
     "yv3_conv2d_form": (c_int, [ctypes.POINTER(ConvDesc)]),
     "yv3_conv2d_launches": (c_int, [ctypes.POINTER(ConvDesc)]),
+    "yv3_conv2d_kernel": (c_int, [ctypes.POINTER(ConvDesc), ctypes.c_char_p, c_size_t]),
     "yv3_conv2d_sequence": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_void_p]),
     "yv3_decode": (c_int, [c_void_p, c_int, ctypes.POINTER(c_float), c_float, c_void_p, c_longlong,
                            c_int, c_int, c_int, c_int, c_void_p]),

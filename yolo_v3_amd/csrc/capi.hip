@@ -46,24 +46,26 @@ static int check_dtype(const yv3_conv_desc* d) {
     return YV3_EDTYPE;
 }
 
-// yv3_conv2d and its two queries: the argument checks, ONE CU-count query, ONE call of the selector (conv_select.cpp) -- then launch
-// its choice or report its form / its number of launches (or the YV3_E* code the launch would return)
-enum { CONV_LAUNCH, CONV_FORM, CONV_LAUNCHES };
-static int conv2d(const yv3_conv_desc* d, int what, hipStream_t s) {
+// yv3_conv2d and its three queries: the argument checks, ONE CU-count query, ONE call of the selector (conv_select.cpp), which is the CU
+// count's only reader -- then launch its choice or report its form / its number of launches / its description (or the YV3_E* code the
+// launch would return)
+enum { CONV_LAUNCH, CONV_FORM, CONV_LAUNCHES, CONV_KERNEL };
+static int conv2d(const yv3_conv_desc* d, int what, hipStream_t s, char* buf = nullptr, size_t buf_bytes = 0) {
     int rc = check_desc(d, what == CONV_LAUNCH);    // (the queries: a fused-decode head may not have its output bound yet)
     if (!rc) rc = check_dtype(d);
     if (rc) return rc;
     const int ncu = yv3_num_cu(), np = plane_count(d->dtype);
     if (d->dtype == YV3_F32) {
         const yv3_f32_choice c = yv3_select_f32(d, ncu);
-        return c.rc ? c.rc : what == CONV_FORM ? c.form : what == CONV_LAUNCHES ? c.launches : yv3_conv2d_f32(d, c, ncu, s);
+        return c.rc ? c.rc : what == CONV_FORM ? c.form : what == CONV_LAUNCHES ? c.launches : what == CONV_KERNEL ? yv3_describe_f32(c, buf, buf_bytes) : yv3_conv2d_f32(d, c, s);
     }
     const yv3_planes_choice c = yv3_select_planes(d, np, ncu);
-    return c.rc ? c.rc : what == CONV_FORM ? c.form : what == CONV_LAUNCHES ? c.launches : yv3_conv2d_planes(d, np, c, ncu, s);
+    return c.rc ? c.rc : what == CONV_FORM ? c.form : what == CONV_LAUNCHES ? c.launches : what == CONV_KERNEL ? yv3_describe_planes(c, buf, buf_bytes) : yv3_conv2d_planes(d, np, c, s);
 }
 extern "C" int yv3_conv2d(const yv3_conv_desc* d, void* stream) { return conv2d(d, CONV_LAUNCH, (hipStream_t)stream); }
 extern "C" int yv3_conv2d_form(const yv3_conv_desc* d) { return conv2d(d, CONV_FORM, nullptr); }
 extern "C" int yv3_conv2d_launches(const yv3_conv_desc* d) { return conv2d(d, CONV_LAUNCHES, nullptr); }
+extern "C" int yv3_conv2d_kernel(const yv3_conv_desc* d, char* buf, size_t buf_bytes) { return conv2d(d, CONV_KERNEL, nullptr, buf, buf_bytes); }
 
 extern "C" int yv3_conv2d_sequence(const yv3_conv_desc* descs, int n, void* stream) {
     if (!descs || n < 0) return YV3_EINVAL;

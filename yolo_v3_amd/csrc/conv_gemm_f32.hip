@@ -288,7 +288,7 @@ static_assert(YV3_SEL_CHUNK == 32 && YV3_SEL_GEMM_WAVE_M == 64 && YV3_SEL_GEMM_W
 
 // Launches the GEMM on output pixels [0, c.gemm_rows): whole rounds of the chip (one tile per CU and round) -- plus the last, partial round when
 // it is more than half full (conv_select.cpp).  The caller runs the remaining rows on conv_igemm_f32.hip's tiles.
-int yv3_conv2d_gemm1x1_f32(const yv3_conv_desc* d, const yv3_f32_choice& c, int ncu, hipStream_t s) {
+int yv3_conv2d_gemm1x1_f32(const yv3_conv_desc* d, const yv3_f32_choice& c, hipStream_t s) {
     Gemm1Params p;
     p.x = (const float*)d->x; p.w = (const float*)d->w; p.alpha = d->alpha; p.beta = d->beta; p.y = (float*)d->y;
     p.H = d->H; p.W = d->W; p.Cin = d->cin; p.stride = d->stride; p.cch = d->cin / 32;
@@ -302,7 +302,8 @@ int yv3_conv2d_gemm1x1_f32(const yv3_conv_desc* d, const yv3_f32_choice& c, int 
     p.ntn = c.ntiles;
     const long long tiles = ((Mr + bm - 1) / bm) * p.ntn;
     p.ntiles = (int)tiles;
-    const int grid = (int)(tiles < ncu ? (tiles + 7) / 8 * 8 : ncu);
+    const int grid = c.gemm_grid;
+    if (grid <= 0) return YV3_EINVAL;
     const size_t lds = (size_t)G1_NST * (bm + bn) * 128 + 2 * d->cout * sizeof(float);
     if (c.kernel == YV3_FK_GEMM_K3)      hipLaunchKernelGGL((conv_gemm1x1_f32_kernel<2, 4, true>), dim3(grid), dim3(512), lds, s, p);
     else if (wide)                       hipLaunchKernelGGL((conv_gemm1x1_f32_kernel<2, 4, false>), dim3(grid), dim3(512), lds, s, p);

@@ -376,7 +376,7 @@ int launch(const ConvParams& p, bool k3, bool dual, hipStream_t s, bool pin) {
 
 int yv3_wino_input_transform_f32(const float* x, float* v, int B, int H, int W, int C, hipStream_t s);
 int yv3_conv2d_wino4_f32(const yv3_conv_desc* d, const yv3_f32_choice& c, hipStream_t s);                   // csrc/conv_wino4_f32.hip
-int yv3_conv2d_gemm1x1_f32(const yv3_conv_desc* d, const yv3_f32_choice& c, int ncu, hipStream_t s);        // csrc/conv_gemm_f32.hip: persistent DMA-fed GEMM
+int yv3_conv2d_gemm1x1_f32(const yv3_conv_desc* d, const yv3_f32_choice& c, hipStream_t s);                 // csrc/conv_gemm_f32.hip: persistent DMA-fed GEMM
 
 static_assert(BK == YV3_SEL_CHUNK, "conv_select.cpp counts K chunks of BK elements");
 
@@ -409,7 +409,7 @@ static int launch_wino_f32(const yv3_conv_desc* d, ConvParams p, bool half, bool
 }
 
 // Launches what the selector chose (conv_select.cpp: yv3_select_f32) for a descriptor that passed its checks.
-int yv3_conv2d_f32(const yv3_conv_desc* d, const yv3_f32_choice& c, int ncu, hipStream_t s) {
+int yv3_conv2d_f32(const yv3_conv_desc* d, const yv3_f32_choice& c, hipStream_t s) {
     if (c.kernel == YV3_FK_WINO4) return yv3_conv2d_wino4_f32(d, c, s);
     ConvParams p;
     p.x = (const float*)d->x; p.x2 = (const float*)d->x2; p.w = (const float*)d->w;
@@ -425,7 +425,7 @@ int yv3_conv2d_f32(const yv3_conv_desc* d, const yv3_f32_choice& c, int ncu, hip
     yv3_f32_kernel kernel = c.kernel;
     if (kernel == YV3_FK_GEMM_128x128 || kernel == YV3_FK_GEMM_256x64 || kernel == YV3_FK_GEMM_K3) {
         // whole rounds of the chip on the persistent GEMM, the rest (< half a round of its tiles) on the tiles below
-        const int rc = yv3_conv2d_gemm1x1_f32(d, c, ncu, s);
+        const int rc = yv3_conv2d_gemm1x1_f32(d, c, s);
         if (rc || c.rest == YV3_FK_NONE) return rc;
         p.m_base = c.gemm_rows; p.ntiles = c.rest_ntiles;
         kernel = c.rest;

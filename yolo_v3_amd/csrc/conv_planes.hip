@@ -38,7 +38,7 @@ template <int N> __device__ __forceinline__ void wait_lgkmcnt() { __builtin_amdg
 // Every compile-time measurement switch below (timeline dumps that overwrite alpha[], ablations with INVALID results, schedule
 // experiments) exists only in measurement builds: the shipped libyv3.so is compiled without any of them.
 #if !defined(YV3_MEASURE) && (defined(YV3_TIMELINE) || defined(YV3_ABLATE) || defined(YV3_WABL) || defined(YV3_PPX) || defined(YV3_PRIO) || \
-                              defined(YV3_EXP_BF16MFMA) || defined(YV3_AB_NO_TWO_LANES_RULE))
+                              defined(YV3_EXP_BF16MFMA) || defined(YV3_AB_NO_TWO_LANES_RULE) || defined(YV3_WINO_ROLL))
 #error "measurement switches need -DYV3_MEASURE (make measure / tools/build_variant.sh); the shipped library has none"
 #endif
 // Measurement switches.  Run time: yv3_conv_desc.tune[] (conv_select.h names the codes; tune[3], measurement builds only: epilogue IO ablations).
@@ -763,42 +763,31 @@ __global__ __launch_bounds__(64 * WM * WN, MINW) void conv_planes_kernel(const C
     epilogue_store<NP, BM, BN, WM, WN, OUT_F32, true, EMTG>(acc, p, lds, m0, n0, wid, lane);
 }
 
+// Launches the instantiation the choice names: tile / waves / ring are the template arguments (the switch of yv3_conv2d_planes), main loop
+// and schedule are c.loop / c.stream_k.  The `if constexpr`s only keep combinations that do not exist from being instantiated; a choice
+// that asks for one is an error of the selector.
 template <int NP, int BM, int BN, int WM, int WN, int NSTAGE, int MINW = 1, int MTG = 0, bool ROLL = false>
-int launch_cfg(const ConvParamsP& p, bool k3, bool dual, bool out_f32, bool use_pp, int num_cu, hipStream_t s) {
+int launch_cfg(const ConvParamsP& p, bool k3, bool dual, bool out_f32, const yv3_planes_choice& c, hipStream_t s) {
     const int mtiles = (p.M + BM - 1) / BM;
     const dim3 grid((unsigned)(mtiles * p.ntiles));
     const dim3 block(64 * WM * WN);
     const size_t pipe = (size_t)NSTAGE * NP * (BM + BN) * ROWB;
     const size_t epi = (size_t)WM * WN * (MTG ? MTG * 32 : BM / WM) * (BN / WN + 4) * 4;   // WM*WN waves x rows per round x (BN/WN + 4) floats
     const size_t lds = pipe > epi ? pipe : epi;
-    const bool use_sk = true;                                      // stream-K persistent schedule iff the caller gave a workspace
-    // (num_cu: of the CURRENT device; multiple of 8: equal workgroups per XCD)
     ConvParamsP q = p;
     q.total = (int)grid.x;
-    // stream-K: opt-in (the caller passes yv3_conv_desc.workspace): a split tile is summed as head + middle.. + tail, so its rounding
-    // depends on where the split falls, i.e. on the batch size / the image's position in the batch -- results stay
-    // within the parity tolerance but are no longer bit-identical across batch compositions.
-    // It is used only for launches of fewer than two rounds of tiles (the 13x13 layers at bs=64; nearly every layer of a
-    // small batch, where it splits each tile's K range over the otherwise idle CUs): filling the idle CUs of a last
-    // partial round buys nothing on this power-limited kernel (the busy CUs simply clock higher: measured -9 % on the
-    // 2.6- and 5.3-round layers, which also lose the hardware's dynamic tile dispatch), but with 1.3 rounds the even
-    // split wins, and it lets the 13x13 3x3 layers use 256x128 tiles (+9 ... +11 %).
-    // Measured rule (tools/conv_bench.py, bs = 4 ... 64): it pays for the long-K 3x3 layers when the tiles fill 1 - 2
-    // rounds (even split instead of a 30 - 100 % idle second round) or at most 0.4 rounds (each tile's K range spread
-    // over the idle CUs: the 13x13 3x3 layer at bs=4 0.084 -> 0.039 ms); it loses for 1x1 layers (the accumulator
-    // exchange outweighs their few K chunks) and around 0.7 rounds.
-    const bool sk_shape = k3 && ((q.total >= num_cu && q.total < 2 * num_cu) || 5 * q.total <= 2 * num_cu);
-    const bool sk = use_sk && p.ws && p.wsflags && sk_shape && (long long)q.total * p.nk >= num_cu &&
-                    num_cu <= YV3_SK_MAX_WG && p.ws_bytes >= yv3_conv_workspace_bytes();
-    const dim3 sgrid((unsigned)num_cu);
+    const dim3 sgrid((unsigned)c.grid);
+    const bool pp = c.loop == YV3_LOOP_PINGPONG;
+    if ((c.loop == YV3_LOOP_ROLLING) != ROLL || (c.stream_k && (!pp || c.grid <= 0))) return YV3_EINVAL;
 #define YV3_LAUNCH(K3_, DUAL_, OF_) do { \
     if constexpr (NP == 1 && WM * WN == 8 && NSTAGE >= 3 && !ROLL) { \
-        if (use_pp) { hipLaunchKernelGGL((conv_planes_kernel<NP, BM, BN, WM, WN, NSTAGE, K3_, DUAL_, OF_, true, false, 1, MTG>), grid, block, lds, s, q); break; } \
+        if (pp && !c.stream_k) { hipLaunchKernelGGL((conv_planes_kernel<NP, BM, BN, WM, WN, NSTAGE, K3_, DUAL_, OF_, true, false, 1, MTG>), grid, block, lds, s, q); break; } \
     } \
     if constexpr (NP == 2 && WM * WN == 8 && NSTAGE >= 3 && !ROLL) { \
-        if (use_pp && sk) { hipLaunchKernelGGL((conv_planes_kernel<NP, BM, BN, WM, WN, NSTAGE, K3_, DUAL_, OF_, true, true>), sgrid, block, lds, s, q); break; } \
-        if (use_pp) { hipLaunchKernelGGL((conv_planes_kernel<NP, BM, BN, WM, WN, NSTAGE, K3_, DUAL_, OF_, true>), grid, block, lds, s, q); break; } \
+        if (c.stream_k) { hipLaunchKernelGGL((conv_planes_kernel<NP, BM, BN, WM, WN, NSTAGE, K3_, DUAL_, OF_, true, true>), sgrid, block, lds, s, q); break; } \
+        if (pp) { hipLaunchKernelGGL((conv_planes_kernel<NP, BM, BN, WM, WN, NSTAGE, K3_, DUAL_, OF_, true>), grid, block, lds, s, q); break; } \
     } \
+    if (pp) return YV3_EINVAL; \
     hipLaunchKernelGGL((conv_planes_kernel<NP, BM, BN, WM, WN, NSTAGE, K3_, DUAL_, OF_, false, false, MINW, MTG, false, ROLL>), grid, block, lds, s, q); } while (0)
     if (out_f32) {
         if (k3 || dual) return YV3_ESHAPE;                   // fp32 outputs are the 1x1 head convs
@@ -904,7 +893,7 @@ int yv3_wino_input_transform(const u16* x, long long xs, u16* v, int B, int H, i
 
 // Winograd F(2x2,3x3) form of a 3x3 / stride-1 fp16-plane layer: input transform (winograd.hip) + the 16-position GEMM with the
 // output transform folded into the main loop.  `p` = the direct launch's parameters (x, res, y, strides, Cout, act, flags).
-static int launch_wino(const yv3_conv_desc* d, ConvParamsP p, yv3_planes_kernel kernel, int num_cu, hipStream_t s) {
+static int launch_wino(const yv3_conv_desc* d, ConvParamsP p, const yv3_planes_choice& c, hipStream_t s) {
     const int th = (d->H + 1) / 2, tw = (d->W + 1) / 2;
     const long long T = (long long)d->B * th * tw;
     u16* v = (u16*)d->wino_ws;
@@ -921,18 +910,16 @@ static int launch_wino(const yv3_conv_desc* d, ConvParamsP p, yv3_planes_kernel 
     p.total = (int)grid.x;
     const size_t pipe = (size_t)NS * 2 * (BM + BN) * ROWB, epi = (size_t)8 * 32 * (BN / 2 + 4) * 4;
     const size_t lds = pipe > epi ? pipe : epi;
-    if (kernel == YV3_PK_WINO_EVEN) {
+    if (c.kernel == YV3_PK_WINO_EVEN) {
+        if (c.grid <= 0) return YV3_EINVAL;
         const size_t vbytes = (size_t)2 * 16 * T * d->cin * sizeof(u16);
         p.ws = (float*)((char*)d->wino_ws + ((vbytes + 255) & ~(size_t)255));
         p.wsflags = (int*)((char*)p.ws + (size_t)YV3_WINO_SK_MAX_WG * YV3_WINO_SK_PART_BYTES);
         p.ws_bytes = yv3_wino_sk_bytes();
-        hipLaunchKernelGGL((conv_planes_kernel<2, BM, BN, 4, 2, NS, false, false, false, true, true, 1, 0, true>), dim3((unsigned)num_cu), dim3(512), lds, s, p);
+        hipLaunchKernelGGL((conv_planes_kernel<2, BM, BN, 4, 2, NS, false, false, false, true, true, 1, 0, true>), dim3((unsigned)c.grid), dim3(512), lds, s, p);
     } else {
         p.ws = nullptr; p.wsflags = nullptr; p.ws_bytes = 0;
-#ifndef YV3_WINO_ROLL
-#define YV3_WINO_ROLL 0            // (A/B builds: 1 swaps the two loops' roles)
-#endif
-        if ((kernel == YV3_PK_WINO_ROLL) != YV3_WINO_ROLL)
+        if (c.kernel == YV3_PK_WINO_ROLL)
             hipLaunchKernelGGL((conv_planes_kernel<2, BM, BN, 4, 2, NS, false, false, false, false, false, 1, 0, true, true>), grid, dim3(512), lds, s, p);
         else
             hipLaunchKernelGGL((conv_planes_kernel<2, BM, BN, 4, 2, NS, false, false, false, true, false, 1, 0, true>), grid, dim3(512), lds, s, p);
@@ -941,12 +928,13 @@ static int launch_wino(const yv3_conv_desc* d, ConvParamsP p, yv3_planes_kernel 
     return 0;
 }
 
-extern "C" size_t yv3_conv_workspace_bytes(void) { return (size_t)YV3_SK_MAX_WG * (YV3_SK_PART_BYTES + sizeof(int)); }
+extern "C" size_t yv3_conv_workspace_bytes(void) { return yv3_sk_bytes(); }
 
 static_assert(PBK == YV3_SEL_CHUNK, "conv_select.cpp counts K chunks of PBK elements");
+static_assert(YV3_SK_PART_BYTES == 256 * 128 * sizeof(float), "a stream-K part holds the accumulators of the largest tile with a stream-K instantiation, 256x128");
 
 // Launches what the selector chose (conv_select.cpp: yv3_select_planes) for a descriptor that passed its checks.
-int yv3_conv2d_planes(const yv3_conv_desc* d, int np, const yv3_planes_choice& c, int ncu, hipStream_t s) {
+int yv3_conv2d_planes(const yv3_conv_desc* d, int np, const yv3_planes_choice& c, hipStream_t s) {
     ConvParamsP p;
     p.x = (const u16*)d->x; p.x2 = (const u16*)d->x2; p.w = (const u16*)d->w;
     p.alpha = d->alpha; p.beta = d->beta; p.res = (const u16*)d->residual; p.y = d->y;
@@ -977,31 +965,30 @@ int yv3_conv2d_planes(const yv3_conv_desc* d, int np, const yv3_planes_choice& c
     p.tb = d->cout_pad < 128 ? d->cout_pad : 128;
     p.ntiles = c.ntiles;
     const bool k3 = d->k == 3, dual = d->cin_up > 0, out_f32 = d->out_dtype == YV3_F32;
-    const bool use_pp = c.pingpong;
-#define YV3_CFG(BM_, BN_, WM_, WN_, NS_) (np == 3 ? launch_cfg<3, BM_, BN_, WM_, WN_, NS_>(p, k3, dual, out_f32, use_pp, ncu, s) : \
-                                         np == 2 ? launch_cfg<2, BM_, BN_, WM_, WN_, (NS_) + 1>(p, k3, dual, out_f32, use_pp, ncu, s) : \
-                                                   launch_cfg<1, BM_, BN_, WM_, WN_, NS_>(p, k3, dual, out_f32, false, ncu, s))
+#define YV3_CFG(BM_, BN_, WM_, WN_, NS_) (np == 3 ? launch_cfg<3, BM_, BN_, WM_, WN_, NS_>(p, k3, dual, out_f32, c, s) : \
+                                         np == 2 ? launch_cfg<2, BM_, BN_, WM_, WN_, (NS_) + 1>(p, k3, dual, out_f32, c, s) : \
+                                                   launch_cfg<1, BM_, BN_, WM_, WN_, NS_>(p, k3, dual, out_f32, c, s))
     switch (c.kernel) {
         case YV3_PK_K3S1_256x128: case YV3_PK_K3S1_128x128: case YV3_PK_K3S1_128x64: return yv3_conv2d_planes_k3s1(p, np, c.kernel, s);
-        case YV3_PK_WINO_PINGPONG: case YV3_PK_WINO_ROLL: case YV3_PK_WINO_EVEN: return launch_wino(d, p, c.kernel, ncu, s);
+        case YV3_PK_WINO_PINGPONG: case YV3_PK_WINO_ROLL: case YV3_PK_WINO_EVEN: return launch_wino(d, p, c, s);
         case YV3_PK_W4_192x128:     return yv3_conv2d_planes_w4(p, s);
         case YV3_PK_256x128_W8:     return YV3_CFG(256, 128, 4, 2, 2);
         case YV3_PK_128x128_W8:     return YV3_CFG(128, 128, 4, 2, 3);
-        case YV3_PK_128x128_W4:     return np == 2 ? launch_cfg<2, 128, 128, 2, 2, 2, 2>(p, k3, dual, out_f32, false, ncu, s)
-                                                   : launch_cfg<1, 128, 128, 2, 2, 2, 2>(p, k3, dual, out_f32, false, ncu, s);
-        case YV3_PK_128x64:         return np == 2 ? launch_cfg<2, 128, 64, 2, 2, 2>(p, k3, dual, out_f32, false, ncu, s) : YV3_CFG(128, 64, 2, 2, 2);
-        case YV3_PK_128x32:         return np == 2 ? launch_cfg<2, 128, 32, 4, 1, 2>(p, k3, dual, out_f32, false, ncu, s) : YV3_CFG(128, 32, 4, 1, 2);
-        case YV3_PK_256x128_W8_PP6: return launch_cfg<1, 256, 128, 4, 2, 6>(p, k3, dual, out_f32, true, ncu, s);
-        case YV3_PK_256x128_W4:     return launch_cfg<1, 256, 128, 2, 2, 3, 2, 2>(p, k3, dual, out_f32, false, ncu, s);
-        case YV3_PK_256x128_W4_ROLL: return launch_cfg<1, 256, 128, 2, 2, 3, 2, 2, true>(p, k3, dual, out_f32, false, ncu, s);
-        case YV3_PK_256x256:        return launch_cfg<1, 256, 256, 2, 4, 3, 1, 1>(p, k3, dual, out_f32, false, ncu, s);
-        case YV3_PK_256x256_ROLL:   return launch_cfg<1, 256, 256, 2, 4, 3, 1, 1, true>(p, k3, dual, out_f32, false, ncu, s);
-        case YV3_PK_256x256_ROLL4:  return launch_cfg<1, 256, 256, 2, 4, 4, 1, 1, true>(p, k3, dual, out_f32, false, ncu, s);
-        case YV3_PK_256x256_PP3:    return launch_cfg<1, 256, 256, 2, 4, 3, 1, 1>(p, k3, dual, out_f32, true, ncu, s);
-        case YV3_PK_256x256_PP4:    return launch_cfg<1, 256, 256, 2, 4, 4, 1, 1>(p, k3, dual, out_f32, true, ncu, s);
-        case YV3_PK_192x256_ROLL:   return launch_cfg<1, 192, 256, 2, 4, 3, 1, 1, true>(p, k3, dual, out_f32, false, ncu, s);
-        case YV3_PK_192x256_PP3:    return launch_cfg<1, 192, 256, 2, 4, 3, 1, 1>(p, k3, dual, out_f32, true, ncu, s);
-        case YV3_PK_192x256_PP4:    return launch_cfg<1, 192, 256, 2, 4, 4, 1, 1>(p, k3, dual, out_f32, true, ncu, s);
+        case YV3_PK_128x128_W4:     return np == 2 ? launch_cfg<2, 128, 128, 2, 2, 2, 2>(p, k3, dual, out_f32, c, s)
+                                                   : launch_cfg<1, 128, 128, 2, 2, 2, 2>(p, k3, dual, out_f32, c, s);
+        case YV3_PK_128x64:         return np == 2 ? launch_cfg<2, 128, 64, 2, 2, 2>(p, k3, dual, out_f32, c, s) : YV3_CFG(128, 64, 2, 2, 2);
+        case YV3_PK_128x32:         return np == 2 ? launch_cfg<2, 128, 32, 4, 1, 2>(p, k3, dual, out_f32, c, s) : YV3_CFG(128, 32, 4, 1, 2);
+        case YV3_PK_256x128_W8_PP6: return launch_cfg<1, 256, 128, 4, 2, 6>(p, k3, dual, out_f32, c, s);
+        case YV3_PK_256x128_W4:     return launch_cfg<1, 256, 128, 2, 2, 3, 2, 2>(p, k3, dual, out_f32, c, s);
+        case YV3_PK_256x128_W4_ROLL: return launch_cfg<1, 256, 128, 2, 2, 3, 2, 2, true>(p, k3, dual, out_f32, c, s);
+        case YV3_PK_256x256:        return launch_cfg<1, 256, 256, 2, 4, 3, 1, 1>(p, k3, dual, out_f32, c, s);
+        case YV3_PK_256x256_ROLL:   return launch_cfg<1, 256, 256, 2, 4, 3, 1, 1, true>(p, k3, dual, out_f32, c, s);
+        case YV3_PK_256x256_ROLL4:  return launch_cfg<1, 256, 256, 2, 4, 4, 1, 1, true>(p, k3, dual, out_f32, c, s);
+        case YV3_PK_256x256_PP3:    return launch_cfg<1, 256, 256, 2, 4, 3, 1, 1>(p, k3, dual, out_f32, c, s);
+        case YV3_PK_256x256_PP4:    return launch_cfg<1, 256, 256, 2, 4, 4, 1, 1>(p, k3, dual, out_f32, c, s);
+        case YV3_PK_192x256_ROLL:   return launch_cfg<1, 192, 256, 2, 4, 3, 1, 1, true>(p, k3, dual, out_f32, c, s);
+        case YV3_PK_192x256_PP3:    return launch_cfg<1, 192, 256, 2, 4, 3, 1, 1>(p, k3, dual, out_f32, c, s);
+        case YV3_PK_192x256_PP4:    return launch_cfg<1, 192, 256, 2, 4, 4, 1, 1>(p, k3, dual, out_f32, c, s);
     }
 #undef YV3_CFG
     return YV3_EINVAL;

@@ -32,10 +32,7 @@ struct ConvParamsP {
     int wH, wW, wth, wtw;       // output height / width, tile grid
 };
 
-// stream-K workspace geometry (yv3_conv_workspace_bytes): one 512-thread workgroup's accumulators per CU + one flag
-#define YV3_SK_MAX_WG 512
-#define YV3_SK_PART_BYTES (512 * 64 * 4)
-// (the Winograd stages' hand-over area -- YV3_WINO_SK_* -- is in yv3_common.h: conv_wino4_f32.hip shares it)
+// (the stream-K workspace geometry YV3_SK_* and the Winograd stages' hand-over area YV3_WINO_SK_* are in conv_select.h: the selector counts with them)
 
 // IO ablations of the epilogue (bit 0 no stores, bit 1 no residual loads, bit 2 no decode arithmetic: results INVALID) exist only in
 // measurement builds (-DYV3_MEASURE: `make measure` / tools/build_variant.sh -> libyv3_measure.so / libyv3_<name>.so); the shipped

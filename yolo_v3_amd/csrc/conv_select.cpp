@@ -1,5 +1,6 @@
 // Kernel selection of yv3_conv2d (conv_select.h): every measured crossover of the convolution path lives in this file.
 #include "conv_select.h"
+#include <stdio.h>
 
 yv3_conv_shape yv3_conv_out_shape(const yv3_conv_desc* d) {
     const int pad = (d->k - 1) / 2;
@@ -42,7 +43,7 @@ yv3_planes_choice yv3_select_planes(const yv3_conv_desc* d, int np, int ncu_) {
     yv3_planes_choice c = {};
     c.form = YV3_FORM_DIRECT; c.launches = 1;
     const auto fail = [&c](int rc) { c.rc = rc; return c; };
-    const auto pick = [&c](yv3_planes_kernel k, int ntiles) { c.kernel = k; c.ntiles = ntiles; return c; };
+    const auto pick = [&c](yv3_planes_kernel k, int ntiles, yv3_planes_loop loop = YV3_LOOP_PLAIN) { c.kernel = k; c.ntiles = ntiles; c.loop = loop; return c; };
     const long long ncu = ncu_;
     const bool k3 = d->k == 3, dual = d->cin_up > 0, out_f32 = d->out_dtype == YV3_F32;
     const int npad = d->cout_pad, tune1 = d->tune[1];
@@ -58,8 +59,7 @@ yv3_planes_choice yv3_select_planes(const yv3_conv_desc* d, int np, int ncu_) {
     if (tb <= 0 || npad % tb) return fail(YV3_ESHAPE);
     if (out_f32 && (k3 || dual)) return fail(YV3_ESHAPE);      // fp32 outputs are the 1x1 head convs
     const int nk = d->k * d->k * d->cin / YV3_SEL_CHUNK;
-    c.pingpong = !(d->options & YV3_OPT_NO_PINGPONG);          // ping-pong main loop (fp16x2, 8-wave tiles) unless disabled
-    const bool use_pp = c.pingpong;
+    const bool use_pp = !(d->options & YV3_OPT_NO_PINGPONG);   // ping-pong main loop (fp16x2 and the bf16 6-deep ring, 8-wave tiles) unless disabled
 
     // ---- the opt-in kw-tap reuse kernel (YV3_OPT_K3S1, conv_planes_k3s1.hip), BEFORE the Winograd rule: 44 % less L2->LDS traffic, same
     // results, but no faster on MI355X because this MFMA stream is power-limited -- opt-in until that changes.
@@ -91,7 +91,12 @@ yv3_planes_choice yv3_select_planes(const yv3_conv_desc* d, int np, int ncu_) {
         // two-group ping-pong loop (default) or the rolling single-phase loop (one barrier per chunk, fragment reads spread under the
         // MFMAs; tune[1] bit 1: A/B measurements -- bit-identical, equal speed: profiles/r04d_wino_roll_vs_pingpong_ab.log; the same stage
         // on FOUR waves with 64x64 wave tiles and the rolling loop was 1.4x slower, profiles/r04f_wino_4waves_roll_ab.log)
-        return pick(even ? YV3_PK_WINO_EVEN : (tune1 & YV3_T1P_WINO_OTHER_LOOP) ? YV3_PK_WINO_ROLL : YV3_PK_WINO_PINGPONG, npad / 128);
+#ifndef YV3_WINO_ROLL
+#define YV3_WINO_ROLL 0            // (A/B builds, -DYV3_MEASURE: 1 swaps the two loops' roles -- the build tools/timelines/roll.py reads its timeline from)
+#endif
+        if (even) { c.grid = ncu_; return pick(YV3_PK_WINO_EVEN, npad / 128, YV3_LOOP_PINGPONG); }
+        if (((tune1 & YV3_T1P_WINO_OTHER_LOOP) != 0) != YV3_WINO_ROLL) return pick(YV3_PK_WINO_ROLL, npad / 128, YV3_LOOP_ROLLING);
+        return pick(YV3_PK_WINO_PINGPONG, npad / 128, YV3_LOOP_PINGPONG);
     }
 
     // ---- direct tiles
@@ -104,6 +109,31 @@ yv3_planes_choice yv3_select_planes(const yv3_conv_desc* d, int np, int ncu_) {
         const int nt128 = npad / 128, nt256 = npad / 256;
         // (with the stream-K schedule every CU gets the same share whatever the tile count: one tile per CU suffices)
         const bool sk_ok = np == 2 && d->workspace && use_pp;
+        // The eight-wave 256x128 / 128x128 tiles (rows = 256 / 128): fp16 planes run the ping-pong loop (3- / 4-deep ring) unless it is disabled, one or
+        // three bf16 planes the plain loop (the 2- / 3-deep ring; three planes have no ping-pong instantiation) -- and the fp16-plane ping-pong
+        // tiles the persistent stream-K schedule, one workgroup per CU, by the rule below.
+
+        // (num_cu: of the CURRENT device; multiple of 8: equal workgroups per XCD)
+        // stream-K: opt-in (the caller passes yv3_conv_desc.workspace): a split tile is summed as head + middle.. + tail, so its rounding
+        // depends on where the split falls, i.e. on the batch size / the image's position in the batch -- results stay
+        // within the parity tolerance but are no longer bit-identical across batch compositions.
+        // It is used only for launches of fewer than two rounds of tiles (the 13x13 layers at bs=64; nearly every layer of a
+        // small batch, where it splits each tile's K range over the otherwise idle CUs): filling the idle CUs of a last
+        // partial round buys nothing on this power-limited kernel (the busy CUs simply clock higher: measured -9 % on the
+        // 2.6- and 5.3-round layers, which also lose the hardware's dynamic tile dispatch), but with 1.3 rounds the even
+        // split wins, and it lets the 13x13 3x3 layers use 256x128 tiles (+9 ... +11 %).
+        // Measured rule (tools/conv_bench.py, bs = 4 ... 64): it pays for the long-K 3x3 layers when the tiles fill 1 - 2
+        // rounds (even split instead of a 30 - 100 % idle second round) or at most 0.4 rounds (each tile's K range spread
+        // over the idle CUs: the 13x13 3x3 layer at bs=4 0.084 -> 0.039 ms); it loses for 1x1 layers (the accumulator
+        // exchange outweighs their few K chunks) and around 0.7 rounds.
+        const auto pick_w8 = [&](yv3_planes_kernel k, int rows) {
+            const long long num_cu = ncu, total = ((M + rows - 1) / rows) * nt128;
+            const bool sk_shape = k3 && ((total >= num_cu && total < 2 * num_cu) || 5 * total <= 2 * num_cu);
+            c.stream_k = sk_ok && sk_shape && (long long)total * nk >= num_cu &&
+                         num_cu <= YV3_SK_MAX_WG && d->workspace_bytes >= yv3_sk_bytes();
+            if (c.stream_k) c.grid = ncu_;
+            return pick(k, nt128, np == 2 && use_pp ? YV3_LOOP_PINGPONG : YV3_LOOP_PLAIN);
+        };
         const int big_min = d->big_tile_min > 0 ? d->big_tile_min : 128;
         const int force = (int)((d->options >> YV3_OPT_TILE_SHIFT) & 0xffu);
         // (code 12: the four-wave 256x128 tile with 16-deep chunks, two workgroups per CU -- conv_planes_w4.hip; it needs two K chunks)
@@ -116,18 +146,18 @@ yv3_planes_choice yv3_select_planes(const yv3_conv_desc* d, int np, int ncu_) {
         const bool t256_ok = np == 1 && npad % 256 == 0 && !out_f32;
         if (t256_ok && force == YV3_TILE_256x256) return pick(YV3_PK_256x256, nt256);
         // (code 8: the 256x256 tile with the rolling loop; code 9: 4-deep ring)
-        if (t256_ok && force == YV3_TILE_256x256_ROLL) return pick(YV3_PK_256x256_ROLL, nt256);
-        if (t256_ok && force == YV3_TILE_256x256_ROLL4) return pick(YV3_PK_256x256_ROLL4, nt256);
+        if (t256_ok && force == YV3_TILE_256x256_ROLL) return pick(YV3_PK_256x256_ROLL, nt256, YV3_LOOP_ROLLING);
+        if (t256_ok && force == YV3_TILE_256x256_ROLL4) return pick(YV3_PK_256x256_ROLL4, nt256, YV3_LOOP_ROLLING);
         // (code 11: the 192-row variant of the 256x256 rolling tile -- 96x64 wave tiles; also measured and dropped: 192x128 on four waves
         // and 128x256 on eight, profiles/r04aa_bf16_192row_tiles_ab.log)
         // (codes 13 / 14: the 256x256 tile with the eight-wave PING-PONG loop, 128x64 wave tiles, 3- / 4-deep ring; 14 is what the rule below ships)
-        if (t256_ok && force == YV3_TILE_256x256_PP3) return pick(YV3_PK_256x256_PP3, nt256);
-        if (t256_ok && force == YV3_TILE_256x256_PP4) return pick(YV3_PK_256x256_PP4, nt256);
+        if (t256_ok && force == YV3_TILE_256x256_PP3) return pick(YV3_PK_256x256_PP3, nt256, YV3_LOOP_PINGPONG);
+        if (t256_ok && force == YV3_TILE_256x256_PP4) return pick(YV3_PK_256x256_PP4, nt256, YV3_LOOP_PINGPONG);
         // (code 15: the 192-row variant with the ping-pong loop)
-        if (t256_ok && force == YV3_TILE_192x256_PP3) return pick(YV3_PK_192x256_PP3, nt256);
+        if (t256_ok && force == YV3_TILE_192x256_PP3) return pick(YV3_PK_192x256_PP3, nt256, YV3_LOOP_PINGPONG);
         // (code 16: ... with a 4-deep ring: one more chunk of prefetch lead)
-        if (t256_ok && force == YV3_TILE_192x256_PP4) return pick(YV3_PK_192x256_PP4, nt256);
-        if (t256_ok && force == YV3_TILE_192x256_ROLL) return pick(YV3_PK_192x256_ROLL, nt256);
+        if (t256_ok && force == YV3_TILE_192x256_PP4) return pick(YV3_PK_192x256_PP4, nt256, YV3_LOOP_PINGPONG);
+        if (t256_ok && force == YV3_TILE_192x256_ROLL) return pick(YV3_PK_192x256_ROLL, nt256, YV3_LOOP_ROLLING);
         if (np == 2 && force == YV3_TILE_128x64) return pick(YV3_PK_128x64, npad / 64);
         // Round 5: the four-wave 192x128 tile, TWO workgroups per CU (conv_planes_w4.hip): one workgroup's prologue / epilogue / launch gap
         // under the other's main loop; bit-identical to the eight-wave tile (same K order).  Same-box A/B, bs=64 (profiles/r05e_w4_192x128_ab.txt):
@@ -151,8 +181,8 @@ yv3_planes_choice yv3_select_planes(const yv3_conv_desc* d, int np, int ncu_) {
         // (the head convs at 52x52 / 26x26 included: +0.2...0.7 %; the 104x104 3x3 layers, K = 576, lose 1 % on it)
         if (np == 2 && !k3 && nk <= 16 && force == YV3_TILE_AUTO && blocks256 >= big_min && !(tune1 & YV3_T1P_NO_SHORT_K))
             return pick(YV3_PK_128x128_W4, nt128);
-        if (force == YV3_TILE_256x128_W8) return pick(YV3_PK_256x128_W8, nt128);
-        if (force == YV3_TILE_128x128_W8) return pick(YV3_PK_128x128_W8, nt128);
+        if (force == YV3_TILE_256x128_W8) return pick_w8(YV3_PK_256x128_W8, 256);
+        if (force == YV3_TILE_128x128_W8) return pick_w8(YV3_PK_128x128_W8, 128);
         // one bf16 plane (YV3_BF16): the same ping-pong loop with one MFMA per unit -- 608x608 bs=16: 2727 -> 3155
         // images/s on one lane (two 4-wave workgroups per CU instead: 2953)
         // (6-deep ring, 147 KB: with 8 MFMAs per chunk and wave a DMA piece needs several chunk times to land; 3-deep 3690, 4-deep
@@ -166,7 +196,7 @@ yv3_planes_choice yv3_select_planes(const yv3_conv_desc* d, int np, int ncu_) {
         // tile wins by 7...30 % (twice the waves per tile).  A 256x256 / 8-wave tile (code 6) loses to both at these sizes.
         // (tune[2] > 0: threshold override for A/B measurements)
         // (code 7: the same tile with the rolling loop -- barrier between the k-steps, next chunk's first fragments read under the MFMAs)
-        if (np == 1 && force == YV3_TILE_256x128_W4_ROLL) return pick(YV3_PK_256x128_W4_ROLL, nt128);
+        if (np == 1 && force == YV3_TILE_256x128_W4_ROLL) return pick(YV3_PK_256x128_W4_ROLL, nt128, YV3_LOOP_ROLLING);
         // Round 4 (tools/tile_ab.py, profiles/r04d_bf16_roll_ab.log, r04j_bf16_tiles_ab.log): the 3x3 layers take the ROLLING loop on that
         // tile (+2...6 %; the 1x1 layers lose 1-3 % on it and keep the plain loop) -- and a 256x256 tile on eight waves (128x64 wave tiles,
         // one workgroup per CU, rolling loop: 32 KB of DMA per 128 MFMAs instead of 24 KB per 64 -- the L2 -> LDS path delivers 62 B/clk/CU,
@@ -192,15 +222,15 @@ yv3_planes_choice yv3_select_planes(const yv3_conv_desc* d, int np, int ncu_) {
             // (profiles/r05ae_*, r05af_*; a per-layer A/B decides nothing by itself).
             const bool roll = (tune1 & YV3_T1P_BF16_ROLL) != 0, pp3 = (tune1 & YV3_T1P_BF16_PP3) != 0;
             if (!(tune1 & YV3_T1P_BF16_NO_192) && t192 * 100 >= 85 * r192 && t256 * 100 < 80 * r256)
-                return pick(roll ? YV3_PK_192x256_ROLL : pp3 ? YV3_PK_192x256_PP3 : YV3_PK_192x256_PP4, nt256);
-            if (fill) return pick(roll ? YV3_PK_256x256_ROLL : pp3 ? YV3_PK_256x256_PP3 : YV3_PK_256x256_PP4, nt256);
+                return pick(roll ? YV3_PK_192x256_ROLL : pp3 ? YV3_PK_192x256_PP3 : YV3_PK_192x256_PP4, nt256, roll ? YV3_LOOP_ROLLING : YV3_LOOP_PINGPONG);
+            if (fill) return pick(roll ? YV3_PK_256x256_ROLL : pp3 ? YV3_PK_256x256_PP3 : YV3_PK_256x256_PP4, nt256, roll ? YV3_LOOP_ROLLING : YV3_LOOP_PINGPONG);
         }
         const int w4_min = d->tune[2] > 0 ? d->tune[2] : 256;
-        if (np == 1 && force == YV3_TILE_AUTO && k3 && blocks256 >= w4_min && !out_f32 && !(tune1 & YV3_T1P_BF16_ROUND3)) return pick(YV3_PK_256x128_W4_ROLL, nt128);
+        if (np == 1 && force == YV3_TILE_AUTO && k3 && blocks256 >= w4_min && !out_f32 && !(tune1 & YV3_T1P_BF16_ROUND3)) return pick(YV3_PK_256x128_W4_ROLL, nt128, YV3_LOOP_ROLLING);
         if (np == 1 && force == YV3_TILE_AUTO && blocks256 >= w4_min && !out_f32) return pick(YV3_PK_256x128_W4, nt128);
-        if (np == 1 && use_pp && force == YV3_TILE_AUTO && blocks256 >= big_min) return pick(YV3_PK_256x128_W8_PP6, nt128);
-        if (blocks256 >= (sk_ok ? 256 : big_min)) return pick(YV3_PK_256x128_W8, nt128);
-        return pick(YV3_PK_128x128_W8, nt128);
+        if (np == 1 && use_pp && force == YV3_TILE_AUTO && blocks256 >= big_min) return pick(YV3_PK_256x128_W8_PP6, nt128, YV3_LOOP_PINGPONG);
+        if (blocks256 >= (sk_ok ? 256 : big_min)) return pick_w8(YV3_PK_256x128_W8, 256);
+        return pick_w8(YV3_PK_128x128_W8, 128);
     }
     // fp16 planes: 2-deep ring (49 KB) -> three workgroups per CU instead of two (+4 % on the 208x208 3x3 layer)
     if (npad % 64 == 0) return pick(YV3_PK_128x64, npad / 64);
@@ -337,6 +367,8 @@ yv3_f32_choice yv3_select_f32(const yv3_conv_desc* d, int ncu_) {
                 if (rounds >= 1 && rest > 0 && 2 * rest <= ncu) mt_run = rounds * ncu / ntn;
             }
             c.gemm_rows = (int)(mt_run * bm < M ? mt_run * bm : M);
+            const long long tiles = ((c.gemm_rows + bm - 1) / bm) * ntn;
+            c.gemm_grid = (int)(tiles < ncu ? (tiles + 7) / 8 * 8 : ncu);
             if (c.gemm_rows < M) {
                 c.launches = 2;
                 c.rest = k3 ? YV3_FK_128x128_W8 : np % 128 == 0 ? YV3_FK_64x64 : YV3_FK_128x64;
@@ -361,4 +393,67 @@ yv3_f32_choice yv3_select_f32(const yv3_conv_desc* d, int ncu_) {
     }
     if (np % 64 == 0) return pick(YV3_FK_128x64, np / 64);
     return pick(YV3_FK_128x32, np / 32);
+}
+
+// =========================================================================================== names: what yv3_conv2d_kernel prints
+
+const char* yv3_planes_kernel_name(yv3_planes_kernel k) {
+    switch (k) {
+#define N(x) case YV3_PK_##x: return #x;
+        N(256x128_W8) N(128x128_W8) N(128x128_W4) N(128x64) N(128x32) N(256x128_W8_PP6) N(256x128_W4) N(256x128_W4_ROLL)
+        N(256x256) N(256x256_ROLL) N(256x256_ROLL4) N(256x256_PP3) N(256x256_PP4) N(192x256_ROLL) N(192x256_PP3) N(192x256_PP4)
+        N(W4_192x128) N(K3S1_256x128) N(K3S1_128x128) N(K3S1_128x64) N(WINO_PINGPONG) N(WINO_ROLL) N(WINO_EVEN)
+#undef N
+    }
+    return "?";
+}
+const char* yv3_planes_loop_name(yv3_planes_loop l) {
+    switch (l) {
+        case YV3_LOOP_PLAIN: return "plain";
+        case YV3_LOOP_ROLLING: return "rolling";
+        case YV3_LOOP_PINGPONG: return "pingpong";
+    }
+    return "?";
+}
+const char* yv3_f32_kernel_name(yv3_f32_kernel k) {
+    switch (k) {
+#define N(x) case YV3_FK_##x: return #x;
+        N(NONE) N(128x128_W8) N(128x128_W4) N(64x64) N(128x64) N(128x32) N(WINO2) N(WINO4) N(GEMM_128x128) N(GEMM_256x64) N(GEMM_K3)
+#undef N
+    }
+    return "?";
+}
+
+// One line: the kernel's name and its channel tiles, the planes' loop / exact fp32's pin, then every other field of the choice that is not at
+// its default (absent = no stream-K, no persistent grid, no F(2x2) half tile, not F(4x4), no GEMM rows, no rest)
+namespace {
+struct line {
+    char* buf; size_t room, n = 0; bool ok = true;
+    line(char* b, size_t bytes) : buf(b), room(bytes < YV3_KERNEL_LINE_BYTES ? bytes : YV3_KERNEL_LINE_BYTES) {}
+    void took(int m) { if (m < 0 || (size_t)m >= room - n) ok = false; else n += m; }
+    void word(const char* w) { if (ok) took(snprintf(buf + n, room - n, n ? " %s" : "%s", w)); }
+    void field(const char* key, int v) { if (ok) took(snprintf(buf + n, room - n, " %s=%d", key, v)); }
+    int rc() const { return ok ? 0 : YV3_EINVAL; }
+};
+}  // namespace
+
+int yv3_describe_planes(const yv3_planes_choice& c, char* buf, size_t buf_bytes) {
+    if (!buf || !buf_bytes) return YV3_EINVAL;
+    line l(buf, buf_bytes);
+    l.word(yv3_planes_kernel_name(c.kernel)); l.field("nt", c.ntiles);
+    l.word(yv3_planes_loop_name(c.loop));
+    if (c.stream_k) l.word("sk");
+    if (c.grid) l.field("grid", c.grid);
+    return l.rc();
+}
+int yv3_describe_f32(const yv3_f32_choice& c, char* buf, size_t buf_bytes) {
+    if (!buf || !buf_bytes) return YV3_EINVAL;
+    line l(buf, buf_bytes);
+    l.word(yv3_f32_kernel_name(c.kernel)); l.field("nt", c.ntiles);
+    l.field("pin", c.pin);
+    if (c.wino2_half) l.word("half");
+    if (c.kernel == YV3_FK_WINO4 || c.n_full || c.parts != 1) { l.field("full", c.n_full); l.field("parts", c.parts); }
+    if (c.gemm_rows || c.gemm_grid) { l.field("rows", c.gemm_rows); l.field("grid", c.gemm_grid); }
+    if (c.rest != YV3_FK_NONE || c.rest_ntiles) { l.word("rest"); l.word(yv3_f32_kernel_name(c.rest)); l.field("nt", c.rest_ntiles); }
+    return l.rc();
 }

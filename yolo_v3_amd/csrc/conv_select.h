@@ -1,8 +1,9 @@
-// Kernel selection of yv3_conv2d: which form, kernel, tile, ring depth and schedule a descriptor runs, decided in ONE place
-// (conv_select.cpp) and apart from launching it.  Plain host code: no HIP, no runtime call, no static state -- the CU count is a parameter.
-// yv3_conv2d, yv3_conv2d_form and yv3_conv2d_launches (capi.hip) each call the selector once; the launchers (conv_planes.hip,
-// conv_igemm_f32.hip, ...) fill their parameter structs from the descriptor and the choice and switch on the kernel enum.
-// yv3_conv_desc.options, .big_tile_min and .tune[0..2] are read here and nowhere else.
+// Kernel selection of yv3_conv2d: which form, kernel, tile, ring depth, main loop, schedule and persistent grid a descriptor runs,
+// decided in ONE place (conv_select.cpp) and apart from launching it.  Plain host code: no HIP, no runtime call, no static state -- the
+// CU count is a parameter, and the selector is its only reader.  yv3_conv2d and its queries yv3_conv2d_form, yv3_conv2d_launches and
+// yv3_conv2d_kernel (capi.hip) each call the selector once; the launchers (conv_planes.hip, conv_igemm_f32.hip, ...) fill their parameter
+// structs from the descriptor and the choice, switch on the kernel enum and decide nothing: a choice they have no instantiation for is
+// YV3_EINVAL.  yv3_conv_desc.options, .big_tile_min and .tune[0..2] are read here and nowhere else.
 #pragma once
 #include <stddef.h>
 #include "yv3.h"
@@ -69,6 +70,11 @@ constexpr int YV3_SEL_WINO4_TILES = 32, YV3_SEL_WINO4_CHANNELS = 64;  // conv_wi
 // (the plane / fp32 implicit-GEMM tiles -- 256, 192, 128 or 64 rows by 256, 128, 64 or 32 channels -- are template arguments at the
 // launchers' switch; an enumerator's name carries them)
 
+// stream-K workspace of the direct fp16-plane tiles (yv3_conv_desc.workspace, yv3_conv_workspace_bytes()): YV3_SK_MAX_WG parts -- one
+// 512-thread workgroup's accumulators per CU -- then as many flags
+#define YV3_SK_MAX_WG 512
+#define YV3_SK_PART_BYTES (512 * 64 * 4)
+static inline size_t yv3_sk_bytes() { return (size_t)YV3_SK_MAX_WG * (YV3_SK_PART_BYTES + sizeof(int)); }
 // Hand-over area of the Winograd stages' even schedules (tail of yv3_conv_desc.wino_ws): YV3_WINO_SK_MAX_WG parts, then as many flags.
 // A part holds one workgroup's partial outputs: four output accumulator sets of a 512-thread workgroup (F(2x2), fp16 planes: 256 KB) or
 // the sixteen outputs of a 256-thread workgroup (F(4x4), exact fp32: 128 KB of it).
@@ -82,17 +88,19 @@ constexpr int YV3_SEL_WINO4_MAX_TAIL_WG = 2 * YV3_WINO_SK_MAX_WG - 1;     // tai
 static inline size_t yv3_wino4_v_bytes(int B, int H, int W, int cin) { return (size_t)36 * B * ((H + 3) / 4) * ((W + 3) / 4) * cin * sizeof(float); }
 static inline size_t yv3_wino4_ws_bytes(int B, int H, int W, int cin) { return ((yv3_wino4_v_bytes(B, H, W, cin) + 255) & ~(size_t)255) + yv3_wino_sk_bytes(); }
 
-// ---- the choice.  One enumerator per kernel instantiation a launcher can reach (the plane count NP, 3x3 / dual-source / fp32-output
-// are properties of the descriptor, not choices: the launchers take them from there).
+// ---- the choice.  An enumerator names tile, waves and ring of a launch, the loop kind and the schedule beside it the main loop: together
+// one kernel instantiation (the plane count NP, 3x3 / dual-source / fp32-output are properties of the descriptor, not choices: the
+// launchers take them from there).
 enum yv3_planes_kernel {
-    // conv_planes.hip launch_cfg<NP, BM, BN, WM, WN, ring, ...>: rows x channels, waves, loop
-    YV3_PK_256x128_W8,          // 8 waves; ring 2 (3 for fp16 planes); fp16 planes: ping-pong unless YV3_OPT_NO_PINGPONG, stream-K with a workspace
-    YV3_PK_128x128_W8,          // 8 waves; ring 3 (4 for fp16 planes); as above
-    YV3_PK_128x128_W4,          // 4 waves, two workgroups per CU, ring 2
-    YV3_PK_128x64,              // 4 waves, ring 2
-    YV3_PK_128x32,              // 4 waves, ring 2
+    // conv_planes.hip launch_cfg<NP, BM, BN, WM, WN, ring, ...>: rows x channels, waves
+    YV3_PK_256x128_W8,          // 8 waves; ring 2 (3 for fp16 planes).  fp16 planes: ping-pong loop (plain under YV3_OPT_NO_PINGPONG), stream-K by
+                                // the rule; one or three bf16 planes: plain loop
+    YV3_PK_128x128_W8,          // 8 waves; ring 3 (4 for fp16 planes); loops and schedule as above
+    YV3_PK_128x128_W4,          // 4 waves, two workgroups per CU, ring 2, plain loop
+    YV3_PK_128x64,              // 4 waves, ring 2, plain loop
+    YV3_PK_128x32,              // 4 waves, ring 2, plain loop
     YV3_PK_256x128_W8_PP6,      // bf16: 8-wave ping-pong loop, 6-deep ring
-    YV3_PK_256x128_W4,          // bf16: 4 waves, two workgroups per CU, ring 3
+    YV3_PK_256x128_W4,          // bf16: 4 waves, two workgroups per CU, ring 3, plain loop
     YV3_PK_256x128_W4_ROLL,     //   ... rolling loop
     YV3_PK_256x256,             // bf16: 8 waves, single-phase loop, ring 3
     YV3_PK_256x256_ROLL,        //   ... rolling loop, ring 3
@@ -102,21 +110,31 @@ enum yv3_planes_kernel {
     YV3_PK_192x256_ROLL,        // bf16: 8 waves of 96x64, rolling loop, ring 3
     YV3_PK_192x256_PP3,         //   ... ping-pong loop, ring 3
     YV3_PK_192x256_PP4,         //   ... ping-pong loop, ring 4
-    YV3_PK_W4_192x128,          // conv_planes_w4.hip
+    YV3_PK_W4_192x128,          // conv_planes_w4.hip (a kernel with one main loop of its own: the loop kind says plain, as for the next three)
     YV3_PK_K3S1_256x128,        // conv_planes_k3s1.hip launch_k3s1<NP, 256, 128, 4, 2>
     YV3_PK_K3S1_128x128,        //   <NP, 128, 128, 4, 2>
     YV3_PK_K3S1_128x64,         //   <NP, 128, 64, 2, 2>
     YV3_PK_WINO_PINGPONG,       // Winograd F(2x2) stage, one 128x128 tile per workgroup: the tune bit's two main loops
     YV3_PK_WINO_ROLL,
-    YV3_PK_WINO_EVEN,           //   ... stream-K over transform positions (YV3_OPT_WINO_EVEN)
+    YV3_PK_WINO_EVEN,           //   ... stream-K over transform positions (YV3_OPT_WINO_EVEN): ping-pong loop, one persistent workgroup per CU
 };
+const char* yv3_planes_kernel_name(yv3_planes_kernel k);        // the enumerator without YV3_PK_
+// main loop of conv_planes_kernel (its PP / ROLL template arguments)
+enum yv3_planes_loop {
+    YV3_LOOP_PLAIN,             // single phase, one barrier pair per chunk
+    YV3_LOOP_ROLLING,           // single phase, next chunk's first fragments read under the MFMAs
+    YV3_LOOP_PINGPONG,          // two four-wave groups: one reads fragments while the other issues MFMAs (eight-wave tiles, ring >= 3, <= 2 planes)
+};
+const char* yv3_planes_loop_name(yv3_planes_loop l);
 struct yv3_planes_choice {
     int rc;                     // the YV3_E* code yv3_conv2d returns before anything is launched, or 0
     int form, launches;
     yv3_planes_kernel kernel;
     int Ho, Wo, M;
     int ntiles;                 // channel tiles of the launch
-    bool pingpong;              // !YV3_OPT_NO_PINGPONG (YV3_PK_256x128_W8 / _128x128_W8 / _128x64 / _128x32)
+    yv3_planes_loop loop;       // the main loop that runs
+    bool stream_k;              // YV3_PK_256x128_W8 / _128x128_W8 on fp16 planes, ping-pong loop: the persistent stream-K schedule (yv3_conv_desc.workspace)
+    int grid;                   // workgroups of a persistent launch (stream_k, YV3_PK_WINO_EVEN: one per CU), else 0: one per tile
 };
 
 enum yv3_f32_kernel {
@@ -128,6 +146,7 @@ enum yv3_f32_kernel {
     // conv_gemm_f32.hip conv_gemm1x1_f32_kernel<WM, WN, K3>
     YV3_FK_GEMM_128x128, YV3_FK_GEMM_256x64, YV3_FK_GEMM_K3,
 };
+const char* yv3_f32_kernel_name(yv3_f32_kernel k);              // the enumerator without YV3_FK_
 struct yv3_f32_choice {
     int rc;                     // the YV3_E* code yv3_conv2d returns before anything is launched, or 0
     int form, launches;
@@ -138,6 +157,7 @@ struct yv3_f32_choice {
     bool wino2_half;            // F(2x2): the four-wave 64x128 tile
     int n_full, parts;          // F(4x4): whole-item workgroups, ranges per item of the rest (1: one item per workgroup throughout)
     int gemm_rows;              // persistent GEMM: the output pixels [0, gemm_rows) it takes ...
+    int gemm_grid;              //   ... on this many workgroups (one per CU; a multiple of 8 when there are fewer tiles) ...
     yv3_f32_kernel rest;        //   ... and the direct kernel for the others (YV3_FK_NONE: none left)
     int rest_ntiles;
 };
@@ -148,3 +168,9 @@ yv3_conv_shape yv3_conv_out_shape(const yv3_conv_desc* d);
 
 yv3_planes_choice yv3_select_planes(const yv3_conv_desc* d, int np, int ncu);     // np = planes per tensor: 1 bf16, 2 fp16 hi+lo, 3 bf16 x3
 yv3_f32_choice yv3_select_f32(const yv3_conv_desc* d, int ncu);
+
+// One line (at most YV3_KERNEL_LINE_BYTES with its NUL) that holds every field of a choice that is not a function of the descriptor alone
+// (those at their default left out): what yv3_conv2d_kernel writes.  Returns 0, or YV3_EINVAL when it does not fit into buf_bytes.
+constexpr size_t YV3_KERNEL_LINE_BYTES = 96;
+int yv3_describe_planes(const yv3_planes_choice& c, char* buf, size_t buf_bytes);
+int yv3_describe_f32(const yv3_f32_choice& c, char* buf, size_t buf_bytes);

@@ -29,9 +29,10 @@ static inline int yv3_num_cu() {
 }
 
 // The convolution launchers behind yv3_conv2d (capi.hip): each fills its parameter struct from the descriptor and the selector's choice
-// (conv_select.h; the Winograd stages' hand-over area YV3_WINO_SK_* is there too) and returns only launch errors.
-int yv3_conv2d_planes(const yv3_conv_desc* d, int np, const yv3_planes_choice& c, int ncu, hipStream_t s);
-int yv3_conv2d_f32(const yv3_conv_desc* d, const yv3_f32_choice& c, int ncu, hipStream_t s);
+// (conv_select.h; the workspace geometries YV3_SK_* / YV3_WINO_SK_* are there too), decides nothing -- the CU count stays with the selector --
+// and returns launch errors, or YV3_EINVAL for a choice it has no instantiation for.
+int yv3_conv2d_planes(const yv3_conv_desc* d, int np, const yv3_planes_choice& c, hipStream_t s);
+int yv3_conv2d_f32(const yv3_conv_desc* d, const yv3_f32_choice& c, hipStream_t s);
 
 // float -> bf16 bits, round to nearest even (NaN kept quiet)
 __host__ __device__ static inline u16 yv3_f2bf(float f) {

@@ -476,6 +476,11 @@ class Plan:
             out.append(int(n))
         return out
 
+    def kernels(self):
+        """Per descriptor of the launch sequence: the line ``yv3_conv2d_kernel`` writes -- kernel instantiation, tiles, loop, schedule and
+        grids as the library chooses them on the current device."""
+        return [_ffi.conv2d_kernel(self.descs[j]) for j in range(self.first_desc, self.n_desc)]
+
     def forms(self):
         """Per descriptor of the launch sequence (``descs[first_desc:]``): (conv spec index, form) with form = 0 direct /
         1 Winograd F(2x2,3x3) / 2 Winograd F(4x4,3x3) (exact-fp32 mode), as the library decides it on the current device
