@@ -111,6 +111,34 @@ def desc_inputs_by_pointer(plan):
     return names
 
 
+CANARY = 4096
+
+
+def copy_desc(d):
+    """A copy of a ConvDesc (the plan tests relaunch copies of a plan's own descriptors with one field changed)."""
+    import ctypes
+    from yolo_v3_amd import _ffi
+    c = _ffi.ConvDesc()
+    ctypes.memmove(ctypes.byref(c), ctypes.byref(d), ctypes.sizeof(c))
+    return c
+
+
+def relaunch_desc(d, n, what, dtype=torch.float32, planes=1):
+    """Launch descriptor `d` into a fresh NaN-filled buffer of `planes` x n elements of `dtype` (the packed plane layout of an n-element
+    output) + a NaN canary behind it: every element written, nothing behind.  Returns the [planes * n] elements."""
+    import ctypes
+    from yolo_v3_amd import _ffi
+    n *= planes
+    y = torch.full((n + CANARY,), float("nan"), dtype=dtype, device="cuda")
+    d.y = y.data_ptr()
+    _ffi.check(_ffi.lib().yv3_conv2d(ctypes.byref(d), _ffi.stream_ptr()), what)
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(y[n:]).all()), "%s: wrote past the end of y" % what
+    holes = int(torch.isnan(y[:n]).sum())
+    assert holes == 0, "%s: %d output elements not written" % (what, holes)
+    return y[:n]
+
+
 def teacher_forced_layers(net, mode, x, taps):
     """Run every one of the 75 convolutions of `net` ALONE through the C-ABI in math mode `mode`, each fed the
     ORACLE's activations (``taps`` = [(name, NCHW fp32 tensor)] from oracle_cpu.head_logits) instead of the previous

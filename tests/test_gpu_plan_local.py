@@ -38,7 +38,7 @@ import torch
 from yolo_v3_amd import _ffi, synth, Detector, YoloNet, WeightManager
 from tests import conv_ref as cr
 from tests import plan_ref as pr
-from tests.helpers import load_sw1_net, desc_inputs_by_pointer
+from tests.helpers import load_sw1_net, desc_inputs_by_pointer, copy_desc, relaunch_desc
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +46,6 @@ F32 = _ffi.F32
 BAR = pr.BAR                # the fused front kernels (K = 27 ... 288): the project's fixed exact-fp32 bar
 DIRECT_X, WINO_X = 4, 8     # yv3_conv2d launches: multiples of torch fp32's own error on the same rows (direct forms / Winograd forms)
 FP32_ULP = 2.0 ** -24       # ... which is never taken below one fp32 rounding of the result
-CANARY = 4096
 NAN = float("nan")
 
 
@@ -58,22 +57,7 @@ def _gpu():
     torch.cuda.synchronize()
 
 
-def _copy(d):
-    c = _ffi.ConvDesc()
-    ctypes.memmove(ctypes.byref(c), ctypes.byref(d), ctypes.sizeof(c))
-    return c
-
-
-def _relaunch(d, n, what):
-    """Launch descriptor `d` into a fresh NaN-filled buffer of n elements + canary: every element written, nothing behind."""
-    y = torch.full((n + CANARY,), NAN, dtype=torch.float32, device="cuda")
-    d.y = y.data_ptr()
-    _ffi.check(_ffi.lib().yv3_conv2d(ctypes.byref(d), _ffi.stream_ptr()), what)
-    torch.cuda.synchronize()
-    assert bool(torch.isnan(y[n:]).all()), "%s: wrote past the end of y" % what
-    holes = int(torch.isnan(y[:n]).sum())
-    assert holes == 0, "%s: %d output elements not written" % (what, holes)
-    return y[:n]
+_copy, _relaunch = copy_desc, relaunch_desc      # (shared with tests/test_gpu_plane_plan_local.py: tests/helpers.py)
 
 
 def _dev_err(a, b):
