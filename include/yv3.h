@@ -298,6 +298,12 @@ int yv3_decode_nchw(const float* logits_nchw, const float* anchors_host, float s
                     float* out, long long out_batch_stride, int B, int H, int W, int num_class,
                     void* stream);
 
+/* dlogits (NCHW, as logits_nchw) = dL/dlogits of yv3_decode_nchw for dout = dL/dout ([B][H*W*3][5+C], contiguous): per element
+ * dout times the decode map's derivative, recomputed from the logit -- stride s(1-s) for tx and ty, the decoded w and h for tw and
+ * th, s(1-s) for conf and every class (s = sigmoid). */
+int yv3_decode_bwd_nchw(const float* logits_nchw, const float* dout, const float* anchors_host, float stride,
+                        float* dlogits_nchw, int B, int H, int W, int num_class, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Geometry helpers.  Replace boundingbox.py:25-29, utils.py:98-119, utils.py:122-146.
  * ------------------------------------------------------------------------------------------ */
@@ -542,6 +548,11 @@ int yv3_train_conv_fwd(const float* x, const float* x2, const float* wf, const f
 int yv3_train_conv_dgrad(const float* dz, const float* wd, float* dx, int B, int H, int W, int cin, int cout, int k, int stride,
                          int accumulate, void* stream);
 
+/* dx = dL/dx of layer 0 (3x3, stride 1, pad 1, cin = 3): dz [B][H][W][cout] fp32, w the parameter itself [cout][3][3][3] fp32,
+ * dx [B][3][H][W] fp32, overwritten -- the input gradient in the caller's NCHW layout (a direct memory-bound kernel, not the GEMM
+ * tile).  cout must be a multiple of 4 (YV3_ESHAPE). */
+int yv3_train_conv0_dgrad(const float* dz, const float* w, float* dx_nchw, int B, int H, int W, int cout, void* stream);
+
 /* dw = dL/dw ([cout][cin][k][k], overwritten), a sum over all B*Ho*Wo output pixels split into chunks whose partials live in ws
  * and are added in chunk order.  The workspace size query takes the full cin (cin_up does not change it); 0 on a bad shape. */
 size_t yv3_train_conv_wgrad_workspace_bytes(int B, int H, int W, int cin, int cout, int k, int stride);
@@ -603,6 +614,10 @@ int yv3_train_conv_fwd_bf16(const void* x, const void* x2, const void* wf, const
 /* dx (+)= dL/dx for the bf16 dz ([B][Ho][Wo][coutp]); dx fp32 [B][H][W][cin]. */
 int yv3_train_conv_dgrad_bf16(const void* dz, const void* wd, float* dx, int B, int H, int W, int cin, int cout, int k, int stride,
                               int accumulate, void* stream);
+
+/* The same for the bf16 dz copy ([B][H][W][coutp], coutp = cout rounded up to 8); w is rounded to bf16 inside, RNE as
+ * yv3_train_to_bf16 rounds; products accumulate in fp32. */
+int yv3_train_conv0_dgrad_bf16(const void* dz, const float* w, float* dx_nchw, int B, int H, int W, int cout, void* stream);
 
 /* dw = dL/dw (fp32 [cout][cin][k][k]) from bf16 x and dz ([B][Ho][Wo][coutp]); fp32 split partials summed in split order in fp64. */
 size_t yv3_train_conv_wgrad_bf16_workspace_bytes(int B, int H, int W, int cin, int cout, int k, int stride);

@@ -4,7 +4,12 @@ in fp32 (F.conv2d / F.batch_norm on MIOpen, tests/train_ref.forward) and, with b
 torch.autocast("cuda", torch.bfloat16), all in the same process.  7 interleaved rounds, median reported; then one profiled step of
 each of ours split by kernel class (conv classes also in TFLOP/s of the products they compute).
 
-    python tools/train_bench.py [--batches 8 16] [--rounds 7] [--math f32 bf16]
+--input-grad instead times our step with net.input_grad off and on (x.requires_grad), interleaved in the same way, and the layer-0
+input-gradient kernel alone (yv3_train_conv0_dgrad[_bf16]) beside layer 0's wgrad launch, which reads the same dz: device events
+around 50 launches that rotate over enough dz buffers to exceed the 256 MiB Infinity Cache, and the rate over the bytes the kernel
+must move (dz read once, dx written).
+
+    python tools/train_bench.py [--batches 8 16] [--rounds 7] [--math f32 bf16] [--input-grad]
 """
 import argparse
 import json
@@ -21,7 +26,7 @@ sys.path.insert(0, REPO)
 from tests import train_ref as T                      # noqa: E402
 from tests import yolo_loss_ref as R                  # noqa: E402
 from tests.helpers import trained_like_stream         # noqa: E402
-from yolo_v3_amd import YoloNet, WeightManager, synth, arch, F32, BF16  # noqa: E402
+from yolo_v3_amd import YoloNet, WeightManager, synth, arch, _ffi, F32, BF16  # noqa: E402
 
 DEV = "cuda:0"
 
@@ -42,7 +47,7 @@ def kernel_classes(fn):
     cls = {}
     for ev in prof.key_averages():
         n = ev.key
-        k = ("conv fwd" if "conv_gemm<0>" in n or "conv_bf16<0," in n else "conv dgrad" if "conv_gemm<1>" in n or "conv_bf16<1," in n
+        k = ("input dgrad" if "conv0_dgrad" in n else "conv fwd" if "conv_gemm<0>" in n or "conv_bf16<0," in n else "conv dgrad" if "conv_gemm<1>" in n or "conv_bf16<1," in n
              else "conv wgrad" if "conv_gemm<2>" in n or "conv_bf16<2," in n or "wgrad_reduce" in n
              else "cast" if "to_bf16" in n else "weight pack" if "pack_weight" in n
              else "BN / act" if any(s in n for s in ("channel_partials", "finalize", "bn_act", "eval_stats"))
@@ -59,16 +64,86 @@ def step_gflop(B, size=416):
     return tot / 1e9
 
 
+def event_ms(launch, n_buffers, reps=50):
+    """Mean device time of launch(i % n_buffers) over `reps` launches (after one warm-up pass over the buffers)."""
+    for i in range(n_buffers):
+        launch(i)
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for i in range(reps):
+        launch(i % n_buffers)
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def conv0_dgrad_alone(B, math, size=416, cout=32):
+    """The input-gradient kernel and layer 0's wgrad on [B, size, size, cout] dz -> dict of times and the dgrad's rate."""
+    lib, s = _ffi.lib(), _ffi.stream_ptr()
+    bf = math == BF16
+    dz_bytes = B * size * size * cout * (2 if bf else 4)
+    dx_bytes = B * 3 * size * size * 4
+    nbuf = max(2, -(-600 * 2 ** 20 // dz_bytes))
+    g = torch.Generator(device=DEV).manual_seed(1)
+    dzs = [torch.randn(B, size, size, cout, device=DEV, generator=g).to(torch.bfloat16 if bf else torch.float32) for _ in range(nbuf)]
+    x = torch.randn(B, 3, size, size, device=DEV, generator=g)
+    xin = x.to(torch.bfloat16) if bf else x
+    w = torch.randn(cout, 3, 3, 3, device=DEV, generator=g) / 27 ** 0.5
+    dx, dw = torch.empty_like(x), torch.empty_like(w)
+    dgrad = lib.yv3_train_conv0_dgrad_bf16 if bf else lib.yv3_train_conv0_dgrad
+    wgrad = lib.yv3_train_conv_wgrad_bf16 if bf else lib.yv3_train_conv_wgrad
+    nw = (lib.yv3_train_conv_wgrad_bf16_workspace_bytes if bf else lib.yv3_train_conv_wgrad_workspace_bytes)(B, size, size, 3, cout, 3, 1)
+    ws = torch.empty(nw, device=DEV, dtype=torch.uint8)
+    t_d = event_ms(lambda i: _ffi.check(dgrad(dzs[i].data_ptr(), w.data_ptr(), dx.data_ptr(), B, size, size, cout, s)), nbuf)
+    t_w = event_ms(lambda i: _ffi.check(wgrad(xin.data_ptr(), None, dzs[i].data_ptr(), dw.data_ptr(), B, size, size, 3, 0, cout, 3, 1, 1,
+                                              ws.data_ptr(), nw, s)), nbuf)
+    return {"conv0_dgrad_ms": round(t_d, 4), "conv0_dgrad_bytes": dz_bytes + dx_bytes,
+            "conv0_dgrad_TBps": round((dz_bytes + dx_bytes) / t_d / 1e9, 3), "layer0_wgrad_ms": round(t_w, 4), "dz_buffers": nbuf}
+
+
+def input_grad_cost(net, a):
+    """--input-grad: the step with net.input_grad off / on, interleaved, and the new kernel alone."""
+    out = {}
+    net.input_grad = True
+    for B in a.batches:
+        x = torch.from_numpy(synth.images(B, 416, 7)).to(DEV)
+        tg = torch.from_numpy(R.random_rows(5, B, 30, 80, (0.03, 0.8)))
+        out[B] = {}
+        for m in a.math:
+            def step(want_x, math={"f32": F32, "bf16": BF16}[m]):
+                net.backprop_math = math
+                net.zero_grad(set_to_none=True)
+                xin = x.clone().requires_grad_(True) if want_x else x
+                net(xin, tg).backward()
+            fns = {"off_ms": lambda: step(False), "on_ms": lambda: step(True)}
+            for f in fns.values():
+                f()
+            times = {k: [] for k in fns}
+            for _ in range(a.rounds):
+                for k, f in fns.items():
+                    times[k].append(timed(f))
+            r = {k: round(float(np.median(v)), 3) for k, v in times.items()}
+            r["spread_ms"] = {k: [round(min(v), 3), round(max(v), 3)] for k, v in times.items()}
+            r.update(conv0_dgrad_alone(B, {"f32": F32, "bf16": BF16}[m]))
+            out[B][m] = r
+            print(B, m, json.dumps(r), flush=True)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[8, 16])
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--math", nargs="+", choices=("f32", "bf16"), default=["f32"])
+    ap.add_argument("--input-grad", action="store_true", help="time the step with net.input_grad off and on, and the layer-0 dgrad alone")
     a = ap.parse_args()
     net = YoloNet((416, 416), numClass=80)
     WeightManager(net).load_stream(trained_like_stream(80))
     net = net.to(DEV).train()
     net.backprop = True
+    if a.input_grad:
+        return input_grad_cost(net, a)
     sd_gpu = {k: v.detach().clone() for k, v in net.state_dict().items()}
     out = {}
     for B in a.batches:

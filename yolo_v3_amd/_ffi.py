@@ -117,6 +117,8 @@ _SIGNATURES = {
                            c_int, c_int, c_int, c_int, c_void_p]),
     "yv3_decode_nchw": (c_int, [c_void_p, ctypes.POINTER(c_float), c_float, c_void_p, c_longlong,
                                 c_int, c_int, c_int, c_int, c_void_p]),
+    "yv3_decode_bwd_nchw": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_float), c_float, c_void_p,
+                                    c_int, c_int, c_int, c_int, c_void_p]),
     "yv3_cxcywh_to_xyxy": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p]),
     "yv3_iou_matrix": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "yv3_letterbox": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
@@ -141,6 +143,7 @@ _SIGNATURES = {
     "yv3_train_pack_weight": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "yv3_train_conv_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
     "yv3_train_conv_dgrad": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 8 + [c_void_p]),
+    "yv3_train_conv0_dgrad": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "yv3_train_conv_wgrad_workspace_bytes": (c_size_t, [c_int] * 7),
     "yv3_train_conv_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_size_t, c_void_p]),
     "yv3_train_channel_workspace_bytes": (c_size_t, [c_longlong, c_int]),
@@ -155,6 +158,7 @@ _SIGNATURES = {
     "yv3_train_pack_weight_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "yv3_train_conv_fwd_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
     "yv3_train_conv_dgrad_bf16": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 8 + [c_void_p]),
+    "yv3_train_conv0_dgrad_bf16": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "yv3_train_conv_wgrad_bf16_workspace_bytes": (c_size_t, [c_int] * 7),
     "yv3_train_conv_wgrad_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_size_t, c_void_p]),
 }

@@ -16,7 +16,16 @@ BF16 uses their ``_bf16`` counterparts and keeps a bf16 copy (yv3_train_to_bf16)
 One ``torch.autograd.Function`` covers the whole network: it takes the input and the parameters (``net.parameters()`` order, i.e.
 ``state_dict`` order without the buffers) and keeps z, y and the statistics of every layer for the backward.  Backward stops at the
 first layer whose inputs need no gradient, e.g. at the backbone/head boundary when the backbone is frozen.  In ``.train()``
-the running statistics move as nn.BatchNorm2d moves them (momentum, unbiased variance, ``num_batches_tracked``)."""
+the running statistics move as nn.BatchNorm2d moves them (momentum, unbiased variance, ``num_batches_tracked``).
+
+Two Functions share that forward (``net_forward``) and that reverse walk (``walk``).  ``_TrainStep`` is ``net(x, target)``: the loss
+comes out, and the walk starts from the loss kernel's dL/dlogits scaled by dL/dloss.  ``_Logits`` is ``net.logits(x)``: the three
+heads' logits come out as NCHW views, and the walk starts from whatever gradients autograd hands back for them, so any loss written
+in torch on the logits (``net.yoloK(lgK, img_dim, target)`` included) trains the net.
+
+The input gradient is opt-in (``net.input_grad = True``; an ``x`` that requires grad raises NotImplementedError otherwise).  The
+walk then runs down to layer 0, whose dgrad (yv3_train_conv0_dgrad) writes dL/dx in x's own NCHW layout, and ``x`` is a real input
+of the Function."""
 import numbers
 
 import torch
@@ -104,8 +113,8 @@ def _bf16(lib, s, t, rows, C, ld, what):
 class _Run:
     """Forward state of one training step: what the backward needs."""
 
-    def __init__(self, net, x, target, math=_ffi.F32):
-        self.net, self.x, self.target, self.math = net, x, target, math
+    def __init__(self, net, x, target, math=_ffi.F32, input_grad=False):
+        self.net, self.x, self.target, self.math, self.input_grad = net, x, target, math, bool(input_grad)
         self.ops = graph(net)
         self.saved = {}            # op index -> dict of tensors
         self.shape = {}            # buffer -> (B, H, W, C)
@@ -122,8 +131,9 @@ def _ws(nbytes, dev):
     return torch.empty(nbytes, device=dev, dtype=torch.uint8)
 
 
-def forward(run, want_grad):
-    """The training forward of the whole net, the loss and dL/dlogits; returns the loss (fp32 0-d GPU tensor) and sets net.stats."""
+def net_forward(run, want_grad):
+    """The training forward of the whole net up to the heads -> their logits [(fp32 NHWC tensor, h, w)] * 3; with want_grad the
+    run keeps what the walk needs."""
     lib, s = _ffi.lib(), _ffi.stream_ptr()
     net, x = run.net, run.x
     B, _, H, W = x.shape
@@ -132,7 +142,7 @@ def forward(run, want_grad):
     bf = run.math == _ffi.BF16
     bufs_b = {"x": _bf16(lib, s, x, x.numel(), 1, 1, "x")} if bf else None      # bf16 copies of the conv inputs (BF16)
     run.shape["x"] = (B, H, W, 3)
-    run.need["x"] = False
+    run.need["x"] = run.input_grad
     logits = [None] * 3
     for i, op in enumerate(run.ops):
         c = op.conv
@@ -207,6 +217,14 @@ def forward(run, want_grad):
     if want_grad:
         run.bufs = bufs
         run.bufs_b = bufs_b
+    return logits
+
+
+def forward(run, want_grad):
+    """The training forward of the whole net, the loss and dL/dlogits; returns the loss (fp32 0-d GPU tensor) and sets net.stats."""
+    net, x = run.net, run.x
+    B, H, dev = x.shape[0], x.shape[2], x.device
+    logits = net_forward(run, want_grad)
     # the loss of the three heads (as YoloNet._loss), with dL/dlogits when a backward will follow
     heads = (net.yolo1, net.yolo2, net.yolo3)
     t = _yl.loss_target(run.target, B, dev)
@@ -221,13 +239,14 @@ def forward(run, want_grad):
     return net._loss_from_device(out, B, dev)
 
 
-def backward(run, grad_output):
-    """dL/dparameter for every parameter that requires grad, as {id(param): tensor}, for dL/dloss = grad_output."""
+def walk(run, dlogits, scale=None):
+    """The reverse walk from the heads: dlogits[k] = dL/dlogits of head k (contiguous NHWC fp32, or None: that head got no gradient),
+    times the fp32 0-d GPU tensor `scale` when one is given.  -> ({id(param): dL/dparam}, dL/dx [B,3,H,W] fp32 or None); the
+    latter when run.need["x"]."""
     lib, s = _ffi.lib(), _ffi.stream_ptr()
     dev = run.x.device
     bf = run.math == _ffi.BF16
-    g = grad_output.detach().to(device=dev, dtype=torch.float32).reshape(()).contiguous()
-    grads = {}                 # buffer -> dL/dbuffer (NHWC fp32)
+    grads = {}                 # buffer -> dL/dbuffer (NHWC fp32; "x": NCHW)
     pg = {}
     trace = run.trace
 
@@ -246,7 +265,8 @@ def backward(run, grad_output):
 
     head_ops = {op.head_idx: op for op in run.ops if op.head}
     for kk in range(3):
-        grads[head_ops[kk].out] = run.dlogits[kk]
+        if dlogits[kk] is not None:
+            grads[head_ops[kk].out] = dlogits[kk]
     for i in range(len(run.ops) - 1, -1, -1):
         op, sv = run.ops[i], run.saved[i]
         dy = grads.pop(op.out, None)
@@ -262,8 +282,8 @@ def backward(run, grad_output):
         c = op.conv
         if op.head:
             db = torch.empty(cout, device=dev, dtype=torch.float32)
-            _ffi.check(lib.yv3_train_bias_bwd(dy.data_ptr(), g.data_ptr(), dz.data_ptr(), db.data_ptr(), P, cout, ws.data_ptr(), nb, s),
-                       "yv3_train_bias_bwd")
+            _ffi.check(lib.yv3_train_bias_bwd(dy.data_ptr(), scale.data_ptr() if scale is not None else None, dz.data_ptr(),
+                                              db.data_ptr(), P, cout, ws.data_ptr(), nb, s), "yv3_train_bias_bwd")
             pg[id(c.bias)] = db
             rec(i, dz=dz, dbias=db)
         else:
@@ -300,6 +320,18 @@ def backward(run, grad_output):
             rec(i, dw=dw)
         if not (need_src or need_src2):
             continue
+        if op.src == "x":                  # layer 0: dL/dx in the caller's NCHW layout, from the parameter itself
+            dx = torch.empty((b_, cin, h, w), device=dev, dtype=torch.float32)
+            wt = _f32(c.weight, "weight of " + op.out)
+            if bf:
+                _ffi.check(lib.yv3_train_conv0_dgrad_bf16(dzb.data_ptr(), wt.data_ptr(), dx.data_ptr(), b_, h, w, cout, s),
+                           "yv3_train_conv0_dgrad_bf16")
+            else:
+                _ffi.check(lib.yv3_train_conv0_dgrad(dz.data_ptr(), wt.data_ptr(), dx.data_ptr(), b_, h, w, cout, s),
+                           "yv3_train_conv0_dgrad")
+            grads["x"] = dx
+            rec(i, dx_after=dx)
+            continue
 
         def dgrad(dx, acc):
             if bf:
@@ -335,7 +367,28 @@ def backward(run, grad_output):
                                                dtail.data_ptr() if dtail is not None else None, b_, h, w, op.cin_up, ct,
                                                acc_low, acc_tail, s), "yv3_train_upcat_bwd")
             rec(i, dlow_after=dlow, dtail_after=dtail)
-    return pg
+    return pg, grads.get("x")
+
+
+def loss_walk(run, grad_output):
+    """walk() from the loss kernel's dL/dlogits (forward(run, want_grad=True)) for dL/dloss = grad_output."""
+    g = grad_output.detach().to(device=run.x.device, dtype=torch.float32).reshape(()).contiguous()
+    return walk(run, run.dlogits, g)
+
+
+def backward(run, grad_output):
+    """dL/dparameter for every parameter that requires grad, as {id(param): tensor}, for dL/dloss = grad_output."""
+    return loss_walk(run, grad_output)[0]
+
+
+def _input_grads(ctx, x, params, pg, dx):
+    """The backward's return values for (run, x, *params)."""
+    out = []
+    for i, p in enumerate(params):
+        gp = pg.get(id(p)) if ctx.needs_input_grad[2 + i] else None
+        out.append(gp.view_as(p) if gp is not None else None)
+    gx = dx.to(x.dtype) if dx is not None and ctx.needs_input_grad[1] else None
+    return (None, gx) + tuple(out)
 
 
 class _TrainStep(torch.autograd.Function):
@@ -345,40 +398,82 @@ class _TrainStep(torch.autograd.Function):
     def forward(ctx, run, x, *params):
         loss = forward(run, want_grad=True)
         ctx.run = run
-        ctx.save_for_backward(*params)         # (an in-place change of a parameter before backward() then raises, as in torch)
+        ctx.save_for_backward(x, *params)      # (an in-place change of a parameter before backward() then raises, as in torch)
         return loss
 
     @staticmethod
     def backward(ctx, grad_output):
-        params = ctx.saved_tensors
+        x, params = ctx.saved_tensors[0], ctx.saved_tensors[1:]
         run = ctx.run
         ctx.run = None
         with torch.cuda.device(run.x.device):
-            pg = backward(run, grad_output)
-        out = []
-        for i, p in enumerate(params):
-            gp = pg.get(id(p)) if ctx.needs_input_grad[2 + i] else None
-            out.append(gp.view_as(p) if gp is not None else None)
-        return (None, None) + tuple(out)
+            pg, dx = loss_walk(run, grad_output)
+        return _input_grads(ctx, x, params, pg, dx)
 
 
-def loss(net, x, target):
-    """net(x, target) with net.backprop = True (see the module docstring)."""
+class _Logits(torch.autograd.Function):
+    """(lg1, lg2, lg3) = the heads' logits of YoloNet(x) in training form, as NCHW views; backward walks the net from the gradients
+    autograd hands back for them (any strides; a head that got none counts as zero)."""
+
+    @staticmethod
+    def forward(ctx, run, x, *params):
+        logits = net_forward(run, want_grad=True)
+        ctx.run = run
+        ctx.save_for_backward(x, *params)
+        ctx.set_materialize_grads(False)
+        return tuple(z.permute(0, 3, 1, 2) for z, _, _ in logits)
+
+    @staticmethod
+    def backward(ctx, *grad_logits):
+        x, params = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        run = ctx.run
+        ctx.run = None
+        dev = run.x.device
+        with torch.cuda.device(dev):
+            dl = [None if g is None else g.detach().to(device=dev, dtype=torch.float32).permute(0, 2, 3, 1).contiguous()
+                  for g in grad_logits]
+            pg, dx = walk(run, dl)
+        return _input_grads(ctx, x, params, pg, dx)
+
+
+def _start(net, x, target):
+    """The checks of the training path -> (the Function's x argument, the run, the parameters, differentiable?)."""
     math = backprop_math(net)
     if not x.is_cuda:
         raise _ffi.GpuOnlyError("input images must live on the GPU: this package runs only on MI355X (HIP kernels), "
                                 "there is no CPU path")
-    if x.requires_grad:
-        raise NotImplementedError("the training path does not compute the input gradient: pass x without requires_grad")
+    input_grad = bool(getattr(net, "input_grad", False))
+    if x.requires_grad and not input_grad:
+        raise NotImplementedError("the training path computes the input gradient only with net.input_grad = True: set it, or pass "
+                                  "x without requires_grad")
     if x.dim() != 4 or x.shape[1] != 3:
         raise _ffi.Yv3Error("input must be [B, 3, H, W], got %s" % (tuple(x.shape),))
     if x.shape[2] % 32 or x.shape[3] % 32:
         raise _ffi.Yv3Error("input height and width must be multiples of 32, got %dx%d" % (x.shape[2], x.shape[3]))
-    x = x.detach().float().contiguous()
     params = list(net.parameters())
-    with torch.cuda.device(x.device):
-        run = _Run(net, x, target, math)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+    want_x = x.requires_grad and torch.is_grad_enabled()
+    run = _Run(net, x.detach().float().contiguous(), target, math, input_grad=want_x)
+    diff = torch.is_grad_enabled() and (want_x or any(p.requires_grad for p in params))
+    return (x if want_x else run.x), run, params, diff
+
+
+def loss(net, x, target):
+    """net(x, target) with net.backprop = True (see the module docstring)."""
+    x, run, params, diff = _start(net, x, target)
+    with torch.cuda.device(run.x.device):
+        if diff:
             return _TrainStep.apply(run, x, *params)
         with torch.no_grad():
             return forward(run, want_grad=False)
+
+
+def logits(net, x):
+    """net.logits(x): the three heads' logits (lg1, lg2, lg3), each [B, 3*(5+C), h, w] (NCHW views of the fp32 NHWC buffers), from
+    the training forward -- BatchNorm in the module's mode, arithmetic by net.backprop_math -- differentiable in the parameters and,
+    with net.input_grad, in x (see the module docstring).  Under torch.no_grad(), or when nothing requires grad, forward only."""
+    x, run, params, diff = _start(net, x, None)
+    with torch.cuda.device(run.x.device):
+        if diff:
+            return _Logits.apply(run, x, *params)
+        with torch.no_grad():
+            return tuple(z.permute(0, 3, 1, 2) for z, _, _ in net_forward(run, want_grad=False))

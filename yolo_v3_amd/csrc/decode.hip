@@ -53,6 +53,30 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs a) {
     }
 }
 
+// Backward of decode_kernel<true>: dlogits[ca][pix] = dout[pix][ca] * d(decoded value)/d(logit), the derivative recomputed from the
+// logit by the forward's own yv3_decode_value: the decoded w / h itself for tw / th (e^t is its own derivative), s (1 - s) for conf and the
+// classes, stride s (1 - s) for tx / ty (s = sigmoid(t), taken as the forward's value of a conf attribute).
+__global__ __launch_bounds__(256) void decode_bwd_kernel(const DecodeArgs a, const float* __restrict__ dout, float* __restrict__ dlogits) {
+    const int b = blockIdx.y;
+    const int HW = a.H * a.W;
+    const int ch = 3 * a.attrib;
+    const float* src = a.logits + (long long)b * HW * ch;
+    const float* dsrc = dout + (long long)b * HW * ch;
+    float* dst = dlogits + (long long)b * HW * ch;
+    for (int ca = threadIdx.x; ca < ch; ca += 256) {
+        const int anc = (ca >= a.attrib) + (ca >= 2 * a.attrib);
+        const int attr = ca - anc * a.attrib;
+        const float an = attr == 2 ? a.aw[anc] : a.ah[anc];
+        const bool wh = attr == 2 || attr == 3;
+        for (int pix = blockIdx.x; pix < HW; pix += gridDim.x) {
+            const float v = yv3_decode_value(src[(long long)ca * HW + pix], attr < 2 ? 4 : attr, an, 0.f, 0.f, a.stride);
+            const float sd = v * (1.f - v);
+            const float d = wh ? v : (attr < 2 ? a.stride * sd : sd);
+            dst[(long long)ca * HW + pix] = dsrc[(long long)pix * ch + ca] * d;
+        }
+    }
+}
+
 int run(const float* logits, int ld, const float* anchors, float stride, float* out, long long obs,
         int B, int H, int W, int C, bool nchw, void* stream) {
     if (!logits || !anchors || !out || B <= 0 || H <= 0 || W <= 0 || C < 0 || stride <= 0.f) return YV3_EINVAL;
@@ -79,4 +103,19 @@ extern "C" int yv3_decode(const float* logits, int ld_logits, const float* ancho
 extern "C" int yv3_decode_nchw(const float* logits_nchw, const float* anchors_host, float stride,
                                float* out, long long out_batch_stride, int B, int H, int W, int num_class, void* stream) {
     return run(logits_nchw, 0, anchors_host, stride, out, out_batch_stride, B, H, W, num_class, true, stream);
+}
+
+extern "C" int yv3_decode_bwd_nchw(const float* logits_nchw, const float* dout, const float* anchors_host, float stride,
+                                   float* dlogits_nchw, int B, int H, int W, int num_class, void* stream) {
+    if (!logits_nchw || !dout || !anchors_host || !dlogits_nchw || B <= 0 || H <= 0 || W <= 0 || num_class < 0 || stride <= 0.f)
+        return YV3_EINVAL;
+    if (B > 65535) return YV3_ESHAPE;
+    DecodeArgs a = {};
+    a.logits = logits_nchw; a.H = H; a.W = W; a.attrib = 5 + num_class; a.stride = stride;
+    for (int i = 0; i < 3; ++i) { a.aw[i] = anchors_host[2 * i] / stride; a.ah[i] = anchors_host[2 * i + 1] / stride; }
+    const long long hw = (long long)H * W;
+    const dim3 grid((unsigned)(hw < 4096 ? hw : 4096), (unsigned)B);
+    hipLaunchKernelGGL(decode_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, dout, dlogits_nchw);
+    YV3_CHECK_LAUNCH();
+    return 0;
 }

@@ -12,6 +12,7 @@
 // Determinism: no atomics.  Every sum runs in a fixed order (the MFMA k-chain, then the wgrad split partials and the per-channel
 // partials summed in index order in fp64), so identical inputs give identical bits.
 #include "yv3_common.h"
+#include "train_conv0_dgrad.h"
 
 namespace {
 
@@ -449,6 +450,12 @@ int yv3_train_conv_dgrad(const float* dz, const float* wd, float* dx, int B, int
     hipLaunchKernelGGL(conv_gemm<DGRAD>, grid, dim3(NT), 0, (hipStream_t)stream, g);
     YV3_CHECK_LAUNCH();
     return 0;
+}
+
+int yv3_train_conv0_dgrad(const float* dz, const float* w, float* dx_nchw, int B, int H, int W, int cout, void* stream) {
+    if (!dz || !w || !dx_nchw || B <= 0 || H <= 0 || W <= 0 || cout <= 0) return YV3_EINVAL;
+    if (cout & 3) return YV3_ESHAPE;                                   // (16-byte loads of dz)
+    return conv0dg::launch<false>(dz, w, dx_nchw, B, H, W, cout, cout, (hipStream_t)stream);
 }
 
 size_t yv3_train_conv_wgrad_workspace_bytes(int B, int H, int W, int cin, int cout, int k, int stride) {

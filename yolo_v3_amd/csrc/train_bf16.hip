@@ -27,6 +27,7 @@
 //
 // Determinism: no atomics.  The MFMA k-chain runs in a fixed order, and the wgrad split partials are summed in split order in fp64.
 #include "yv3_common.h"
+#include "train_conv0_dgrad.h"
 
 namespace {
 
@@ -425,6 +426,11 @@ int yv3_train_conv_dgrad_bf16(const void* dz, const void* wd, float* dx, int B, 
     g.dz = (const u16*)dz; g.wp = (const u16*)wd; g.out = dx; g.accumulate = accumulate;
     g.M = (long long)B * H * W; g.N = cin; g.K = (long long)k * k * g.coutp;
     return launch_conv<DGRAD, true>(g, 1, (hipStream_t)stream);
+}
+
+int yv3_train_conv0_dgrad_bf16(const void* dz, const float* w, float* dx_nchw, int B, int H, int W, int cout, void* stream) {
+    if (!dz || !w || !dx_nchw || B <= 0 || H <= 0 || W <= 0 || cout <= 0) return YV3_EINVAL;
+    return conv0dg::launch<true>(dz, w, dx_nchw, B, H, W, cout, round8(cout), (hipStream_t)stream);
 }
 
 size_t yv3_train_conv_wgrad_bf16_workspace_bytes(int B, int H, int W, int cin, int cout, int k, int stride) {

@@ -285,6 +285,9 @@ class YoloNet(nn.Module):
         self.backprop = False
         # arithmetic of the training step's convolutions: F32 (exact fp32) or BF16 (bf16 operands, fp32 accumulation)
         self.backprop_math = _ffi.F32
+        # True: the training path (net(x, target) with backprop, net.logits(x)) also fills x.grad when x requires grad; False: such
+        # an x raises NotImplementedError
+        self.input_grad = False
 
     # ---- HIP execution
     def engine(self, dtype=None):
@@ -344,6 +347,13 @@ class YoloNet(nn.Module):
         (channels_last strides) of copies the caller owns.  Computed by the same plan as ``forward(x, target)``."""
         _, plan = self.engine().forward(x, logits=True)
         return tuple(lg.clone().permute(0, 3, 1, 2) for lg, _, _ in plan.logits)
+
+    def logits(self, x):
+        """The three heads' raw logits ``(lg1, lg2, lg3)``, each ``[B, 3*(5+C), h, w]``, from the *training* forward
+        (yolo_v3_amd.backprop.logits): BatchNorm in the module's mode (``.train()`` moves the running statistics once per call),
+        arithmetic by ``self.backprop_math``, whatever ``self.backprop`` says.  Differentiable in every parameter and, with
+        ``self.input_grad = True``, in ``x``: write any loss on them, or feed them to ``self.yoloK(lgK, self.img_dim, target)``."""
+        return _backprop.logits(self, x)
 
     def _loss(self, x, target):
         """forward(x, target): the reference's summed loss of the three heads (darknet.py:225-229) and ``self.stats``."""

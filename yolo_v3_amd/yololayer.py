@@ -4,7 +4,8 @@
 layout, channel = anchor*(5+C)+attr, yololayer.py:42) into ``[B, H*W*3, 5+C]`` rows
 ``cx, cy, w, h, conf, cls...`` in input pixels (yololayer.py:45-59,98-104) with ONE fused HIP
 kernel (``yv3_decode_nchw``); the reference does the box part on the CPU and crosses the
-GPU<->CPU boundary twice (yololayer.py:58-59,98).  Inside ``YoloNet`` the NHWC variant
+GPU<->CPU boundary twice (yololayer.py:58-59,98).  When ``x`` requires grad the decode is differentiable: the same
+kernel forward, ``yv3_decode_bwd_nchw`` backward.  Inside ``YoloNet`` the NHWC variant
 (``yv3_decode``) is used directly on the head conv's output, with no permute at all.
 
 ``YoloLayer.forward(x, img_dim, target)`` is the reference's training branch (yololayer.py:64-95,
@@ -114,6 +115,28 @@ class _YoloLossFn(torch.autograd.Function):
         return (grad_output * grad).to(ctx.x_dtype), None, None, None, None, None
 
 
+class _DecodeFn(torch.autograd.Function):
+    """out = decode(x) (yv3_decode_nchw) with yv3_decode_bwd_nchw as its backward; x: contiguous fp32 logits."""
+
+    @staticmethod
+    def forward(ctx, x, layer, stride, anchors):
+        ctx.save_for_backward(x)
+        ctx.layer, ctx.stride, ctx.anchors = layer, stride, anchors
+        return layer._decode(x, stride, anchors)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, = ctx.saved_tensors
+        nB, _, nH, nW = x.shape
+        dout = dout.detach().to(device=x.device, dtype=torch.float32).contiguous()
+        dx = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _ffi.check(_ffi.lib().yv3_decode_bwd_nchw(x.data_ptr(), dout.data_ptr(), (ctypes.c_float * 6)(*ctx.anchors), ctx.stride,
+                                                      dx.data_ptr(), nB, nH, nW, ctx.layer.numClass, _ffi.stream_ptr()),
+                       "yv3_decode_bwd_nchw")
+        return dx, None, None, None
+
+
 class YoloLayer(nn.Module):
     def __init__(self, anchors_all, anchors_mask, img_dim, numClass):
         super().__init__()
@@ -161,14 +184,20 @@ class YoloLayer(nn.Module):
         nA = len(self.anchors_mask)
         if nA != 3 or ch != nA * self.bbox_attrib:
             raise _ffi.Yv3Error("expected %d channels (3 anchors x %d), got %d" % (3 * self.bbox_attrib, self.bbox_attrib, ch))
-        x = x.float().contiguous()
         stride = img_dim[1] / nH                                            # yololayer.py:36
         flat = []
         for m in self.anchors_mask:
             flat += [float(self.anchors_all[m][0]), float(self.anchors_all[m][1])]
-        out = torch.empty((nB, nA * nH * nW, self.bbox_attrib), device=x.device, dtype=torch.float32)
+        if x.requires_grad and torch.is_grad_enabled():                     # (x.float().contiguous() stays in autograd's graph)
+            return _DecodeFn.apply(x.float().contiguous(), self, stride, flat)
+        return self._decode(x.float().contiguous(), stride, flat)
+
+    def _decode(self, x, stride, anchors):
+        """yv3_decode_nchw on contiguous fp32 logits."""
+        nB, _, nH, nW = x.shape
+        out = torch.empty((nB, 3 * nH * nW, self.bbox_attrib), device=x.device, dtype=torch.float32)
         with torch.cuda.device(x.device):
-            _ffi.check(_ffi.lib().yv3_decode_nchw(x.data_ptr(), (ctypes.c_float * 6)(*flat), stride, out.data_ptr(),
+            _ffi.check(_ffi.lib().yv3_decode_nchw(x.data_ptr(), (ctypes.c_float * 6)(*anchors), stride, out.data_ptr(),
                                                   out.shape[1] * out.shape[2], nB, nH, nW, self.numClass,
                                                   _ffi.stream_ptr()), "yv3_decode_nchw")
         return out
