@@ -417,6 +417,15 @@ int yv3_augment_images(const unsigned char* src, long long src_bytes, const long
                        const double* params, int B, float* out, int out_h, int out_w,
                        void* workspace, size_t workspace_bytes, int* status, void* stream);
 
+/* As yv3_augment_images, with the sources gathered from a larger allocation: image b is read at src + src_offsets[b] (checked
+ * against src_bytes) and its colour copy lives at workspace + ws_offsets[b] (checked against ws_span <= workspace_bytes).  The
+ * same source may occur more than once in a batch; the ws ranges of a batch must not overlap (the caller's duty).  src is not
+ * written.  status[b] = YV3_EINVAL for either range out of bounds, outputs zeros, as today.  All offsets are int64 bytes and need
+ * no alignment; the workspace a batch needs is its own images' bytes, whatever the size of the allocation they are read from. */
+int yv3_augment_images_from(const unsigned char* src, long long src_bytes, const long long* src_offsets,
+                            const long long* ws_offsets, long long ws_span, const int* hw, const double* params, int B,
+                            float* out, int out_h, int out_w, void* workspace, size_t workspace_bytes, int* status, void* stream);
+
 /* Labels, one launch, float64 arithmetic.  labels [B][T][5] float64 rows (cls, cx, cy, w, h) relative to the source (NULL when
  * T == 0); rows with w or h <= 0 (zero padding among them) are dropped, as label_np_to_bbs drops them.  target: fp32
  * [B][max_rows][5], the first max_rows kept rows (cls, cx, cy, w, h relative to out_w x out_h) in input order, zero-filled. */

@@ -19,6 +19,6 @@ from .utils import (postprocessing, iou_vectorized, bbox_iou, PostProcessor, let
 from .boundingbox import bbox_cxcywh_to_x1y1x2y2, correct_yolo_boxes, letterbox_reverse, rescale_bbox   # noqa: F401
 from .detect import detect, Detector, predict  # noqa: F401
 from .dist import detect_sharded                # noqa: F401
-from .augment import sample_params, augment_batch, TrainBatches   # noqa: F401
+from .augment import sample_params, augment_batch, TrainBatches, epoch_schedule   # noqa: F401
 
 __version__ = "0.1.0"

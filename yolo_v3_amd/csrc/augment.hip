@@ -3,7 +3,8 @@
 // for a whole batch of packed uint8 RGB sources of any sizes, with the per-image random draws given as parameters
 // [B][8] float64 = dhue, dsat, dexp, top, right, bottom, left, flip (yolo_v3_amd/augment.py samples them):
 //   hsv_kernel       step 1, iaa_hsv_aug: OpenCV 8-bit RGB2HSV (integer path), h + dhue, s * dsat, v * dexp, 8-bit HSV2RGB ->
-//                    the caller's workspace, at the sources' own byte offsets
+//                    the caller's workspace, image b read at src + src_offsets[b] and written at ws + ws_offsets[b] (the packed
+//                    entry point passes one array for both; the gathering one reads a resident arena and writes compactly)
 //   resample_kernel  steps 2-4: CropAndPad (pad 128, after the colour step), Fliplr, IaaLetterbox (cv2 INTER_CUBIC fixed point,
 //                    replicated border at the edges of the cropped / padded / flipped intermediate, which is never materialised),
 //                    128 canvas, /255, fp32 CHW straight into the [B,3,h,w] network input
@@ -52,9 +53,16 @@ __device__ inline int aug_geometry(const double* __restrict__ p, int H, int W, i
 // OpenCV RGB2HSV_b (hsv_shift = 12, hue range 180): sdiv[v] = round((255 << 12) / v), hdiv[d] = round((180 << 12) / (6 d)),
 // entry 0 = 0 (no ties occur for 1..255: cvRound's half-to-even never matters).  HSV2RGB_b: h, s * (1/255.f), v * (1/255.f) as
 // float32, h * (6.f/180) wrapped into [0, 6) (hue bytes 180..255 wrap here, as in the reference), sector table, saturate_cast<uchar>.
+// Image b's source range [off, off + n3) inside src_bytes and its colour copy's range [wo, wo + n3) inside ws_span, in 64 bits.
+__device__ inline bool aug_in_bounds(long long off, long long src_bytes, long long wo, long long ws_span, long long n3) {
+    return off >= 0 && off <= src_bytes && n3 <= src_bytes - off && wo >= 0 && wo <= ws_span && n3 <= ws_span - wo;
+}
+
 __global__ __launch_bounds__(256) void hsv_kernel(const unsigned char* __restrict__ src, long long src_bytes,
-                                                  const long long* __restrict__ offsets, const int* __restrict__ hw,
-                                                  const double* __restrict__ params, int OH, int OW, unsigned char* __restrict__ ws) {
+                                                  const long long* __restrict__ src_offsets,
+                                                  const long long* __restrict__ ws_offsets, long long ws_span,
+                                                  const int* __restrict__ hw, const double* __restrict__ params, int OH, int OW,
+                                                  unsigned char* __restrict__ ws) {
     __shared__ int sdiv[256], hdiv[256];
     const int t = threadIdx.x;
     sdiv[t] = t ? (int)rint(1044480.0 / t) : 0;
@@ -64,11 +72,11 @@ __global__ __launch_bounds__(256) void hsv_kernel(const unsigned char* __restric
     const double* p = params + 8 * (size_t)b;
     AugGeom g;
     if (aug_geometry(p, hw[2 * b], hw[2 * b + 1], OH, OW, g)) return;
-    const long long off = offsets[b], n = (long long)g.H * g.W;
-    if (off < 0 || off > src_bytes || n * 3 > src_bytes - off) return;
+    const long long off = src_offsets[b], wo = ws_offsets[b], n = (long long)g.H * g.W;
+    if (!aug_in_bounds(off, src_bytes, wo, ws_span, n * 3)) return;
     const float dhue = (float)p[0], dsat = (float)p[1], dexp = (float)p[2];
     const unsigned char* s = src + off;
-    unsigned char* d = ws + off;
+    unsigned char* d = ws + wo;
     const float hscale = 6.f / 180.f;
     for (long long i = (long long)blockIdx.x * blockDim.x + t; i < n; i += (long long)gridDim.x * blockDim.x) {
         const int r = s[3 * i], gg = s[3 * i + 1], bb = s[3 * i + 2];
@@ -115,15 +123,16 @@ __global__ __launch_bounds__(256) void hsv_kernel(const unsigned char* __restric
 // One thread per canvas pixel of one image (grid.y = image).  A tap (x, y) of the (H1, W1) intermediate, border-replicated, is
 // source pixel (x' - left, y - top) with x' = flip ? W1 - 1 - x : x, or the 128 pad when that falls outside the source.
 __global__ __launch_bounds__(256) void resample_kernel(const unsigned char* __restrict__ ws, long long src_bytes,
-                                                       const long long* __restrict__ offsets, const int* __restrict__ hw,
-                                                       const double* __restrict__ params, float* __restrict__ out, int OH, int OW,
-                                                       int* __restrict__ status) {
+                                                       const long long* __restrict__ src_offsets,
+                                                       const long long* __restrict__ ws_offsets, long long ws_span,
+                                                       const int* __restrict__ hw, const double* __restrict__ params,
+                                                       float* __restrict__ out, int OH, int OW, int* __restrict__ status) {
     const int b = blockIdx.y;
     const int px = blockIdx.x * blockDim.x + threadIdx.x;
     AugGeom g;
     int code = aug_geometry(params + 8 * (size_t)b, hw[2 * b], hw[2 * b + 1], OH, OW, g);
-    const long long off = offsets[b];
-    if (!code && (off < 0 || off > src_bytes || (long long)g.H * g.W * 3 > src_bytes - off)) code = YV3_EINVAL;
+    const long long wo = ws_offsets[b];
+    if (!code && !aug_in_bounds(src_offsets[b], src_bytes, wo, ws_span, (long long)g.H * g.W * 3)) code = YV3_EINVAL;
     if (blockIdx.x == 0 && threadIdx.x == 0) status[b] = code;
     if (px >= OH * OW) return;
     const size_t plane = (size_t)OH * OW;
@@ -133,7 +142,7 @@ __global__ __launch_bounds__(256) void resample_kernel(const unsigned char* __re
     int rgb[3] = {128, 128, 128};
     const int bx = ox - g.xp, by = oy - g.yp;
     if (bx >= 0 && bx < g.rw && by >= 0 && by < g.rh) {
-        const unsigned char* img = ws + off;
+        const unsigned char* img = ws + wo;
         int ix, iy, ax[4], ay[4];
         float fx, fy;
         cv_coord(bx, g.scale_x, ix, fx);
@@ -232,23 +241,33 @@ extern "C" size_t yv3_augment_workspace_bytes(long long src_bytes) {
     return src_bytes > 0 ? (size_t)src_bytes : 0;
 }
 
-extern "C" int yv3_augment_images(const unsigned char* src, long long src_bytes, const long long* offsets, const int* hw,
-                                  const double* params, int B, float* out, int out_h, int out_w,
-                                  void* workspace, size_t workspace_bytes, int* status, void* stream) {
-    if (!src || !offsets || !hw || !params || !out || !workspace || !status) return YV3_EINVAL;
-    if (src_bytes <= 0 || B <= 0 || out_h <= 0 || out_w <= 0 || B > 65535) return YV3_EINVAL;
+extern "C" int yv3_augment_images_from(const unsigned char* src, long long src_bytes, const long long* src_offsets,
+                                       const long long* ws_offsets, long long ws_span, const int* hw, const double* params, int B,
+                                       float* out, int out_h, int out_w, void* workspace, size_t workspace_bytes, int* status,
+                                       void* stream) {
+    if (!src || !src_offsets || !ws_offsets || !hw || !params || !out || !workspace || !status) return YV3_EINVAL;
+    if (src_bytes <= 0 || ws_span <= 0 || B <= 0 || out_h <= 0 || out_w <= 0 || B > 65535) return YV3_EINVAL;
     if ((long long)out_h * out_w > (1LL << 30)) return YV3_ESHAPE;
-    if (workspace_bytes < yv3_augment_workspace_bytes(src_bytes)) return YV3_EWORKSPACE;
+    if (workspace_bytes < (size_t)ws_span) return YV3_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     // ~4 waves of work per CU in all, at most one block per 256 source pixels of a 640x480 image
     const int per_image = max(1, min(1200, yv3_num_cu() * 8 / B));
-    hipLaunchKernelGGL(hsv_kernel, dim3(per_image, B), dim3(256), 0, s, src, src_bytes, offsets, hw, params, out_h, out_w,
-                       (unsigned char*)workspace);
+    hipLaunchKernelGGL(hsv_kernel, dim3(per_image, B), dim3(256), 0, s, src, src_bytes, src_offsets, ws_offsets, ws_span, hw, params,
+                       out_h, out_w, (unsigned char*)workspace);
     YV3_CHECK_LAUNCH();
     hipLaunchKernelGGL(resample_kernel, dim3(yv3_ceil_div((long long)out_h * out_w, 256), B), dim3(256), 0, s,
-                       (const unsigned char*)workspace, src_bytes, offsets, hw, params, out, out_h, out_w, status);
+                       (const unsigned char*)workspace, src_bytes, src_offsets, ws_offsets, ws_span, hw, params, out, out_h, out_w,
+                       status);
     YV3_CHECK_LAUNCH();
     return 0;
+}
+
+// The packed form: the colour copy of image b lives at its source's own offset, in a workspace as large as the sources.
+extern "C" int yv3_augment_images(const unsigned char* src, long long src_bytes, const long long* offsets, const int* hw,
+                                  const double* params, int B, float* out, int out_h, int out_w,
+                                  void* workspace, size_t workspace_bytes, int* status, void* stream) {
+    return yv3_augment_images_from(src, src_bytes, offsets, offsets, src_bytes, hw, params, B, out, out_h, out_w, workspace,
+                                   workspace_bytes, status, stream);
 }
 
 extern "C" int yv3_augment_labels(const double* labels, int B, int T, const int* hw, const double* params,
