@@ -633,6 +633,38 @@ size_t yv3_train_conv_wgrad_bf16_workspace_bytes(int B, int H, int W, int cin, i
 int yv3_train_conv_wgrad_bf16(const void* x, const void* x2, const void* dz, float* dw, int B, int H, int W, int cin, int cin_up,
                               int cout, int k, int stride, int x_nchw, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * BF16_ACT training step (net.backprop_math = BF16_ACT, csrc/train_bf16.hip and csrc/train_bf16_act.hip): the BF16 step with every
+ * conv_bn_relu activation stored once, in bf16 -- the conv output zb = bf16(z32), the layer output bf16(leaky(bn(zb)) [+ res]) and
+ * dz -- and no fp32 z, y or dz.  The arithmetic between two stores is fp32 (fp64 in the reductions), each store rounds as
+ * yv3_train_to_bf16 does.  C (cout) must be a multiple of 8 except for yv3_train_bias_bwd_bf16 (YV3_ESHAPE otherwise).
+ * ------------------------------------------------------------------------------------------ */
+
+/* zb = bf16(conv(bf16 x, bf16 w)), [B][Ho][Wo][cout] bf16: yv3_train_conv_fwd_bf16's accumulators (same kernel, same order), no bias. */
+int yv3_train_conv_fwd_bf16o(const void* x, const void* x2, const void* wf, void* zb, int B, int H, int W, int cin, int cin_up, int cout,
+                             int k, int stride, int x_nchw, void* stream);
+
+/* Workspace of the four calls below over P rows of C channels (0 on a bad argument). */
+size_t yv3_train_channel_bf16_workspace_bytes(long long P, int C);
+
+/* yv3_train_bn_stats of a bf16 z. */
+int yv3_train_bn_stats_bf16(const void* z, long long P, int C, float eps, float momentum, const float* run_mean, const float* run_var,
+                            float* run_mean_out, float* run_var_out, float* mean, float* invstd, void* ws, size_t ws_bytes, void* stream);
+
+/* y = bf16(leaky(gamma (z - mean) invstd + beta) [+ residual]); z, residual and y bf16 [P][C]. */
+int yv3_train_bn_act_fwd_bf16(const void* z, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                              const void* residual, void* y, long long P, int C, void* stream);
+
+/* yv3_train_bn_act_bwd of a bf16 z and a fp32 dy; dz is written as bf16 [P][C], dgamma and dbeta as fp32. */
+int yv3_train_bn_act_bwd_bf16(const void* z, const float* dy, const float* mean, const float* invstd, const float* gamma,
+                              const float* beta, void* dz, float* dgamma, float* dbeta, long long P, int C, int train, void* ws,
+                              size_t ws_bytes, void* stream);
+
+/* yv3_train_bias_bwd with dout = bf16(dlogits * (*scale)) in rows of C rounded up to a multiple of 8, the padding channels zero;
+ * dbias sums the fp32 products. */
+int yv3_train_bias_bwd_bf16(const float* dlogits, const float* scale, void* dout, float* dbias, long long P, int C, void* ws,
+                            size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,15 +1,17 @@
 """Time one training step at 416x416 (net(x, target) + loss.backward(), net.backprop = True, .train()) at bs=8 and bs=16, for each
-net.backprop_math in --math (f32: exact fp32; bf16: bf16 convolution operands), against the same network run by torch's own modules
+net.backprop_math in --math (f32: exact fp32; bf16: bf16 convolution operands; bf16_act: bf16 with the activations stored in bf16
+only), against the same network run by torch's own modules
 in fp32 (F.conv2d / F.batch_norm on MIOpen, tests/train_ref.forward) and, with bf16 in --math, the same under
 torch.autocast("cuda", torch.bfloat16), all in the same process.  7 interleaved rounds, median reported; then one profiled step of
-each of ours split by kernel class (conv classes also in TFLOP/s of the products they compute).
+each of ours split by kernel class (conv classes also in TFLOP/s of the products they compute), and the device memory each of ours
+holds between forward and backward (torch.cuda.memory_allocated with the loss alive, minus its value before the forward).
 
 --input-grad instead times our step with net.input_grad off and on (x.requires_grad), interleaved in the same way, and the layer-0
 input-gradient kernel alone (yv3_train_conv0_dgrad[_bf16]) beside layer 0's wgrad launch, which reads the same dz: device events
 around 50 launches that rotate over enough dz buffers to exceed the 256 MiB Infinity Cache, and the rate over the bytes the kernel
 must move (dz read once, dx written).
 
-    python tools/train_bench.py [--batches 8 16] [--rounds 7] [--math f32 bf16] [--input-grad]
+    python tools/train_bench.py [--batches 8 16] [--rounds 7] [--math f32 bf16 bf16_act] [--input-grad]
 """
 import argparse
 import json
@@ -26,7 +28,9 @@ sys.path.insert(0, REPO)
 from tests import train_ref as T                      # noqa: E402
 from tests import yolo_loss_ref as R                  # noqa: E402
 from tests.helpers import trained_like_stream         # noqa: E402
-from yolo_v3_amd import YoloNet, WeightManager, synth, arch, _ffi, F32, BF16  # noqa: E402
+from yolo_v3_amd import YoloNet, WeightManager, synth, arch, _ffi, F32, BF16, BF16_ACT  # noqa: E402
+
+MATH = {"f32": F32, "bf16": BF16, "bf16_act": BF16_ACT}
 
 DEV = "cuda:0"
 
@@ -50,10 +54,22 @@ def kernel_classes(fn):
         k = ("input dgrad" if "conv0_dgrad" in n else "conv fwd" if "conv_gemm<0>" in n or "conv_bf16<0," in n else "conv dgrad" if "conv_gemm<1>" in n or "conv_bf16<1," in n
              else "conv wgrad" if "conv_gemm<2>" in n or "conv_bf16<2," in n or "wgrad_reduce" in n
              else "cast" if "to_bf16" in n else "weight pack" if "pack_weight" in n
-             else "BN / act" if any(s in n for s in ("channel_partials", "finalize", "bn_act", "eval_stats"))
+             else "BN / act" if any(s in n for s in ("channel_partials", "finalize", "bn_act", "eval_stats", "bias_bwd"))
              else "loss" if "yolo" in n.lower() or "loss" in n.lower() else "other")
         cls[k] = cls.get(k, 0.0) + getattr(ev, "device_time_total", getattr(ev, "cuda_time_total", 0.0)) / 1e3
     return {k: round(v, 3) for k, v in sorted(cls.items())}
+
+
+def held_mb(net, x, tg, math):
+    """MB of device memory one step holds between its forward and its backward."""
+    net.backprop_math = math
+    net.zero_grad(set_to_none=True)
+    torch.cuda.synchronize()
+    before = torch.cuda.memory_allocated()
+    loss = net(x, tg)
+    held = torch.cuda.memory_allocated() - before
+    loss.backward()
+    return round(held / 1e6, 1)
 
 
 def step_gflop(B, size=416):
@@ -81,7 +97,7 @@ def event_ms(launch, n_buffers, reps=50):
 def conv0_dgrad_alone(B, math, size=416, cout=32):
     """The input-gradient kernel and layer 0's wgrad on [B, size, size, cout] dz -> dict of times and the dgrad's rate."""
     lib, s = _ffi.lib(), _ffi.stream_ptr()
-    bf = math == BF16
+    bf = math in (BF16, BF16_ACT)
     dz_bytes = B * size * size * cout * (2 if bf else 4)
     dx_bytes = B * 3 * size * size * 4
     nbuf = max(2, -(-600 * 2 ** 20 // dz_bytes))
@@ -111,7 +127,7 @@ def input_grad_cost(net, a):
         tg = torch.from_numpy(R.random_rows(5, B, 30, 80, (0.03, 0.8)))
         out[B] = {}
         for m in a.math:
-            def step(want_x, math={"f32": F32, "bf16": BF16}[m]):
+            def step(want_x, math=MATH[m]):
                 net.backprop_math = math
                 net.zero_grad(set_to_none=True)
                 xin = x.clone().requires_grad_(True) if want_x else x
@@ -125,7 +141,7 @@ def input_grad_cost(net, a):
                     times[k].append(timed(f))
             r = {k: round(float(np.median(v)), 3) for k, v in times.items()}
             r["spread_ms"] = {k: [round(min(v), 3), round(max(v), 3)] for k, v in times.items()}
-            r.update(conv0_dgrad_alone(B, {"f32": F32, "bf16": BF16}[m]))
+            r.update(conv0_dgrad_alone(B, MATH[m]))
             out[B][m] = r
             print(B, m, json.dumps(r), flush=True)
     print(json.dumps(out))
@@ -135,7 +151,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[8, 16])
     ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--math", nargs="+", choices=("f32", "bf16"), default=["f32"])
+    ap.add_argument("--math", nargs="+", choices=tuple(MATH), default=["f32"])
     ap.add_argument("--input-grad", action="store_true", help="time the step with net.input_grad off and on, and the layer-0 dgrad alone")
     a = ap.parse_args()
     net = YoloNet((416, 416), numClass=80)
@@ -166,11 +182,9 @@ def main():
                 logits, _, _ = T.forward(sd_gpu, x, True, torch.float32)
             torch.autograd.backward(logits, [torch.ones_like(l) * 1e-3 for l in logits])
 
-        fns = {"ours_f32_ms": ours(F32)} if "f32" in a.math else {}
-        if "bf16" in a.math:
-            fns["ours_bf16_ms"] = ours(BF16)
+        fns = {"ours_%s_ms" % m: ours(MATH[m]) for m in MATH if m in a.math}
         fns["torch_miopen_fp32_ms"] = torch_modules
-        if "bf16" in a.math:
+        if "bf16" in a.math or "bf16_act" in a.math:
             fns["torch_autocast_bf16_ms"] = torch_autocast
         for f in fns.values():
             f()
@@ -179,6 +193,8 @@ def main():
             for k, f in fns.items():
                 times[k].append(timed(f))
         out[B] = {k: float(np.median(v)) for k, v in times.items()}
+        for m in a.math:
+            out[B]["ours_%s_held_MB" % m] = held_mb(net, x, tg, MATH[m])
         gf = step_gflop(B)
         for m in a.math:
             key = "ours_%s_by_kernel_class_ms" % m

@@ -19,6 +19,7 @@ if os.environ.get("YV3_MEASURE") != "1":
                       "(YV3_MEASURE=1); the bundled libyv3.so and the default plans are used" % ", ".join(_stray), RuntimeWarning)
 
 F32, BF16, F32X3, F32H2 = 0, 1, 2, 3
+BF16_ACT = 4          # net.backprop_math only: the BF16 training step with activations stored in bf16 only (backprop.py)
 ACT_LINEAR, ACT_LEAKY = 0, 1
 PP_EVAL, PP_PROB = 1, 2
 OPT_NO_PINGPONG, OPT_K3S1, OPT_WINO_EVEN, OPT_WINO_ALWAYS, OPT_TWO_LANES, OPT_WINO4_TILES = 1, 2, 4, 8, 16, 32
@@ -163,6 +164,12 @@ _SIGNATURES = {
     "yv3_train_conv0_dgrad_bf16": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "yv3_train_conv_wgrad_bf16_workspace_bytes": (c_size_t, [c_int] * 7),
     "yv3_train_conv_wgrad_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_size_t, c_void_p]),
+    "yv3_train_conv_fwd_bf16o": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
+    "yv3_train_channel_bf16_workspace_bytes": (c_size_t, [c_longlong, c_int]),
+    "yv3_train_bn_stats_bf16": (c_int, [c_void_p, c_longlong, c_int, c_float, c_float] + [c_void_p] * 7 + [c_size_t, c_void_p]),
+    "yv3_train_bn_act_fwd_bf16": (c_int, [c_void_p] * 7 + [c_longlong, c_int, c_void_p]),
+    "yv3_train_bn_act_bwd_bf16": (c_int, [c_void_p] * 9 + [c_longlong, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "yv3_train_bias_bwd_bf16": (c_int, [c_void_p] * 4 + [c_longlong, c_int, c_void_p, c_size_t, c_void_p]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -4,7 +4,12 @@
 governs inference only): ``F32`` (the default) runs the step in exact fp32 on the kernels of csrc/train.hip; ``BF16`` rounds the two
 operands of every convolution product to bf16 (forward: x and w; dgrad: dz and w; wgrad: x and dz) and accumulates in fp32 on the
 kernels of csrc/train_bf16.hip, with z, dx and dw in fp32 and everything else exactly as in F32.  The steps below name the F32 calls;
-BF16 uses their ``_bf16`` counterparts and keeps a bf16 copy (yv3_train_to_bf16) of each conv input and each dz beside the fp32 one:
+BF16 uses their ``_bf16`` counterparts and keeps a bf16 copy (yv3_train_to_bf16) of each conv input and each dz beside the fp32 one.
+``BF16_ACT`` is the BF16 step with every conv_bn_relu activation stored once, in bf16, and no fp32 twin: the conv writes
+``zb = bf16(z)`` (yv3_train_conv_fwd_bf16o), the statistics and both BatchNorm passes read zb, the layer output is
+``bf16(leaky(bn(zb)) [+ res])`` (yv3_train_bn_act_fwd_bf16), and the BatchNorm / bias backward writes dz as bf16
+(yv3_train_bn_act_bwd_bf16, yv3_train_bias_bwd_bf16).  The head logits, dy / dx, parameters, gradients and statistics stay fp32; a
+rounding's gradient is the identity.  The steps:
 
 * forward: each conv_bn_relu is ``z = conv(x, w)`` (yv3_train_conv_fwd), the BatchNorm statistics (yv3_train_bn_stats: the batch's
   mean and biased variance in ``.train()``, the running statistics in ``.eval()``) and ``y = leaky(bn(z)) [+ residual]``
@@ -94,10 +99,10 @@ def _round8(c):
 
 
 def backprop_math(net):
-    """net.backprop_math, checked: F32 or BF16, else Yv3Error (YV3_EINVAL)."""
+    """net.backprop_math, checked: F32, BF16 or BF16_ACT, else Yv3Error (YV3_EINVAL)."""
     m = getattr(net, "backprop_math", _ffi.F32)
-    if not isinstance(m, numbers.Integral) or isinstance(m, bool) or m not in (_ffi.F32, _ffi.BF16):
-        err = _ffi.Yv3Error("net.backprop_math must be yolo_v3_amd.F32 or yolo_v3_amd.BF16, got %r" % (m,))
+    if not isinstance(m, numbers.Integral) or isinstance(m, bool) or m not in (_ffi.F32, _ffi.BF16, _ffi.BF16_ACT):
+        err = _ffi.Yv3Error("net.backprop_math must be yolo_v3_amd.F32, yolo_v3_amd.BF16 or yolo_v3_amd.BF16_ACT, got %r" % (m,))
         err.code = _ffi.EINVAL
         raise err
     return int(m)
@@ -139,8 +144,13 @@ def net_forward(run, want_grad):
     B, _, H, W = x.shape
     dev = x.device
     bufs = {"x": x}
-    bf = run.math == _ffi.BF16
-    bufs_b = {"x": _bf16(lib, s, x, x.numel(), 1, 1, "x")} if bf else None      # bf16 copies of the conv inputs (BF16)
+    act = run.math == _ffi.BF16_ACT            # activations in bf16 only: bufs holds x and the head logits, bufs_b the rest
+    bf = act or run.math == _ffi.BF16
+    bufs_b = {"x": _bf16(lib, s, x, x.numel(), 1, 1, "x")} if bf else None      # bf16 conv inputs (BF16: copies of bufs' tensors)
+    last = {}                                  # buffer -> index of the last op that reads it in the forward
+    for i, op in enumerate(run.ops):
+        last.update({b: i for b in (op.src, op.src2, op.res) if b is not None})
+    keep = set()                               # BF16_ACT: the bf16 buffers the walk reads (the inputs of a wgrad)
     run.shape["x"] = (B, H, W, 3)
     run.need["x"] = run.input_grad
     logits = [None] * 3
@@ -156,7 +166,10 @@ def net_forward(run, want_grad):
         run.need[op.out] = any(p.requires_grad for p in params) or run.need[op.src] or \
             (op.src2 is not None and run.need[op.src2]) or (op.res is not None and run.need[op.res])
         sv = {}
-        z = torch.empty((b_, ho, wo, cout), device=dev, dtype=torch.float32)
+        if want_grad and c.weight.requires_grad:
+            keep.update(b for b in (op.src, op.src2) if b is not None)
+        zb16 = act and not op.head
+        z = torch.empty((b_, ho, wo, cout), device=dev, dtype=torch.int16 if zb16 else torch.float32)
         bias = _f32(c.bias, "bias of " + op.out) if op.head else None
         if bf:
             wf = torch.empty(_round8(cout) * cin * k * k, device=dev, dtype=torch.int16)
@@ -164,9 +177,15 @@ def net_forward(run, want_grad):
             _ffi.check(lib.yv3_train_pack_weight_bf16(wt.data_ptr(), wf.data_ptr(), wd.data_ptr() if wd is not None else None,
                                                       cout, cin, k, s), "yv3_train_pack_weight_bf16")
             x2 = bufs_b[op.src2] if op.src2 is not None else None
-            _ffi.check(lib.yv3_train_conv_fwd_bf16(bufs_b[op.src].data_ptr(), x2.data_ptr() if x2 is not None else None, wf.data_ptr(),
-                                                   bias.data_ptr() if bias is not None else None, z.data_ptr(), b_, h, w, cin,
-                                                   op.cin_up, cout, k, st, int(op.src == "x"), s), "yv3_train_conv_fwd_bf16")
+            if zb16:
+                _ffi.check(lib.yv3_train_conv_fwd_bf16o(bufs_b[op.src].data_ptr(), x2.data_ptr() if x2 is not None else None,
+                                                        wf.data_ptr(), z.data_ptr(), b_, h, w, cin, op.cin_up, cout, k, st,
+                                                        int(op.src == "x"), s), "yv3_train_conv_fwd_bf16o")
+            else:
+                _ffi.check(lib.yv3_train_conv_fwd_bf16(bufs_b[op.src].data_ptr(), x2.data_ptr() if x2 is not None else None,
+                                                       wf.data_ptr(), bias.data_ptr() if bias is not None else None, z.data_ptr(),
+                                                       b_, h, w, cin, op.cin_up, cout, k, st, int(op.src == "x"), s),
+                           "yv3_train_conv_fwd_bf16")
         else:
             wf = torch.empty(cout * cin * k * k, device=dev, dtype=torch.float32)
             wd = torch.empty_like(wf) if want_grad else None
@@ -193,11 +212,12 @@ def net_forward(run, want_grad):
                     bn.num_batches_tracked.add_(1)
                 mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
                 rm_new, rv_new = torch.empty_like(rm), torch.empty_like(rv)
-                nb = lib.yv3_train_channel_workspace_bytes(P, cout)
+                nb = (lib.yv3_train_channel_bf16_workspace_bytes if act else lib.yv3_train_channel_workspace_bytes)(P, cout)
                 ws = _ws(nb, dev)
-                _ffi.check(lib.yv3_train_bn_stats(z.data_ptr(), P, cout, float(bn.eps), float(mom), rm.data_ptr(), rv.data_ptr(),
-                                                  rm_new.data_ptr(), rv_new.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                                                  ws.data_ptr(), nb, s), "yv3_train_bn_stats")
+                stats = lib.yv3_train_bn_stats_bf16 if act else lib.yv3_train_bn_stats
+                _ffi.check(stats(z.data_ptr(), P, cout, float(bn.eps), float(mom), rm.data_ptr(), rv.data_ptr(),
+                                 rm_new.data_ptr(), rv_new.data_ptr(), mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(), nb, s),
+                           "yv3_train_bn_stats")
                 with torch.no_grad():          # (copy_ moves the buffers' _version: the inference engine re-packs)
                     bn.running_mean.copy_(rm_new)
                     bn.running_var.copy_(rv_new)
@@ -205,15 +225,24 @@ def net_forward(run, want_grad):
                 _ffi.check(lib.yv3_train_bn_eval_stats(bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.eps),
                                                        mean.data_ptr(), invstd.data_ptr(), cout, s), "yv3_train_bn_eval_stats")
             y = torch.empty_like(z)
-            res = bufs[op.res] if op.res is not None else None
-            _ffi.check(lib.yv3_train_bn_act_fwd(z.data_ptr(), mean.data_ptr(), invstd.data_ptr(), g.data_ptr(), bt.data_ptr(),
-                                                res.data_ptr() if res is not None else None, y.data_ptr(), P, cout, s),
-                       "yv3_train_bn_act_fwd")
-            bufs[op.out] = y
-            if bf:                             # (every conv_bn_relu output is some conv's input)
-                bufs_b[op.out] = _bf16(lib, s, y, P, cout, cout, op.out)
+            res = (bufs_b if act else bufs)[op.res] if op.res is not None else None
+            _ffi.check((lib.yv3_train_bn_act_fwd_bf16 if act else lib.yv3_train_bn_act_fwd)(
+                z.data_ptr(), mean.data_ptr(), invstd.data_ptr(), g.data_ptr(), bt.data_ptr(),
+                res.data_ptr() if res is not None else None, y.data_ptr(), P, cout, s), "yv3_train_bn_act_fwd")
+            if act:
+                bufs_b[op.out] = y
+                if not (want_grad and run.need[op.out]):       # no walk will reach this op
+                    z = None
+            else:
+                bufs[op.out] = y
+                if bf:                         # (every conv_bn_relu output is some conv's input)
+                    bufs_b[op.out] = _bf16(lib, s, y, P, cout, cout, op.out)
             sv.update(z=z, mean=mean, invstd=invstd, gamma=g, beta=bt, train=int(bn.training))
         run.saved[i] = sv
+        if act:                                # a bf16 buffer lives until its last reader: a later op, or a wgrad of the walk
+            for b in {op.src, op.src2, op.res} - {None}:
+                if last[b] == i and b not in keep:
+                    del bufs_b[b]
     if want_grad:
         run.bufs = bufs
         run.bufs_b = bufs_b
@@ -245,7 +274,8 @@ def walk(run, dlogits, scale=None):
     latter when run.need["x"]."""
     lib, s = _ffi.lib(), _ffi.stream_ptr()
     dev = run.x.device
-    bf = run.math == _ffi.BF16
+    act = run.math == _ffi.BF16_ACT
+    bf = act or run.math == _ffi.BF16
     grads = {}                 # buffer -> dL/dbuffer (NHWC fp32; "x": NCHW)
     pg = {}
     trace = run.trace
@@ -276,22 +306,25 @@ def walk(run, dlogits, scale=None):
         b_, h, w, cin, cout, k, st = sv["geo"]
         _, ho, wo, _ = run.shape[op.out]
         P = b_ * ho * wo
-        nb = lib.yv3_train_channel_workspace_bytes(P, cout)
+        nb = (lib.yv3_train_channel_bf16_workspace_bytes if act else lib.yv3_train_channel_workspace_bytes)(P, cout)
         ws = _ws(nb, dev)
-        dz = torch.empty_like(dy)
+        # BF16_ACT: dz is born in bf16, in the padded rows the dgrad / wgrad kernels read
+        dz = torch.empty(P * _round8(cout), device=dev, dtype=torch.int16) if act else torch.empty_like(dy)
         c = op.conv
         if op.head:
             db = torch.empty(cout, device=dev, dtype=torch.float32)
-            _ffi.check(lib.yv3_train_bias_bwd(dy.data_ptr(), scale.data_ptr() if scale is not None else None, dz.data_ptr(),
-                                              db.data_ptr(), P, cout, ws.data_ptr(), nb, s), "yv3_train_bias_bwd")
+            _ffi.check((lib.yv3_train_bias_bwd_bf16 if act else lib.yv3_train_bias_bwd)(
+                dy.data_ptr(), scale.data_ptr() if scale is not None else None, dz.data_ptr(), db.data_ptr(), P, cout, ws.data_ptr(),
+                nb, s), "yv3_train_bias_bwd")
             pg[id(c.bias)] = db
             rec(i, dz=dz, dbias=db)
         else:
             dgam = torch.empty(cout, device=dev, dtype=torch.float32)
             dbet = torch.empty_like(dgam)
-            _ffi.check(lib.yv3_train_bn_act_bwd(sv["z"].data_ptr(), dy.data_ptr(), sv["mean"].data_ptr(), sv["invstd"].data_ptr(),
-                                                sv["gamma"].data_ptr(), sv["beta"].data_ptr(), dz.data_ptr(), dgam.data_ptr(),
-                                                dbet.data_ptr(), P, cout, sv["train"], ws.data_ptr(), nb, s), "yv3_train_bn_act_bwd")
+            _ffi.check((lib.yv3_train_bn_act_bwd_bf16 if act else lib.yv3_train_bn_act_bwd)(
+                sv["z"].data_ptr(), dy.data_ptr(), sv["mean"].data_ptr(), sv["invstd"].data_ptr(), sv["gamma"].data_ptr(),
+                sv["beta"].data_ptr(), dz.data_ptr(), dgam.data_ptr(), dbet.data_ptr(), P, cout, sv["train"], ws.data_ptr(), nb, s),
+                "yv3_train_bn_act_bwd")
             pg[id(op.bn.weight)], pg[id(op.bn.bias)] = dgam, dbet
             rec(i, dz=dz, dgamma=dgam, dbeta=dbet)
             if op.res is not None and run.need[op.res]:
@@ -299,7 +332,7 @@ def walk(run, dlogits, scale=None):
         need_src = run.need[op.src]
         need_src2 = op.src2 is not None and run.need[op.src2]
         if bf:
-            dzb = _bf16(lib, s, dz, P, cout, _round8(cout), "dz of " + op.out)
+            dzb = dz if act else _bf16(lib, s, dz, P, cout, _round8(cout), "dz of " + op.out)
         if c.weight.requires_grad:
             dw = torch.empty_like(c.weight, dtype=torch.float32, memory_format=torch.contiguous_format)
             if bf:

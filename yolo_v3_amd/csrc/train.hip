@@ -13,6 +13,7 @@
 // partials summed in index order in fp64), so identical inputs give identical bits.
 #include "yv3_common.h"
 #include "train_conv0_dgrad.h"
+#include "train_channel.h"
 
 namespace {
 
@@ -208,8 +209,6 @@ struct Red {
     double* part;     // [split][2][C]
 };
 
-__device__ __forceinline__ float leaky_grad(float u, float d) { return u > 0.f ? d : d * 0.1f; }
-
 template <int MODE>
 __global__ __launch_bounds__(NT) void channel_partials(Red r) {
     __shared__ double s0[RR][RC], s1[RR][RC];
@@ -241,32 +240,6 @@ __global__ __launch_bounds__(NT) void channel_partials(Red r) {
     }
 }
 
-__device__ __forceinline__ void sum_partials(const double* part, int split, int C, int c, double* a, double* b) {
-    double x = 0.0, y = 0.0;
-    for (int s = 0; s < split; ++s) { x += part[((long long)s * 2) * C + c]; y += part[((long long)s * 2 + 1) * C + c]; }
-    *a = x; *b = y;
-}
-
-// batch statistics -> mean, 1/sqrt(var_biased + eps); running stats (momentum, unbiased variance) written to run_*_out
-__global__ void stats_finalize(const double* part, int split, int C, long long P, float eps, float momentum,
-                               const float* run_mean, const float* run_var, float* run_mean_out, float* run_var_out,
-                               float* mean, float* invstd) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    double s, q;
-    sum_partials(part, split, C, c, &s, &q);
-    const double mu = s / (double)P;
-    double var = q / (double)P - mu * mu;
-    if (var < 0.0) var = 0.0;
-    mean[c] = (float)mu;
-    invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-    if (run_mean_out) {
-        const double unb = P > 1 ? var * (double)P / (double)(P - 1) : var;
-        run_mean_out[c] = (float)((1.0 - momentum) * (double)run_mean[c] + momentum * mu);
-        run_var_out[c] = (float)((1.0 - momentum) * (double)run_var[c] + momentum * unb);
-    }
-}
-
 __global__ void eval_stats(const float* run_mean, const float* run_var, float eps, float* mean, float* invstd, int C) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
@@ -286,20 +259,6 @@ __global__ void bn_act_fwd(const float* __restrict__ z, const float* mean, const
     }
 }
 
-// per-channel coefficients of the backward: dgamma, dbeta out; coef[0] = gamma invstd, coef[1] = dbeta / P, coef[2] = dgamma / P
-__global__ void bnbwd_finalize(const double* part, int split, int C, long long P, int train, const float* gamma, const float* invstd,
-                               float* dgamma, float* dbeta, float* coef) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    double a, b;
-    sum_partials(part, split, C, c, &a, &b);
-    dbeta[c] = (float)a;
-    dgamma[c] = (float)b;
-    coef[c] = gamma[c] * invstd[c];
-    coef[C + c] = train ? (float)(a / (double)P) : 0.f;
-    coef[2 * C + c] = train ? (float)(b / (double)P) : 0.f;
-}
-
 // dz = gamma invstd (du - dbeta / P - xhat dgamma / P)   (train; eval: the last two terms are 0)
 __global__ void bn_act_bwd_dz(const float* __restrict__ z, const float* __restrict__ dy, const float* mean, const float* invstd,
                               const float* gamma, const float* beta, const float* coef, float* __restrict__ dz, long long n, int C) {
@@ -309,14 +268,6 @@ __global__ void bn_act_bwd_dz(const float* __restrict__ z, const float* __restri
         const float du = leaky_grad(gamma[c] * xh + beta[c], dy[i]);
         dz[i] = coef[c] * ((du - coef[C + c]) - xh * coef[2 * C + c]);
     }
-}
-
-__global__ void colsum_finalize(const double* part, int split, int C, float* out) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    double a, b;
-    sum_partials(part, split, C, c, &a, &b);
-    out[c] = (float)a;
 }
 
 __global__ void scale_copy(const float* __restrict__ src, const float* scale, float* __restrict__ dst, long long n) {

@@ -28,6 +28,7 @@
 // Determinism: no atomics.  The MFMA k-chain runs in a fixed order, and the wgrad split partials are summed in split order in fp64.
 #include "yv3_common.h"
 #include "train_conv0_dgrad.h"
+#include "train_bf16_round.h"
 
 namespace {
 
@@ -42,16 +43,10 @@ struct GeoB {
     const u16* wp;    // FWD: wf [coutp][K]; DGRAD: wd [cin][K]
     const float* bias;
     float* out;       // FWD z [M][cout], DGRAD dx [M][cin], WGRAD partials [split][cout][k*k*cin]
+    u16* out_b;       // FWD with a bf16 result (OUT_B16): zb [M][cout], out unused
     int B, H, W, cin, cin_up, cout, coutp, k, stride, pad, Ho, Wo, nchw, accumulate;
     long long M, N, K, kchunk;
 };
-
-// fp32 -> bf16 bits, round to nearest even as torch's conversion: NaN -> the canonical quiet NaN 0x7fc0, subnormals rounded (no flush)
-__device__ __forceinline__ u16 rne_bf16(float f) {
-    const uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u16)0x7fc0;
-    return (u16)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
 
 __device__ __forceinline__ u16 load_x1(const GeoB& g, int n, int ih, int iw, int ci) {
     if (ih < 0 || iw < 0 || ih >= g.H || iw >= g.W) return 0;
@@ -86,8 +81,9 @@ __device__ __forceinline__ u32x4 pack8(const u16* v) {
     return u32x4{v[0] | ((unsigned)v[1] << 16), v[2] | ((unsigned)v[3] << 16), v[4] | ((unsigned)v[5] << 16), v[6] | ((unsigned)v[7] << 16)};
 }
 
-// WAVES_M x WAVES_N waves, each a 64x64 block of the (64 WAVES_M) x (64 WAVES_N) C tile; WGRAD: blockIdx.z is the K split
-template <int MODE, bool VEC, int WAVES_M, int WAVES_N>
+// WAVES_M x WAVES_N waves, each a 64x64 block of the (64 WAVES_M) x (64 WAVES_N) C tile; WGRAD: blockIdx.z is the K split.
+// OUT_B16 (FWD, N % 8 == 0, no bias): the same accumulators stored once as bf16 in g.out_b -- BF16_ACT's zb
+template <int MODE, bool VEC, int WAVES_M, int WAVES_N, bool OUT_B16 = false>
 __global__ __launch_bounds__(NT) void conv_bf16(GeoB g) {
     constexpr int TM = 64 * WAVES_M, TN = 64 * WAVES_N;
     constexpr int A_PER = TM * TK / 8 / NT, B_PER = TN * TK / 8 / NT;     // 16-byte chunks per thread and K step
@@ -266,6 +262,29 @@ __global__ __launch_bounds__(NT) void conv_bf16(GeoB g) {
         }
     }
     // C/D map of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+    if (OUT_B16) {
+        // A lane holds one column, so the memory neighbour of its element sits in lane ^ 1.  The two lanes of a pair trade: the even
+        // lane keeps the even rows r and gets its neighbour's, the odd lane the odd rows, and each stores both columns of its rows in
+        // one 4-byte store (N % 8 == 0 and an even column: a pair lies wholly inside or outside the row).  Every lane takes part
+        // in the exchange; only the store is guarded.
+        const bool odd = lane & 1;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const long long n = n0 + wn * 64 + j * 32 + (lane & 30);
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {
+                    const unsigned own0 = rne_bf16(acc[i][j][r]), own1 = rne_bf16(acc[i][j][r + 1]);
+                    const unsigned got = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(odd ? own0 : own1), 0xB1, 0xf, 0xf, true);  // quad_perm [1,0,3,2]
+                    const unsigned v = odd ? (got | (own1 << 16)) : (own0 | (got << 16));
+                    const int rr = r + (odd ? 1 : 0);
+                    const long long m = m0 + wm * 64 + i * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * (lane >> 5);
+                    if (m < g.M && n < g.N) *(unsigned*)(g.out_b + m * g.N + n) = v;
+                }
+        }
+        return;
+    }
     float* out = g.out + (MODE == WGRAD ? (long long)blockIdx.z * g.M * g.N : 0);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -370,15 +389,15 @@ void wgrad_split(long long M, long long N, long long K, int* split, long long* c
     *split = (int)((K + c - 1) / c);
 }
 
-template <int MODE, bool VEC>
+template <int MODE, bool VEC, bool OUT_B16 = false>
 int launch_conv(const GeoB& g, int split, hipStream_t st) {
     int wm, wn;
     pick_tile(g.M, g.N, &wm, &wn);
     dim3 grid((unsigned)((g.M + 64 * wm - 1) / (64 * wm)), (unsigned)((g.N + 64 * wn - 1) / (64 * wn)), (unsigned)split);
     if (grid.x > 0x7fffffffu || grid.y > 65535u) return YV3_ESHAPE;
-    if (wm == 4) hipLaunchKernelGGL((conv_bf16<MODE, VEC, 4, 1>), grid, dim3(NT), 0, st, g);
-    else if (wm == 1) hipLaunchKernelGGL((conv_bf16<MODE, VEC, 1, 4>), grid, dim3(NT), 0, st, g);
-    else hipLaunchKernelGGL((conv_bf16<MODE, VEC, 2, 2>), grid, dim3(NT), 0, st, g);
+    if (wm == 4) hipLaunchKernelGGL((conv_bf16<MODE, VEC, 4, 1, OUT_B16>), grid, dim3(NT), 0, st, g);
+    else if (wm == 1) hipLaunchKernelGGL((conv_bf16<MODE, VEC, 1, 4, OUT_B16>), grid, dim3(NT), 0, st, g);
+    else hipLaunchKernelGGL((conv_bf16<MODE, VEC, 2, 2, OUT_B16>), grid, dim3(NT), 0, st, g);
     YV3_CHECK_LAUNCH();
     return 0;
 }
@@ -415,6 +434,18 @@ int yv3_train_conv_fwd_bf16(const void* x, const void* x2, const void* wf, const
     g.x = (const u16*)x; g.x2 = (const u16*)x2; g.wp = (const u16*)wf; g.bias = bias; g.out = z;
     g.M = (long long)B * g.Ho * g.Wo; g.N = cout; g.K = (long long)k * k * cin;
     return x_nchw ? launch_conv<FWD, false>(g, 1, (hipStream_t)stream) : launch_conv<FWD, true>(g, 1, (hipStream_t)stream);
+}
+
+int yv3_train_conv_fwd_bf16o(const void* x, const void* x2, const void* wf, void* zb, int B, int H, int W, int cin, int cin_up, int cout,
+                             int k, int stride, int x_nchw, void* stream) {
+    if (!x || !wf || !zb || (cin_up > 0 && !x2)) return YV3_EINVAL;
+    if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0) return YV3_EINVAL;
+    if (!shape_ok(B, H, W, cin, cin_up, cout, k, stride) || (x_nchw && cin_up) || (cout & 7)) return YV3_ESHAPE;
+    if (!x_nchw && ((cin & 7) || (cin_up & 7))) return YV3_ESHAPE;
+    GeoB g = make_geo(B, H, W, cin, cin_up, cout, k, stride, x_nchw);
+    g.x = (const u16*)x; g.x2 = (const u16*)x2; g.wp = (const u16*)wf; g.out_b = (u16*)zb;
+    g.M = (long long)B * g.Ho * g.Wo; g.N = cout; g.K = (long long)k * k * cin;
+    return x_nchw ? launch_conv<FWD, false, true>(g, 1, (hipStream_t)stream) : launch_conv<FWD, true, true>(g, 1, (hipStream_t)stream);
 }
 
 int yv3_train_conv_dgrad_bf16(const void* dz, const void* wd, float* dx, int B, int H, int W, int cin, int cout, int k, int stride,

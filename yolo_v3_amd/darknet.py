@@ -283,7 +283,8 @@ class YoloNet(nn.Module):
         self.math_mode = DEFAULT_MATH_MODE
         # net(x, target) as a differentiable training step (yolo_v3_amd/backprop.py): False keeps the no-grad loss
         self.backprop = False
-        # arithmetic of the training step's convolutions: F32 (exact fp32) or BF16 (bf16 operands, fp32 accumulation)
+        # arithmetic of the training step's convolutions: F32 (exact fp32), BF16 (bf16 operands, fp32 accumulation) or BF16_ACT
+        # (BF16 with the activations stored in bf16 only)
         self.backprop_math = _ffi.F32
         # True: the training path (net(x, target) with backprop, net.logits(x)) also fills x.grad when x requires grad; False: such
         # an x raises NotImplementedError
