@@ -21,6 +21,7 @@ from tests import test_gpu_train_bf16 as GB
 from tests import train_kernel_ref as K
 from tests import train_ref as T
 from tests import train_ref_bf16 as TB
+from tests import train_states as S
 from tests import yolo_loss_ref as R
 from tests.helpers import trained_like_stream
 from yolo_v3_amd import YoloNet, WeightManager, backprop, synth, F32, BF16
@@ -74,12 +75,22 @@ def traced_step(net, x, tg):
     return run, loss, pg
 
 
-def check_step(net, sd, run, pg, train, what):
-    """Each op of the traced step against float64 on the GPU's own inputs; sd: the state_dict before the step."""
+def check_step(net, sd, run, pg, train, what, state=None):
+    """Each op of the traced step against float64 on the GPU's own inputs; sd: the state_dict before the step.  With a `state`
+    (tests/train_states.py) it, not `train`, gives each op's BatchNorm mode, momentum and eps, and the ops the walk visits and what
+    each does there must be exactly tests/train_states.py's expected_walk."""
     bf = run.math == BF16
     r = K.rb if bf else (lambda t: t)
     ops, keys = run.ops, K.op_params(net, run.ops)
     bufs, tr = run.bufs, run.trace
+    walk = S.expected_walk(state if state is not None else S.ALL_TRAIN, ops)
+    assert state is not None or all(v is not None for v in walk.values())
+    assert sorted(tr) == [i for i in range(len(ops)) if walk[i] is not None]
+
+    def bn_of(kbn):
+        """(training, the batch's weight in the running statistics, eps) of one op's BatchNorm."""
+        return (train, K.MOMENTUM, K.EPS) if state is None else (state.bn(kbn)[0], state.factor(kbn), state.bn(kbn)[2])
+
     P = {k: v.detach().cpu().double() for k, v in net.state_dict().items()}       # parameters (unchanged) and the new running stats
     before = {k: v.detach().cpu().double() for k, v in sd.items()}
     w = Worst()
@@ -110,14 +121,15 @@ def check_step(net, sd, run, pg, train, what):
         sv = run.saved[i]
         zr = K.rows(nchw64(z_gpu))
         mean_g, invstd_g = sv["mean"].cpu().double(), sv["invstd"].cpu().double()
-        if train:
-            mean, var, invstd = K.bn_batch_stats(zr)
-            rm, rv = K.bn_running(mean, var, zr.shape[0], before[kbn + ".running_mean"], before[kbn + ".running_var"])
+        training, mom, eps = bn_of(kbn)
+        if training:
+            mean, var, invstd = K.bn_batch_stats(zr, eps)
+            rm, rv = K.bn_running(mean, var, zr.shape[0], before[kbn + ".running_mean"], before[kbn + ".running_var"], mom)
             w.add("mean", op.out, K.bn_ratio(mean_g, mean))
             w.add("running_mean", op.out, K.bn_ratio(P[kbn + ".running_mean"], rm))
             w.add("running_var", op.out, K.bn_ratio(P[kbn + ".running_var"], rv))
         else:
-            _, invstd = K.bn_eval_stats(before[kbn + ".running_mean"], before[kbn + ".running_var"])
+            _, invstd = K.bn_eval_stats(before[kbn + ".running_mean"], before[kbn + ".running_var"], eps)
             assert torch.equal(mean_g, before[kbn + ".running_mean"]), op.out
             assert torch.equal(P[kbn + ".running_mean"], before[kbn + ".running_mean"]), op.out
             assert torch.equal(P[kbn + ".running_var"], before[kbn + ".running_var"]), op.out
@@ -143,8 +155,15 @@ def check_step(net, sd, run, pg, train, what):
 
     named = dict(net.named_parameters())
     und = total = 0
+    want_pg = set()
     for i in range(len(ops) - 1, -1, -1):
+        if walk[i] is None:                                            # not needed: no contribution may have reached it either
+            assert ops[i].head or ops[i].out not in count, ops[i].out
+            continue
         op, (kw, kb, kbn), t = ops[i], keys[i], tr[i]
+        assert set(t) & set(S.WALK_KEYS) == walk[i], (op.out, sorted(t), sorted(walk[i]))
+        mine = ([kb] if op.head else [kbn + ".weight", kbn + ".bias"]) + ([kw] if "dw" in walk[i] else [])
+        want_pg.update(id(named[k]) for k in mine)
         st = op.conv.stride[0]
         assert count[op.out] == consumers[op.out], (op.out, count[op.out], consumers[op.out])
         assert torch.equal(t["dy"], last[op.out]), op.out              # the dy the op got is what its consumers left
@@ -157,22 +176,25 @@ def check_step(net, sd, run, pg, train, what):
             assert pg[id(named[kb])] is not None and torch.equal(pg[id(named[kb])], t["dbias"])
         else:
             zr, mean_g, invstd_g = stats[i]
-            b = K.bn_act_bwd(zr, K.rows(dy), mean_g, invstd_g, P[kbn + ".weight"], P[kbn + ".bias"], train)
+            b = K.bn_act_bwd(zr, K.rows(dy), mean_g, invstd_g, P[kbn + ".weight"], P[kbn + ".bias"], bn_of(kbn)[0])
             und, total = und + int(b["und"].sum()), total + b["und"].numel()
             for k_, v in K.bn_bwd_ratios(K.rows(nchw64(t["dz"])), t["dgamma"], t["dbeta"], b).items():
                 w.add(k_, op.out, v)
             assert torch.equal(pg[id(named[kbn + ".weight"])], t["dgamma"]) and torch.equal(pg[id(named[kbn + ".bias"])], t["dbeta"])
-            if op.res is not None:
+            if "res_after" in walk[i]:
                 want = t["dy"] if "res_before" not in t else (t["res_before"].double() + t["dy"].double()).float()
                 assert torch.equal(t["res_after"], want), op.out       # one fp32 add per element: exact
                 contribute(op.res, t["res_after"])
         dz = r(nchw64(t["dz"]))
         xin = r(conv_in(op))
-        ref, sc = K.conv_wgrad(xin, P[kw].shape, dz, st)
-        w.add("dw", op.out, K.conv_ratio(t["dw"], ref, sc))
-        assert torch.equal(pg[id(named[kw])].view_as(t["dw"]), t["dw"])
+        if "dw" in walk[i]:
+            ref, sc = K.conv_wgrad(xin, P[kw].shape, dz, st)
+            w.add("dw", op.out, K.conv_ratio(t["dw"], ref, sc))
+            assert torch.equal(pg[id(named[kw])].view_as(t["dw"]), t["dw"])
         if op.src == "x":
             assert "dx_after" not in t and "dcat" not in t
+            continue
+        if not walk[i] & {"dx_after", "dcat"}:                         # no input is needed: no dgrad ran
             continue
         ref, sc = K.conv_dgrad(xin.shape, r(P[kw]), dz, st)
         if op.cin_up == 0:
@@ -187,13 +209,17 @@ def check_step(net, sd, run, pg, train, what):
             if "dlow_before" in t:
                 base = nchw64(t["dlow_before"])
                 rl, sl = rl + base, sl + base.abs()
-            w.add("dlow", op.out, K.ratio(nchw64(t["dlow_after"]), rl, K.BN_BAR * sl + 1e-30))
-            if "dtail_before" in t:
-                rt = (nchw64(t["dtail_before"]) + rt).float().double()
-            assert torch.equal(nchw64(t["dtail_after"]), rt), op.out   # a copy or one fp32 add: exact
-            contribute(op.src2, t["dlow_after"])
-            contribute(op.src, t["dtail_after"])
-    assert len(pg) == len(named) == 75 + 2 * 72 + 3
+            if "dlow_after" in walk[i]:
+                w.add("dlow", op.out, K.ratio(nchw64(t["dlow_after"]), rl, K.BN_BAR * sl + 1e-30))
+                contribute(op.src2, t["dlow_after"])
+            if "dtail_after" in walk[i]:
+                if "dtail_before" in t:
+                    rt = (nchw64(t["dtail_before"]) + rt).float().double()
+                assert torch.equal(nchw64(t["dtail_after"]), rt), op.out   # a copy or one fp32 add: exact
+                contribute(op.src, t["dtail_after"])
+    assert set(pg) == want_pg                                          # exactly the gradients of the walked ops' parameters
+    if state is None:
+        assert len(pg) == len(named) == 75 + 2 * 72 + 3
     share = und / max(total, 1)
     print("%s: %d of %d BN elements undecided at the kink (%.3g)" % (what, und, total, share))
     assert share <= K.KINK_SHARE

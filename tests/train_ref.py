@@ -17,19 +17,35 @@ def param_names(sd):
     return [k for k in sd if not k.endswith(("running_mean", "running_var", "num_batches_tracked"))]
 
 
-def forward(sd, x, train=True, dtype=torch.float64, frozen_backbone=False):
-    """-> (logits [3 x [B, 3(5+C), h, w]], leaf parameters {name: tensor}, running statistics after the step {prefix: (mean, var)})."""
+def leaf_params(sd, dtype, frozen_backbone=False, state=None):
+    """The parameters as leaves {name: tensor}: all trainable (but the backbone with frozen_backbone), or as `state.trainable` says."""
     P = {}
     for k in param_names(sd):
         t = sd[k].detach().to(dtype).clone()
-        P[k] = t.requires_grad_(not (frozen_backbone and k.startswith("feature.")))
+        P[k] = t.requires_grad_(state.trainable(k) if state is not None else not (frozen_backbone and k.startswith("feature.")))
+    return P
+
+
+def bn_args(prefix, train, state=None):
+    """F.batch_norm's training, momentum and eps for the conv_bn_relu `prefix`: nn.BatchNorm2d's defaults in the mode `train`, or
+    what `state.bn(prefix)` says (tests/train_states.py; momentum None is the cumulative average 1 / (num_batches_tracked + 1))."""
+    if state is None:
+        return dict(training=train, momentum=0.1, eps=1e-5)
+    training, momentum, eps, nbt = state.bn(prefix)
+    return dict(training=training, momentum=1.0 / (nbt + 1) if momentum is None else momentum, eps=eps)
+
+
+def forward(sd, x, train=True, dtype=torch.float64, frozen_backbone=False, state=None):
+    """-> (logits [3 x [B, 3(5+C), h, w]], leaf parameters {name: tensor}, running statistics after the step {prefix: (mean, var)}).
+    With a `state` (tests/train_states.py) it, not train / frozen_backbone, says what is trainable and how each BatchNorm runs."""
+    P = leaf_params(sd, dtype, frozen_backbone, state)
     running = {}
 
     def cbr(prefix, h, stride=1):
         w = P[prefix + ".conv.weight"]
         z = F.conv2d(h, w, stride=stride, padding=(w.shape[-1] - 1) // 2)
         rm, rv = sd[prefix + ".bn.running_mean"].to(dtype).clone(), sd[prefix + ".bn.running_var"].to(dtype).clone()
-        y = F.batch_norm(z, rm, rv, P[prefix + ".bn.weight"], P[prefix + ".bn.bias"], training=train, momentum=0.1, eps=1e-5)
+        y = F.batch_norm(z, rm, rv, P[prefix + ".bn.weight"], P[prefix + ".bn.bias"], **bn_args(prefix, train, state))
         running[prefix] = (rm, rv)
         return F.leaky_relu(y, 0.1)
 
@@ -65,13 +81,15 @@ def head_losses(logits, target, img_dim_h, num_class):
                         img_dim_h, num_class) for k, lg in enumerate(logits)]
 
 
-def run(sd, x, target, num_class, train=True, dtype=torch.float64, frozen_backbone=False, logits_and_params=None):
+def run(sd, x, target, num_class, train=True, dtype=torch.float64, frozen_backbone=False, logits_and_params=None, state=None):
     """One step -> dict(loss, stats (the reference's 9 values summed over the heads, nCorrect/nGT), res (per head), grads, running)."""
     x = torch.as_tensor(x)
     B, img_dim_h = x.shape[0], x.shape[2]
-    logits, P, running = logits_and_params or forward(sd, x, train, dtype, frozen_backbone)
+    logits, P, running = logits_and_params or forward(sd, x, train, dtype, frozen_backbone, state)
     res = head_losses(logits, target, img_dim_h, num_class)
-    torch.autograd.backward(logits, [torch.from_numpy(r["grad"]).to(dtype) for r in res])
+    # (every head, unless a state leaves nothing trainable upstream of one)
+    heads = [(lg, torch.from_numpy(r["grad"]).to(dtype)) for lg, r in zip(logits, res) if lg.requires_grad]
+    torch.autograd.backward([lg for lg, _ in heads], [g for _, g in heads])
     stats = [sum(R.stats_tuple(r, B)[i] for r in res) for i in range(9)]
     return dict(loss=float(sum(float(r["sums"].sum()) for r in res)), stats=stats, res=res,
                 grads={k: (p.grad.detach() if p.grad is not None else None) for k, p in P.items()},

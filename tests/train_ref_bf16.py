@@ -48,19 +48,16 @@ def rounded_conv(rounding=True):
     return conv
 
 
-def forward(sd, x, train=True, dtype=torch.float64, frozen_backbone=False, conv=None):
+def forward(sd, x, train=True, dtype=torch.float64, frozen_backbone=False, conv=None, state=None):
     """train_ref.forward with `conv(h, w, bias, stride)` in place of F.conv2d (default: the bf16-rounding conv)."""
     conv = conv or rounded_conv(True)
-    P = {}
-    for k in param_names(sd):
-        t = sd[k].detach().to(dtype).clone()
-        P[k] = t.requires_grad_(not (frozen_backbone and k.startswith("feature.")))
+    P = T.leaf_params(sd, dtype, frozen_backbone, state)
     running = {}
 
     def cbr(prefix, h, stride=1):
         z = conv(h, P[prefix + ".conv.weight"], None, stride)
         rm, rv = sd[prefix + ".bn.running_mean"].to(dtype).clone(), sd[prefix + ".bn.running_var"].to(dtype).clone()
-        y = F.batch_norm(z, rm, rv, P[prefix + ".bn.weight"], P[prefix + ".bn.bias"], training=train, momentum=0.1, eps=1e-5)
+        y = F.batch_norm(z, rm, rv, P[prefix + ".bn.weight"], P[prefix + ".bn.bias"], **T.bn_args(prefix, train, state))
         running[prefix] = (rm, rv)
         return F.leaky_relu(y, 0.1)
 
@@ -90,8 +87,8 @@ def forward(sd, x, train=True, dtype=torch.float64, frozen_backbone=False, conv=
     return [l1, l2, l3], P, running
 
 
-def run(sd, x, target, num_class, train=True, dtype=torch.float64, frozen_backbone=False, rounding=True):
+def run(sd, x, target, num_class, train=True, dtype=torch.float64, frozen_backbone=False, rounding=True, state=None):
     """One BF16 step (rounding = False: the F32 step) -> train_ref.run's dict."""
     x = torch.as_tensor(x)
-    fw = forward(sd, x, train, dtype, frozen_backbone, conv=rounded_conv(rounding))
+    fw = forward(sd, x, train, dtype, frozen_backbone, conv=rounded_conv(rounding), state=state)
     return T.run(sd, x, target, num_class, train=train, dtype=dtype, frozen_backbone=frozen_backbone, logits_and_params=fw)

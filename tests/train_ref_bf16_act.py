@@ -33,21 +33,18 @@ class _RoundST(torch.autograd.Function):
         return g
 
 
-def forward(sd, x, train=True, dtype=torch.float64, frozen_backbone=False, act_rounding=True, x_requires_grad=False):
+def forward(sd, x, train=True, dtype=torch.float64, frozen_backbone=False, act_rounding=True, x_requires_grad=False, state=None):
     """train_ref_bf16.forward with the stored activations rounded -> (logits, leaf parameters, running statistics after the step);
     with x_requires_grad the input is a leaf too, returned under the key "x" of the parameters."""
     conv = TB.rounded_conv(True)
     st = _RoundST.apply if act_rounding else (lambda t: t)
-    P = {}
-    for k in param_names(sd):
-        t = sd[k].detach().to(dtype).clone()
-        P[k] = t.requires_grad_(not (frozen_backbone and k.startswith("feature.")))
+    P = T.leaf_params(sd, dtype, frozen_backbone, state)
     running = {}
 
     def cbr(prefix, h, stride=1, res=None):
         zb = st(conv(h, P[prefix + ".conv.weight"], None, stride))
         rm, rv = sd[prefix + ".bn.running_mean"].to(dtype).clone(), sd[prefix + ".bn.running_var"].to(dtype).clone()
-        y = F.batch_norm(zb, rm, rv, P[prefix + ".bn.weight"], P[prefix + ".bn.bias"], training=train, momentum=0.1, eps=1e-5)
+        y = F.batch_norm(zb, rm, rv, P[prefix + ".bn.weight"], P[prefix + ".bn.bias"], **T.bn_args(prefix, train, state))
         running[prefix] = (rm, rv)
         y = F.leaky_relu(y, 0.1)
         return st(y if res is None else y + res)
@@ -83,8 +80,9 @@ def forward(sd, x, train=True, dtype=torch.float64, frozen_backbone=False, act_r
     return [l1, l2, l3], P, running
 
 
-def run(sd, x, target, num_class, train=True, dtype=torch.float64, frozen_backbone=False, act_rounding=True, x_requires_grad=False):
+def run(sd, x, target, num_class, train=True, dtype=torch.float64, frozen_backbone=False, act_rounding=True, x_requires_grad=False,
+        state=None):
     """One BF16_ACT step (act_rounding = False: the BF16 step) -> train_ref.run's dict; grads["x"] with x_requires_grad."""
     x = torch.as_tensor(x)
-    fw = forward(sd, x, train, dtype, frozen_backbone, act_rounding, x_requires_grad)
+    fw = forward(sd, x, train, dtype, frozen_backbone, act_rounding, x_requires_grad, state)
     return T.run(sd, x, target, num_class, train=train, dtype=dtype, frozen_backbone=frozen_backbone, logits_and_params=fw)
