@@ -17,7 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from tests import train_kernel_ref as K
-from yolo_v3_amd import _ffi
+from yolo_v3_amd import _ffi, backprop, F32, BF16
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -132,10 +132,8 @@ def test_conv_edges(case, math):
         ref_wd[:, :, :cout] = wr.permute(1, 2, 3, 0).reshape(cin, k * k, cout)
         assert torch.equal(wf[:nwp].cpu(), ref_wf.view(torch.int16).reshape(-1))
         assert torch.equal(wdd[:nwp].cpu(), ref_wd.view(torch.int16).reshape(-1))
-    fwd = lib.yv3_train_conv_fwd_bf16 if bf else lib.yv3_train_conv_fwd
-    dgrad = lib.yv3_train_conv_dgrad_bf16 if bf else lib.yv3_train_conv_dgrad
-    wgrad = lib.yv3_train_conv_wgrad_bf16 if bf else lib.yv3_train_conv_wgrad
-    wbytes = lib.yv3_train_conv_wgrad_bf16_workspace_bytes if bf else lib.yv3_train_conv_wgrad_workspace_bytes
+    m = backprop.MATH[BF16 if bf else F32]
+    fwd, dgrad, wgrad, wbytes = (backprop.entry(lib, n) for n in (m.conv_fwd_head, m.conv_dgrad, m.conv_wgrad, m.conv_wgrad_ws))
     worst = {}
     # forward (with the bias and with it NULL where the case has one)
     nz = B * Ho * Wo * cout

@@ -28,7 +28,7 @@ sys.path.insert(0, REPO)
 from tests import train_ref as T                      # noqa: E402
 from tests import yolo_loss_ref as R                  # noqa: E402
 from tests.helpers import trained_like_stream         # noqa: E402
-from yolo_v3_amd import YoloNet, WeightManager, synth, arch, _ffi, F32, BF16, BF16_ACT  # noqa: E402
+from yolo_v3_amd import YoloNet, WeightManager, synth, arch, backprop, _ffi, F32, BF16, BF16_ACT  # noqa: E402
 
 MATH = {"f32": F32, "bf16": BF16, "bf16_act": BF16_ACT}
 
@@ -97,7 +97,8 @@ def event_ms(launch, n_buffers, reps=50):
 def conv0_dgrad_alone(B, math, size=416, cout=32):
     """The input-gradient kernel and layer 0's wgrad on [B, size, size, cout] dz -> dict of times and the dgrad's rate."""
     lib, s = _ffi.lib(), _ffi.stream_ptr()
-    bf = math in (BF16, BF16_ACT)
+    m = backprop.MATH[math]
+    bf = m.bf16_operands
     dz_bytes = B * size * size * cout * (2 if bf else 4)
     dx_bytes = B * 3 * size * size * 4
     nbuf = max(2, -(-600 * 2 ** 20 // dz_bytes))
@@ -107,9 +108,8 @@ def conv0_dgrad_alone(B, math, size=416, cout=32):
     xin = x.to(torch.bfloat16) if bf else x
     w = torch.randn(cout, 3, 3, 3, device=DEV, generator=g) / 27 ** 0.5
     dx, dw = torch.empty_like(x), torch.empty_like(w)
-    dgrad = lib.yv3_train_conv0_dgrad_bf16 if bf else lib.yv3_train_conv0_dgrad
-    wgrad = lib.yv3_train_conv_wgrad_bf16 if bf else lib.yv3_train_conv_wgrad
-    nw = (lib.yv3_train_conv_wgrad_bf16_workspace_bytes if bf else lib.yv3_train_conv_wgrad_workspace_bytes)(B, size, size, 3, cout, 3, 1)
+    dgrad, wgrad = backprop.entry(lib, m.conv0_dgrad), backprop.entry(lib, m.conv_wgrad)
+    nw = backprop.entry(lib, m.conv_wgrad_ws)(B, size, size, 3, cout, 3, 1)
     ws = torch.empty(nw, device=DEV, dtype=torch.uint8)
     t_d = event_ms(lambda i: _ffi.check(dgrad(dzs[i].data_ptr(), w.data_ptr(), dx.data_ptr(), B, size, size, cout, s)), nbuf)
     t_w = event_ms(lambda i: _ffi.check(wgrad(xin.data_ptr(), None, dzs[i].data_ptr(), dw.data_ptr(), B, size, size, 3, 0, cout, 3, 1, 1,

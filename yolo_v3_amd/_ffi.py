@@ -158,19 +158,13 @@ _SIGNATURES = {
     "yv3_train_add": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p]),
     "yv3_train_upcat_bwd": (c_int, [c_void_p] * 3 + [c_int] * 7 + [c_void_p]),
     "yv3_train_to_bf16": (c_int, [c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p]),
-    "yv3_train_pack_weight_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "yv3_train_conv_fwd_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
-    "yv3_train_conv_dgrad_bf16": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 8 + [c_void_p]),
-    "yv3_train_conv0_dgrad_bf16": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
-    "yv3_train_conv_wgrad_bf16_workspace_bytes": (c_size_t, [c_int] * 7),
-    "yv3_train_conv_wgrad_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_size_t, c_void_p]),
     "yv3_train_conv_fwd_bf16o": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
-    "yv3_train_channel_bf16_workspace_bytes": (c_size_t, [c_longlong, c_int]),
-    "yv3_train_bn_stats_bf16": (c_int, [c_void_p, c_longlong, c_int, c_float, c_float] + [c_void_p] * 7 + [c_size_t, c_void_p]),
-    "yv3_train_bn_act_fwd_bf16": (c_int, [c_void_p] * 7 + [c_longlong, c_int, c_void_p]),
-    "yv3_train_bn_act_bwd_bf16": (c_int, [c_void_p] * 9 + [c_longlong, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "yv3_train_bias_bwd_bf16": (c_int, [c_void_p] * 4 + [c_longlong, c_int, c_void_p, c_size_t, c_void_p]),
 }
+# a _bf16 twin takes its base entry's arguments, with bf16 tensors where the base has fp32 ones (all void* here)
+_SIGNATURES.update({twin: _SIGNATURES[twin.replace("_bf16", "")] for twin in (
+    "yv3_train_pack_weight_bf16", "yv3_train_conv_fwd_bf16", "yv3_train_conv_dgrad_bf16", "yv3_train_conv0_dgrad_bf16",
+    "yv3_train_conv_wgrad_bf16_workspace_bytes", "yv3_train_conv_wgrad_bf16", "yv3_train_channel_bf16_workspace_bytes",
+    "yv3_train_bn_stats_bf16", "yv3_train_bn_act_fwd_bf16", "yv3_train_bn_act_bwd_bf16", "yv3_train_bias_bwd_bf16")})
 
 EXPORTS = tuple(_SIGNATURES)
 _lib = None

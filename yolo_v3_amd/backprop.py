@@ -1,22 +1,23 @@
 """Backpropagation of YoloNet's loss into every parameter (reference train.py: ``loss = net(inp, labels); loss.backward()``).
 
-``net.backprop = True`` routes ``net(x, target)`` here.  ``net.backprop_math`` picks the arithmetic of the convolutions (``net.math_mode``
-governs inference only): ``F32`` (the default) runs the step in exact fp32 on the kernels of csrc/train.hip; ``BF16`` rounds the two
-operands of every convolution product to bf16 (forward: x and w; dgrad: dz and w; wgrad: x and dz) and accumulates in fp32 on the
-kernels of csrc/train_bf16.hip, with z, dx and dw in fp32 and everything else exactly as in F32.  The steps below name the F32 calls;
-BF16 uses their ``_bf16`` counterparts and keeps a bf16 copy (yv3_train_to_bf16) of each conv input and each dz beside the fp32 one.
-``BF16_ACT`` is the BF16 step with every conv_bn_relu activation stored once, in bf16, and no fp32 twin: the conv writes
-``zb = bf16(z)`` (yv3_train_conv_fwd_bf16o), the statistics and both BatchNorm passes read zb, the layer output is
-``bf16(leaky(bn(zb)) [+ res])`` (yv3_train_bn_act_fwd_bf16), and the BatchNorm / bias backward writes dz as bf16
-(yv3_train_bn_act_bwd_bf16, yv3_train_bias_bwd_bf16).  The head logits, dy / dx, parameters, gradients and statistics stay fp32; a
-rounding's gradient is the identity.  The steps:
+``net.backprop = True`` routes ``net(x, target)`` here.  ``net.backprop_math`` picks the arithmetic of the step (``net.math_mode``
+governs inference only).  ``MATH`` holds one record per value: the library entry points the step calls, by name, and the few facts
+about its buffers that differ; ``net_forward`` and ``walk`` call every kernel from one place, through the record.  ``F32`` (the
+default) is exact fp32 on the kernels of csrc/train.hip.  ``BF16`` rounds the two operands of every convolution product to bf16
+(forward: x and w; dgrad: dz and w; wgrad: x and dz) and accumulates in fp32 on the kernels of csrc/train_bf16.hip; z, dx and dw
+are fp32 and everything else is F32's; the bf16 operands are copies (yv3_train_to_bf16) of each conv input and each dz beside the
+fp32 ones.  ``BF16_ACT`` is the BF16 step with every conv_bn_relu activation stored once, in bf16, and no fp32 twin: the conv writes
+``zb = bf16(z)``, the statistics and both BatchNorm passes read zb, the layer output is ``bf16(leaky(bn(zb)) [+ res])``, and the
+BatchNorm / bias backward writes dz as bf16 (csrc/train_bf16_act.hip).  The head logits, dy / dx, parameters, gradients and
+statistics stay fp32; a rounding's gradient is the identity.  The steps, by the record's fields:
 
-* forward: each conv_bn_relu is ``z = conv(x, w)`` (yv3_train_conv_fwd), the BatchNorm statistics (yv3_train_bn_stats: the batch's
-  mean and biased variance in ``.train()``, the running statistics in ``.eval()``) and ``y = leaky(bn(z)) [+ residual]``
-  (yv3_train_bn_act_fwd); a head conv is ``z = conv(x, w) + b``; the loss and dL/dlogits come from yv3_yolo_loss;
-* backward, in reverse order: dz from dy (yv3_train_bn_act_bwd, or yv3_train_bias_bwd for a head), dw (yv3_train_conv_wgrad)
-  and dx (yv3_train_conv_dgrad, plus yv3_train_upcat_bwd after an upsample).  Gradients of activations that fan out -- residual
-  skips, the route tails (Darknet layers 36 and 61) and the route heads -- are summed in a fixed order (yv3_train_add).
+* forward: each conv_bn_relu is ``z = conv(x, w)`` (pack_weight, conv_fwd), the BatchNorm statistics (bn_stats: the batch's
+  mean and biased variance in ``.train()``; yv3_train_bn_eval_stats: the running statistics in ``.eval()``) and
+  ``y = leaky(bn(z)) [+ residual]`` (bn_act_fwd); a head conv is ``z = conv(x, w) + b`` (conv_fwd_head); the loss and dL/dlogits
+  come from yv3_yolo_loss;
+* backward, in reverse order: dz from dy (bn_act_bwd, or bias_bwd for a head), dw (conv_wgrad) and dx (conv_dgrad, plus
+  yv3_train_upcat_bwd after an upsample).  Gradients of activations that fan out -- residual skips, the route tails (Darknet
+  layers 36 and 61) and the route heads -- are summed in a fixed order (yv3_train_add).
 
 One ``torch.autograd.Function`` covers the whole network: it takes the input and the parameters (``net.parameters()`` order, i.e.
 ``state_dict`` order without the buffers) and keeps z, y and the statistics of every layer for the backward.  Backward stops at the
@@ -29,9 +30,10 @@ heads' logits come out as NCHW views, and the walk starts from whatever gradient
 in torch on the logits (``net.yoloK(lgK, img_dim, target)`` included) trains the net.
 
 The input gradient is opt-in (``net.input_grad = True``; an ``x`` that requires grad raises NotImplementedError otherwise).  The
-walk then runs down to layer 0, whose dgrad (yv3_train_conv0_dgrad) writes dL/dx in x's own NCHW layout, and ``x`` is a real input
+walk then runs down to layer 0, whose dgrad (conv0_dgrad) writes dL/dx in x's own NCHW layout, and ``x`` is a real input
 of the Function."""
 import numbers
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -98,10 +100,50 @@ def _round8(c):
     return (c + 7) & ~7
 
 
+# What one net.backprop_math value fixes.  ENTRIES name the library's entry points: the weight pack, the conv forward of a
+# conv_bn_relu and of a head, dgrad, layer 0's dgrad, wgrad and its workspace query, the per-channel kernels' workspace query and
+# those kernels.  The facts: act_dtype, how a conv_bn_relu's z and output are stored (int16: as bf16 only, in bufs_b); bf16_operands,
+# whether the convs read bf16 tensors (run.bufs_b) or the fp32 ones (run.bufs); cast_twins, whether those are cast copies
+# (yv3_train_to_bf16) of each fp32 output and dz -- without it they are born in bf16; pad, cout -> the channels of a dz row and of a
+# packed weight's outputs.
+_Math = namedtuple("_Math", "pack_weight conv_fwd conv_fwd_head conv_dgrad conv0_dgrad conv_wgrad conv_wgrad_ws channel_ws bn_stats "
+                            "bn_act_fwd bn_act_bwd bias_bwd act_dtype bf16_operands cast_twins pad")
+ENTRIES = _Math._fields[:12]
+MATH = {_ffi.F32: _Math(                     # net.backprop_math -> its _Math
+    pack_weight="yv3_train_pack_weight", conv_fwd="yv3_train_conv_fwd", conv_fwd_head="yv3_train_conv_fwd",
+    conv_dgrad="yv3_train_conv_dgrad", conv0_dgrad="yv3_train_conv0_dgrad", conv_wgrad="yv3_train_conv_wgrad",
+    conv_wgrad_ws="yv3_train_conv_wgrad_workspace_bytes", channel_ws="yv3_train_channel_workspace_bytes",
+    bn_stats="yv3_train_bn_stats", bn_act_fwd="yv3_train_bn_act_fwd", bn_act_bwd="yv3_train_bn_act_bwd", bias_bwd="yv3_train_bias_bwd",
+    act_dtype=torch.float32, bf16_operands=False, cast_twins=False, pad=int)}
+MATH[_ffi.BF16] = MATH[_ffi.F32]._replace(
+    pack_weight="yv3_train_pack_weight_bf16", conv_fwd="yv3_train_conv_fwd_bf16", conv_fwd_head="yv3_train_conv_fwd_bf16",
+    conv_dgrad="yv3_train_conv_dgrad_bf16", conv0_dgrad="yv3_train_conv0_dgrad_bf16", conv_wgrad="yv3_train_conv_wgrad_bf16",
+    conv_wgrad_ws="yv3_train_conv_wgrad_bf16_workspace_bytes", bf16_operands=True, cast_twins=True, pad=_round8)
+MATH[_ffi.BF16_ACT] = MATH[_ffi.BF16]._replace(
+    conv_fwd="yv3_train_conv_fwd_bf16o", channel_ws="yv3_train_channel_bf16_workspace_bytes", bn_stats="yv3_train_bn_stats_bf16",
+    bn_act_fwd="yv3_train_bn_act_fwd_bf16", bn_act_bwd="yv3_train_bn_act_bwd_bf16", bias_bwd="yv3_train_bias_bwd_bf16",
+    act_dtype=torch.int16, cast_twins=False)
+# an entry point whose arguments differ from its field's other entries, brought to their form (a conv_bn_relu has no bias)
+_ADAPT = {"yv3_train_conv_fwd_bf16o": lambda f: lambda x, x2, wf, bias, zb, *shape: f(x, x2, wf, zb, *shape)}
+
+
+def entry(lib, name):
+    """The library function behind an entry point of a _Math, taking the arguments of its field."""
+    return _ADAPT.get(name, lambda f: f)(getattr(lib, name))
+
+
+def _call(lib, name, *args, what=None):
+    _ffi.check(entry(lib, name)(*args), what or name)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
 def backprop_math(net):
     """net.backprop_math, checked: F32, BF16 or BF16_ACT, else Yv3Error (YV3_EINVAL)."""
     m = getattr(net, "backprop_math", _ffi.F32)
-    if not isinstance(m, numbers.Integral) or isinstance(m, bool) or m not in (_ffi.F32, _ffi.BF16, _ffi.BF16_ACT):
+    if not isinstance(m, numbers.Integral) or isinstance(m, bool) or m not in MATH:
         err = _ffi.Yv3Error("net.backprop_math must be yolo_v3_amd.F32, yolo_v3_amd.BF16 or yolo_v3_amd.BF16_ACT, got %r" % (m,))
         err.code = _ffi.EINVAL
         raise err
@@ -111,7 +153,7 @@ def backprop_math(net):
 def _bf16(lib, s, t, rows, C, ld, what):
     """A bf16 copy (int16 storage) of the fp32 tensor t seen as rows x C, padded with zero channels to ld."""
     out = torch.empty(rows * ld, device=t.device, dtype=torch.int16)
-    _ffi.check(lib.yv3_train_to_bf16(t.data_ptr(), out.data_ptr(), rows, C, ld, s), "yv3_train_to_bf16 (%s)" % what)
+    _call(lib, "yv3_train_to_bf16", t.data_ptr(), out.data_ptr(), rows, C, ld, s, what="yv3_train_to_bf16 (%s)" % what)
     return out
 
 
@@ -136,116 +178,101 @@ def _ws(nbytes, dev):
     return torch.empty(nbytes, device=dev, dtype=torch.uint8)
 
 
+def _conv(lib, s, m, run, op, src, want_grad):
+    """z = conv(x, w) [+ bias] of one op on the conv operands `src` (bufs or bufs_b) -> (z, what the walk keeps of it)."""
+    c = op.conv
+    cin, cout, k, st = c.in_channels, c.out_channels, c.kernel_size[0], c.stride[0]
+    b_, h, w, ct = run.shape[op.src]
+    if ct + op.cin_up != cin:
+        raise _ffi.Yv3Error("%s: %d input channels, expected %d" % (op.out, ct + op.cin_up, cin))
+    ho, wo = (h + 2 * ((k - 1) // 2) - k) // st + 1, (w + 2 * ((k - 1) // 2) - k) // st + 1
+    wt, dev = _f32(c.weight, "weight of " + op.out), run.x.device
+    z = torch.empty((b_, ho, wo, cout), device=dev, dtype=torch.float32 if op.head else m.act_dtype)
+    bias = _f32(c.bias, "bias of " + op.out) if op.head else None
+    wf = torch.empty(m.pad(cout) * cin * k * k, device=dev, dtype=torch.int16 if m.bf16_operands else torch.float32)
+    wd = torch.empty_like(wf) if want_grad else None          # the dgrad's weight image
+    _call(lib, m.pack_weight, wt.data_ptr(), wf.data_ptr(), _ptr(wd), cout, cin, k, s)
+    x2 = src[op.src2] if op.src2 is not None else None
+    _call(lib, m.conv_fwd_head if op.head else m.conv_fwd, src[op.src].data_ptr(), _ptr(x2), wf.data_ptr(), _ptr(bias), z.data_ptr(),
+          b_, h, w, cin, op.cin_up, cout, k, st, int(op.src == "x"), s)
+    run.shape[op.out] = (b_, ho, wo, cout)
+    return z, dict(wd=wd, geo=(b_, h, w, cin, cout, k, st))
+
+
+def _bn_act(lib, s, m, op, z, res, sv):
+    """The BatchNorm statistics of z (.train(): the batch's, and the running ones move) and y = leaky(bn(z)) [+ res] -> y."""
+    bn, dev = op.bn, z.device
+    P, cout = z.numel() // z.shape[-1], z.shape[-1]
+    mean = torch.empty(cout, device=dev, dtype=torch.float32)
+    invstd = torch.empty_like(mean)
+    g, bt = _f32(bn.weight, "bn.weight of " + op.out), _f32(bn.bias, "bn.bias of " + op.out)
+    if bn.training:
+        rm, rv = _f32(bn.running_mean, "running_mean"), _f32(bn.running_var, "running_var")
+        with torch.no_grad():
+            bn.num_batches_tracked.add_(1)
+        mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+        rm_new, rv_new = torch.empty_like(rm), torch.empty_like(rv)
+        nb = entry(lib, m.channel_ws)(P, cout)
+        ws = _ws(nb, dev)
+        _call(lib, m.bn_stats, z.data_ptr(), P, cout, float(bn.eps), float(mom), rm.data_ptr(), rv.data_ptr(), rm_new.data_ptr(),
+              rv_new.data_ptr(), mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(), nb, s, what="yv3_train_bn_stats")
+        with torch.no_grad():          # (copy_ moves the buffers' _version: the inference engine re-packs)
+            bn.running_mean.copy_(rm_new)
+            bn.running_var.copy_(rv_new)
+    else:
+        _call(lib, "yv3_train_bn_eval_stats", bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.eps),
+              mean.data_ptr(), invstd.data_ptr(), cout, s)
+    y = torch.empty_like(z)
+    _call(lib, m.bn_act_fwd, z.data_ptr(), mean.data_ptr(), invstd.data_ptr(), g.data_ptr(), bt.data_ptr(), _ptr(res), y.data_ptr(),
+          P, cout, s, what="yv3_train_bn_act_fwd")
+    sv.update(mean=mean, invstd=invstd, gamma=g, beta=bt, train=int(bn.training))
+    return y
+
+
 def net_forward(run, want_grad):
     """The training forward of the whole net up to the heads -> their logits [(fp32 NHWC tensor, h, w)] * 3; with want_grad the
     run keeps what the walk needs."""
     lib, s = _ffi.lib(), _ffi.stream_ptr()
-    net, x = run.net, run.x
+    m, x = MATH[run.math], run.x
+    act = m.act_dtype == torch.int16           # activations in bf16 only: bufs holds x and the head logits, bufs_b the rest
     B, _, H, W = x.shape
-    dev = x.device
     bufs = {"x": x}
-    act = run.math == _ffi.BF16_ACT            # activations in bf16 only: bufs holds x and the head logits, bufs_b the rest
-    bf = act or run.math == _ffi.BF16
-    bufs_b = {"x": _bf16(lib, s, x, x.numel(), 1, 1, "x")} if bf else None      # bf16 conv inputs (BF16: copies of bufs' tensors)
+    bufs_b = {"x": _bf16(lib, s, x, x.numel(), 1, 1, "x")} if m.bf16_operands else None     # bf16 conv inputs
+    src = bufs_b if m.bf16_operands else bufs  # what the convs read
+    outs = bufs_b if act else bufs             # where a conv_bn_relu's output (a later op's residual) lives
     last = {}                                  # buffer -> index of the last op that reads it in the forward
     for i, op in enumerate(run.ops):
         last.update({b: i for b in (op.src, op.src2, op.res) if b is not None})
-    keep = set()                               # BF16_ACT: the bf16 buffers the walk reads (the inputs of a wgrad)
+    keep = set()                               # act: the bf16 buffers the walk reads (the inputs of a wgrad)
     run.shape["x"] = (B, H, W, 3)
     run.need["x"] = run.input_grad
     logits = [None] * 3
     for i, op in enumerate(run.ops):
         c = op.conv
-        cin, cout, k, st = c.in_channels, c.out_channels, c.kernel_size[0], c.stride[0]
-        b_, h, w, ct = run.shape[op.src]
-        if ct + op.cin_up != cin:
-            raise _ffi.Yv3Error("%s: %d input channels, expected %d" % (op.out, ct + op.cin_up, cin))
-        ho, wo = (h + 2 * ((k - 1) // 2) - k) // st + 1, (w + 2 * ((k - 1) // 2) - k) // st + 1
-        wt = _f32(c.weight, "weight of " + op.out)
         params = [c.weight] + ([c.bias] if op.head else [op.bn.weight, op.bn.bias])
         run.need[op.out] = any(p.requires_grad for p in params) or run.need[op.src] or \
             (op.src2 is not None and run.need[op.src2]) or (op.res is not None and run.need[op.res])
-        sv = {}
         if want_grad and c.weight.requires_grad:
             keep.update(b for b in (op.src, op.src2) if b is not None)
-        zb16 = act and not op.head
-        z = torch.empty((b_, ho, wo, cout), device=dev, dtype=torch.int16 if zb16 else torch.float32)
-        bias = _f32(c.bias, "bias of " + op.out) if op.head else None
-        if bf:
-            wf = torch.empty(_round8(cout) * cin * k * k, device=dev, dtype=torch.int16)
-            wd = torch.empty_like(wf) if want_grad else None
-            _ffi.check(lib.yv3_train_pack_weight_bf16(wt.data_ptr(), wf.data_ptr(), wd.data_ptr() if wd is not None else None,
-                                                      cout, cin, k, s), "yv3_train_pack_weight_bf16")
-            x2 = bufs_b[op.src2] if op.src2 is not None else None
-            if zb16:
-                _ffi.check(lib.yv3_train_conv_fwd_bf16o(bufs_b[op.src].data_ptr(), x2.data_ptr() if x2 is not None else None,
-                                                        wf.data_ptr(), z.data_ptr(), b_, h, w, cin, op.cin_up, cout, k, st,
-                                                        int(op.src == "x"), s), "yv3_train_conv_fwd_bf16o")
-            else:
-                _ffi.check(lib.yv3_train_conv_fwd_bf16(bufs_b[op.src].data_ptr(), x2.data_ptr() if x2 is not None else None,
-                                                       wf.data_ptr(), bias.data_ptr() if bias is not None else None, z.data_ptr(),
-                                                       b_, h, w, cin, op.cin_up, cout, k, st, int(op.src == "x"), s),
-                           "yv3_train_conv_fwd_bf16")
-        else:
-            wf = torch.empty(cout * cin * k * k, device=dev, dtype=torch.float32)
-            wd = torch.empty_like(wf) if want_grad else None
-            _ffi.check(lib.yv3_train_pack_weight(wt.data_ptr(), wf.data_ptr(), wd.data_ptr() if wd is not None else None,
-                                                 cout, cin, k, s), "yv3_train_pack_weight")
-            x2 = bufs[op.src2] if op.src2 is not None else None
-            _ffi.check(lib.yv3_train_conv_fwd(bufs[op.src].data_ptr(), x2.data_ptr() if x2 is not None else None, wf.data_ptr(),
-                                              bias.data_ptr() if bias is not None else None, z.data_ptr(), b_, h, w, cin, op.cin_up,
-                                              cout, k, st, int(op.src == "x"), s), "yv3_train_conv_fwd")
-        run.shape[op.out] = (b_, ho, wo, cout)
-        sv.update(wd=wd, geo=(b_, h, w, cin, cout, k, st))
+        z, sv = _conv(lib, s, m, run, op, src, want_grad)
         if op.head:
             bufs[op.out] = z
-            logits[op.head_idx] = (z, ho, wo)
+            logits[op.head_idx] = (z, z.shape[1], z.shape[2])
         else:
-            bn = op.bn
-            P = b_ * ho * wo
-            mean = torch.empty(cout, device=dev, dtype=torch.float32)
-            invstd = torch.empty_like(mean)
-            g, bt = _f32(bn.weight, "bn.weight of " + op.out), _f32(bn.bias, "bn.bias of " + op.out)
-            if bn.training:
-                rm, rv = _f32(bn.running_mean, "running_mean"), _f32(bn.running_var, "running_var")
-                with torch.no_grad():
-                    bn.num_batches_tracked.add_(1)
-                mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
-                rm_new, rv_new = torch.empty_like(rm), torch.empty_like(rv)
-                nb = (lib.yv3_train_channel_bf16_workspace_bytes if act else lib.yv3_train_channel_workspace_bytes)(P, cout)
-                ws = _ws(nb, dev)
-                stats = lib.yv3_train_bn_stats_bf16 if act else lib.yv3_train_bn_stats
-                _ffi.check(stats(z.data_ptr(), P, cout, float(bn.eps), float(mom), rm.data_ptr(), rv.data_ptr(),
-                                 rm_new.data_ptr(), rv_new.data_ptr(), mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(), nb, s),
-                           "yv3_train_bn_stats")
-                with torch.no_grad():          # (copy_ moves the buffers' _version: the inference engine re-packs)
-                    bn.running_mean.copy_(rm_new)
-                    bn.running_var.copy_(rv_new)
-            else:
-                _ffi.check(lib.yv3_train_bn_eval_stats(bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.eps),
-                                                       mean.data_ptr(), invstd.data_ptr(), cout, s), "yv3_train_bn_eval_stats")
-            y = torch.empty_like(z)
-            res = (bufs_b if act else bufs)[op.res] if op.res is not None else None
-            _ffi.check((lib.yv3_train_bn_act_fwd_bf16 if act else lib.yv3_train_bn_act_fwd)(
-                z.data_ptr(), mean.data_ptr(), invstd.data_ptr(), g.data_ptr(), bt.data_ptr(),
-                res.data_ptr() if res is not None else None, y.data_ptr(), P, cout, s), "yv3_train_bn_act_fwd")
-            if act:
-                bufs_b[op.out] = y
-                if not (want_grad and run.need[op.out]):       # no walk will reach this op
-                    z = None
-            else:
-                bufs[op.out] = y
-                if bf:                         # (every conv_bn_relu output is some conv's input)
-                    bufs_b[op.out] = _bf16(lib, s, y, P, cout, cout, op.out)
-            sv.update(z=z, mean=mean, invstd=invstd, gamma=g, beta=bt, train=int(bn.training))
+            y = _bn_act(lib, s, m, op, z, outs[op.res] if op.res is not None else None, sv)
+            outs[op.out] = y
+            if m.cast_twins:                   # (every conv_bn_relu output is some conv's input)
+                bufs_b[op.out] = _bf16(lib, s, y, y.numel() // y.shape[-1], y.shape[-1], y.shape[-1], op.out)
+            if act and not (want_grad and run.need[op.out]):              # no walk will reach this op
+                z = None
+            sv["z"] = z
         run.saved[i] = sv
         if act:                                # a bf16 buffer lives until its last reader: a later op, or a wgrad of the walk
             for b in {op.src, op.src2, op.res} - {None}:
                 if last[b] == i and b not in keep:
                     del bufs_b[b]
     if want_grad:
-        run.bufs = bufs
-        run.bufs_b = bufs_b
+        run.bufs, run.bufs_b = bufs, bufs_b
     return logits
 
 
@@ -272,134 +299,112 @@ def walk(run, dlogits, scale=None):
     """The reverse walk from the heads: dlogits[k] = dL/dlogits of head k (contiguous NHWC fp32, or None: that head got no gradient),
     times the fp32 0-d GPU tensor `scale` when one is given.  -> ({id(param): dL/dparam}, dL/dx [B,3,H,W] fp32 or None); the
     latter when run.need["x"]."""
-    lib, s = _ffi.lib(), _ffi.stream_ptr()
-    dev = run.x.device
-    act = run.math == _ffi.BF16_ACT
-    bf = act or run.math == _ffi.BF16
-    grads = {}                 # buffer -> dL/dbuffer (NHWC fp32; "x": NCHW)
-    pg = {}
-    trace = run.trace
+    lib, s, dev, m = _ffi.lib(), _ffi.stream_ptr(), run.x.device, MATH[run.math]
+    grads, pg = {}, {}         # buffer -> dL/dbuffer (NHWC fp32; "x": NCHW); id(param) -> dL/dparam
 
     def rec(i, **tensors):
-        if trace is not None:
-            trace.setdefault(i, {}).update({k: t.clone() for k, t in tensors.items() if t is not None})
+        if run.trace is not None:
+            run.trace.setdefault(i, {}).update({k: t.clone() for k, t in tensors.items() if t is not None})
 
     def give(i, buf, t):
         """Add t into the gradient of buf (takes ownership of t when buf has none yet)."""
         if buf in grads:
             rec(i, res_before=grads[buf])
-            _ffi.check(lib.yv3_train_add(t.data_ptr(), grads[buf].data_ptr(), t.numel(), s), "yv3_train_add")
+            _call(lib, "yv3_train_add", t.data_ptr(), grads[buf].data_ptr(), t.numel(), s)
         else:
             grads[buf] = t
         rec(i, res_after=grads[buf])
 
-    head_ops = {op.head_idx: op for op in run.ops if op.head}
-    for kk in range(3):
-        if dlogits[kk] is not None:
-            grads[head_ops[kk].out] = dlogits[kk]
+    def dz_of(i, op, sv, dy):
+        """dy -> the op's per-channel gradients (and its residual's) and (dz, dz as the convs read it: itself or a padded bf16 copy)."""
+        _, ho, wo, cout = run.shape[op.out]
+        P = sv["geo"][0] * ho * wo
+        nb = entry(lib, m.channel_ws)(P, cout)
+        ws = _ws(nb, dev)
+        # bf16 activations: dz is born in bf16, in the padded rows the dgrad / wgrad kernels read
+        dz = torch.empty(P * m.pad(cout), device=dev, dtype=torch.int16) if m.act_dtype == torch.int16 else torch.empty_like(dy)
+        if op.head:
+            db = torch.empty(cout, device=dev, dtype=torch.float32)
+            _call(lib, m.bias_bwd, dy.data_ptr(), _ptr(scale), dz.data_ptr(), db.data_ptr(), P, cout, ws.data_ptr(), nb, s,
+                  what="yv3_train_bias_bwd")
+            pg[id(op.conv.bias)] = db
+            rec(i, dz=dz, dbias=db)
+        else:
+            dgam, dbet = torch.empty(cout, device=dev, dtype=torch.float32), torch.empty(cout, device=dev, dtype=torch.float32)
+            _call(lib, m.bn_act_bwd, sv["z"].data_ptr(), dy.data_ptr(), sv["mean"].data_ptr(), sv["invstd"].data_ptr(),
+                  sv["gamma"].data_ptr(), sv["beta"].data_ptr(), dz.data_ptr(), dgam.data_ptr(), dbet.data_ptr(), P, cout, sv["train"],
+                  ws.data_ptr(), nb, s, what="yv3_train_bn_act_bwd")
+            pg[id(op.bn.weight)], pg[id(op.bn.bias)] = dgam, dbet
+            rec(i, dz=dz, dgamma=dgam, dbeta=dbet)
+            if op.res is not None and run.need[op.res]:
+                give(i, op.res, dy)    # y = act(...) + res: dres = dy (dy is not read again)
+        return dz, _bf16(lib, s, dz, P, cout, m.pad(cout), "dz of " + op.out) if m.cast_twins else dz
+
+    def wgrad(i, op, sv, dz):
+        b_, h, w, cin, cout, k, st = sv["geo"]
+        dw = torch.empty_like(op.conv.weight, dtype=torch.float32, memory_format=torch.contiguous_format)
+        nw = entry(lib, m.conv_wgrad_ws)(b_, h, w, cin, cout, k, st)
+        wsw = _ws(nw, dev)
+        src = run.bufs_b if m.bf16_operands else run.bufs            # what the convs read
+        x2 = src[op.src2] if op.src2 is not None else None
+        _call(lib, m.conv_wgrad, src[op.src].data_ptr(), _ptr(x2), dz.data_ptr(), dw.data_ptr(), b_, h, w, cin, op.cin_up, cout,
+              k, st, int(op.src == "x"), wsw.data_ptr(), nw, s)
+        pg[id(op.conv.weight)] = dw
+        rec(i, dw=dw)
+
+    def dgrad(i, op, sv, dz):
+        """dz into the gradients of those inputs of the op that need one."""
+        need_src, need_src2 = run.need[op.src], op.src2 is not None and run.need[op.src2]
+        if not (need_src or need_src2):
+            return
+        b_, h, w, cin, cout, k, st = sv["geo"]
+        if op.src == "x":                  # layer 0: dL/dx in the caller's NCHW layout, from the parameter itself
+            dx = torch.empty((b_, cin, h, w), device=dev, dtype=torch.float32)
+            wt = _f32(op.conv.weight, "weight of " + op.out)
+            _call(lib, m.conv0_dgrad, dz.data_ptr(), wt.data_ptr(), dx.data_ptr(), b_, h, w, cout, s)
+            grads["x"] = dx
+            rec(i, dx_after=dx)
+            return
+
+        def conv_dgrad(dx, acc):
+            _call(lib, m.conv_dgrad, dz.data_ptr(), sv["wd"].data_ptr(), dx.data_ptr(), b_, h, w, cin, cout, k, st, int(acc), s)
+
+        if op.cin_up == 0:
+            acc = op.src in grads
+            dx = grads[op.src] if acc else torch.empty((b_, h, w, cin), device=dev, dtype=torch.float32)
+            rec(i, dx_before=dx if acc else None)
+            conv_dgrad(dx, acc)
+            grads[op.src] = dx
+            rec(i, dx_after=dx)
+            return
+        dcat = torch.empty((b_, h, w, cin), device=dev, dtype=torch.float32)
+        conv_dgrad(dcat, False)
+        ct = cin - op.cin_up
+        dlow = dtail = None
+        acc_low = acc_tail = 0
+        if need_src2:
+            acc_low = int(op.src2 in grads)
+            dlow = grads[op.src2] if acc_low else torch.empty((b_, h // 2, w // 2, op.cin_up), device=dev, dtype=torch.float32)
+            grads[op.src2] = dlow
+        if need_src:
+            acc_tail = int(op.src in grads)
+            dtail = grads[op.src] if acc_tail else torch.empty((b_, h, w, ct), device=dev, dtype=torch.float32)
+            grads[op.src] = dtail
+        rec(i, dcat=dcat, dlow_before=dlow if acc_low else None, dtail_before=dtail if acc_tail else None)
+        _call(lib, "yv3_train_upcat_bwd", dcat.data_ptr(), _ptr(dlow), _ptr(dtail), b_, h, w, op.cin_up, ct, acc_low, acc_tail, s)
+        rec(i, dlow_after=dlow, dtail_after=dtail)
+
+    grads.update({op.out: dlogits[op.head_idx] for op in run.ops if op.head and dlogits[op.head_idx] is not None})
     for i in range(len(run.ops) - 1, -1, -1):
         op, sv = run.ops[i], run.saved[i]
         dy = grads.pop(op.out, None)
         if dy is None or not run.need[op.out]:
             continue
         rec(i, dy=dy)
-        b_, h, w, cin, cout, k, st = sv["geo"]
-        _, ho, wo, _ = run.shape[op.out]
-        P = b_ * ho * wo
-        nb = (lib.yv3_train_channel_bf16_workspace_bytes if act else lib.yv3_train_channel_workspace_bytes)(P, cout)
-        ws = _ws(nb, dev)
-        # BF16_ACT: dz is born in bf16, in the padded rows the dgrad / wgrad kernels read
-        dz = torch.empty(P * _round8(cout), device=dev, dtype=torch.int16) if act else torch.empty_like(dy)
-        c = op.conv
-        if op.head:
-            db = torch.empty(cout, device=dev, dtype=torch.float32)
-            _ffi.check((lib.yv3_train_bias_bwd_bf16 if act else lib.yv3_train_bias_bwd)(
-                dy.data_ptr(), scale.data_ptr() if scale is not None else None, dz.data_ptr(), db.data_ptr(), P, cout, ws.data_ptr(),
-                nb, s), "yv3_train_bias_bwd")
-            pg[id(c.bias)] = db
-            rec(i, dz=dz, dbias=db)
-        else:
-            dgam = torch.empty(cout, device=dev, dtype=torch.float32)
-            dbet = torch.empty_like(dgam)
-            _ffi.check((lib.yv3_train_bn_act_bwd_bf16 if act else lib.yv3_train_bn_act_bwd)(
-                sv["z"].data_ptr(), dy.data_ptr(), sv["mean"].data_ptr(), sv["invstd"].data_ptr(), sv["gamma"].data_ptr(),
-                sv["beta"].data_ptr(), dz.data_ptr(), dgam.data_ptr(), dbet.data_ptr(), P, cout, sv["train"], ws.data_ptr(), nb, s),
-                "yv3_train_bn_act_bwd")
-            pg[id(op.bn.weight)], pg[id(op.bn.bias)] = dgam, dbet
-            rec(i, dz=dz, dgamma=dgam, dbeta=dbet)
-            if op.res is not None and run.need[op.res]:
-                give(i, op.res, dy)         # y = act(...) + res: dres = dy (dy is not read again)
-        need_src = run.need[op.src]
-        need_src2 = op.src2 is not None and run.need[op.src2]
-        if bf:
-            dzb = dz if act else _bf16(lib, s, dz, P, cout, _round8(cout), "dz of " + op.out)
-        if c.weight.requires_grad:
-            dw = torch.empty_like(c.weight, dtype=torch.float32, memory_format=torch.contiguous_format)
-            if bf:
-                nw = lib.yv3_train_conv_wgrad_bf16_workspace_bytes(b_, h, w, cin, cout, k, st)
-                wsw = _ws(nw, dev)
-                x2 = run.bufs_b[op.src2] if op.src2 is not None else None
-                _ffi.check(lib.yv3_train_conv_wgrad_bf16(run.bufs_b[op.src].data_ptr(), x2.data_ptr() if x2 is not None else None,
-                                                         dzb.data_ptr(), dw.data_ptr(), b_, h, w, cin, op.cin_up, cout, k, st,
-                                                         int(op.src == "x"), wsw.data_ptr(), nw, s), "yv3_train_conv_wgrad_bf16")
-            else:
-                nw = lib.yv3_train_conv_wgrad_workspace_bytes(b_, h, w, cin, cout, k, st)
-                wsw = _ws(nw, dev)
-                x2 = run.bufs[op.src2] if op.src2 is not None else None
-                _ffi.check(lib.yv3_train_conv_wgrad(run.bufs[op.src].data_ptr(), x2.data_ptr() if x2 is not None else None,
-                                                    dz.data_ptr(), dw.data_ptr(), b_, h, w, cin, op.cin_up, cout, k, st,
-                                                    int(op.src == "x"), wsw.data_ptr(), nw, s), "yv3_train_conv_wgrad")
-            pg[id(c.weight)] = dw
-            rec(i, dw=dw)
-        if not (need_src or need_src2):
-            continue
-        if op.src == "x":                  # layer 0: dL/dx in the caller's NCHW layout, from the parameter itself
-            dx = torch.empty((b_, cin, h, w), device=dev, dtype=torch.float32)
-            wt = _f32(c.weight, "weight of " + op.out)
-            if bf:
-                _ffi.check(lib.yv3_train_conv0_dgrad_bf16(dzb.data_ptr(), wt.data_ptr(), dx.data_ptr(), b_, h, w, cout, s),
-                           "yv3_train_conv0_dgrad_bf16")
-            else:
-                _ffi.check(lib.yv3_train_conv0_dgrad(dz.data_ptr(), wt.data_ptr(), dx.data_ptr(), b_, h, w, cout, s),
-                           "yv3_train_conv0_dgrad")
-            grads["x"] = dx
-            rec(i, dx_after=dx)
-            continue
-
-        def dgrad(dx, acc):
-            if bf:
-                _ffi.check(lib.yv3_train_conv_dgrad_bf16(dzb.data_ptr(), sv["wd"].data_ptr(), dx.data_ptr(), b_, h, w, cin, cout, k, st,
-                                                         int(acc), s), "yv3_train_conv_dgrad_bf16")
-            else:
-                _ffi.check(lib.yv3_train_conv_dgrad(dz.data_ptr(), sv["wd"].data_ptr(), dx.data_ptr(), b_, h, w, cin, cout, k, st,
-                                                    int(acc), s), "yv3_train_conv_dgrad")
-
-        if op.cin_up == 0:
-            acc = op.src in grads
-            dx = grads[op.src] if acc else torch.empty((b_, h, w, cin), device=dev, dtype=torch.float32)
-            rec(i, dx_before=dx if acc else None)
-            dgrad(dx, acc)
-            grads[op.src] = dx
-            rec(i, dx_after=dx)
-        else:
-            dcat = torch.empty((b_, h, w, cin), device=dev, dtype=torch.float32)
-            dgrad(dcat, False)
-            ct = cin - op.cin_up
-            dlow = dtail = None
-            acc_low = acc_tail = 0
-            if need_src2:
-                acc_low = int(op.src2 in grads)
-                dlow = grads[op.src2] if acc_low else torch.empty((b_, h // 2, w // 2, op.cin_up), device=dev, dtype=torch.float32)
-                grads[op.src2] = dlow
-            if need_src:
-                acc_tail = int(op.src in grads)
-                dtail = grads[op.src] if acc_tail else torch.empty((b_, h, w, ct), device=dev, dtype=torch.float32)
-                grads[op.src] = dtail
-            rec(i, dcat=dcat, dlow_before=dlow if acc_low else None, dtail_before=dtail if acc_tail else None)
-            _ffi.check(lib.yv3_train_upcat_bwd(dcat.data_ptr(), dlow.data_ptr() if dlow is not None else None,
-                                               dtail.data_ptr() if dtail is not None else None, b_, h, w, op.cin_up, ct,
-                                               acc_low, acc_tail, s), "yv3_train_upcat_bwd")
-            rec(i, dlow_after=dlow, dtail_after=dtail)
+        dz, dzc = dz_of(i, op, sv, dy)          # (dz lives as long as its copy)
+        if op.conv.weight.requires_grad:
+            wgrad(i, op, sv, dzc)
+        dgrad(i, op, sv, dzc)
     return pg, grads.get("x")
 
 

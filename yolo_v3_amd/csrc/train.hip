@@ -11,14 +11,16 @@
 //
 // Determinism: no atomics.  Every sum runs in a fixed order (the MFMA k-chain, then the wgrad split partials and the per-channel
 // partials summed in index order in fp64), so identical inputs give identical bits.
+// These are net.backprop_math = F32's entry points (yolo_v3_amd/backprop.py's table MATH names each mode's).  train_conv.h holds
+// what the conv entry points share with train_bf16.hip's, train_channel.h the finalize kernels shared with train_bf16_act.hip.
 #include "yv3_common.h"
 #include "train_conv0_dgrad.h"
 #include "train_channel.h"
+#include "train_conv.h"
 
 namespace {
 
-constexpr int BM = 64, BN = 64, BK = 32, NT = 256;
-enum { FWD = 0, DGRAD = 1, WGRAD = 2 };
+constexpr int BM = 64, BN = 64, BK = 32;   // (NT = 256 threads: train_conv.h)
 
 struct Geo {
     const float* x;    // input (tail of the concatenation when cin_up > 0)
@@ -173,27 +175,11 @@ __global__ __launch_bounds__(NT) void conv_gemm(Geo g) {
     }
 }
 
-// dw[co][ci][kh][kw] = sum over the splits, in split order (fp64)
-__global__ void wgrad_reduce(const float* __restrict__ part, float* __restrict__ dw, int cout, int cin, int kk2, int split) {
-    const long long MN = (long long)cout * cin * kk2;
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= MN) return;
-    const int co = (int)(i / ((long long)cin * kk2));
-    const int r = (int)(i - (long long)co * cin * kk2);
-    const int ci = r / kk2, tap = r - ci * kk2;
-    const long long src = (long long)co * cin * kk2 + (long long)tap * cin + ci;
-    double s = 0.0;
-    for (int z = 0; z < split; ++z) s += (double)part[z * MN + src];
-    dw[i] = (float)s;
-}
-
 __global__ void pack_weight(const float* __restrict__ w, float* __restrict__ wf, float* __restrict__ wd, int cout, int cin, int kk2) {
     const long long n = (long long)cout * cin * kk2;
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int co = (int)(i / ((long long)cin * kk2));
-    const int r = (int)(i - (long long)co * cin * kk2);
-    const int ci = r / kk2, tap = r - ci * kk2;
+    YV3_WEIGHT_INDEX(i, cin, kk2);
     const float v = w[i];
     if (wf) wf[((long long)tap * cin + ci) * cout + co] = v;
     if (wd) wd[((long long)tap * cout + co) * cin + ci] = v;
@@ -310,26 +296,8 @@ __global__ void upcat_bwd(const float* __restrict__ dcat, float* __restrict__ dl
 }
 
 // ---- host side
-bool conv_shape_ok(int B, int H, int W, int cin, int cin_up, int cout, int k, int stride) {
-    if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || cin_up < 0) return false;
-    if (!(k == 1 || k == 3) || !(stride == 1 || stride == 2)) return false;
-    if (cin_up > 0 && (cin_up >= cin || (H & 1) || (W & 1))) return false;
-    return true;
-}
-
-Geo make_geo(int B, int H, int W, int cin, int cin_up, int cout, int k, int stride, int nchw) {
-    Geo g = {};
-    g.B = B; g.H = H; g.W = W; g.cin = cin; g.cin_up = cin_up; g.cout = cout; g.k = k; g.stride = stride; g.nchw = nchw;
-    g.pad = (k - 1) / 2;
-    g.Ho = (H + 2 * g.pad - k) / stride + 1;
-    g.Wo = (W + 2 * g.pad - k) / stride + 1;
-    return g;
-}
-
-int grid1(long long n) { long long b = (n + NT - 1) / NT; return (int)(b < 65536 ? (b > 0 ? b : 1) : 65536); }
-
 // the wgrad split over output pixels: a function of the shape only, so that the summation order never changes
-void wgrad_split(const Geo& g, long long M, long long N, long long K, int* split, long long* chunk) {
+void wgrad_split(long long M, long long N, long long K, int* split, long long* chunk) {
     const long long tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
     long long s = 2048 / tiles;
     if (s < 1) s = 1;
@@ -377,10 +345,8 @@ int yv3_train_pack_weight(const float* w, float* wf, float* wd, int cout, int ci
 
 int yv3_train_conv_fwd(const float* x, const float* x2, const float* wf, const float* bias, float* z,
                        int B, int H, int W, int cin, int cin_up, int cout, int k, int stride, int x_nchw, void* stream) {
-    if (!x || !wf || !z || (cin_up > 0 && !x2)) return YV3_EINVAL;
-    if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0) return YV3_EINVAL;
-    if (!conv_shape_ok(B, H, W, cin, cin_up, cout, k, stride) || (x_nchw && cin_up)) return YV3_ESHAPE;
-    Geo g = make_geo(B, H, W, cin, cin_up, cout, k, stride, x_nchw);
+    if (int rc = conv_check(x && wf && z && (cin_up <= 0 || x2), B, H, W, cin, cin_up, cout, k, stride, x_nchw)) return rc;
+    Geo g = make_geo<Geo>(B, H, W, cin, cin_up, cout, k, stride, x_nchw);
     g.x = x; g.x2 = x2; g.wp = wf; g.bias = bias; g.out = z;
     g.M = (long long)B * g.Ho * g.Wo; g.N = cout; g.K = (long long)k * k * cin;
     dim3 grid((unsigned)((g.M + BM - 1) / BM), (unsigned)((g.N + BN - 1) / BN));
@@ -391,10 +357,8 @@ int yv3_train_conv_fwd(const float* x, const float* x2, const float* wf, const f
 
 int yv3_train_conv_dgrad(const float* dz, const float* wd, float* dx, int B, int H, int W, int cin, int cout, int k, int stride,
                          int accumulate, void* stream) {
-    if (!dz || !wd || !dx) return YV3_EINVAL;
-    if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0) return YV3_EINVAL;
-    if (!conv_shape_ok(B, H, W, cin, 0, cout, k, stride)) return YV3_ESHAPE;
-    Geo g = make_geo(B, H, W, cin, 0, cout, k, stride, 0);
+    if (int rc = conv_check(dz && wd && dx, B, H, W, cin, 0, cout, k, stride, 0)) return rc;
+    Geo g = make_geo<Geo>(B, H, W, cin, 0, cout, k, stride, 0);
     g.dz = dz; g.wp = wd; g.out = dx; g.accumulate = accumulate;
     g.M = (long long)B * H * W; g.N = cin; g.K = (long long)k * k * cout;
     dim3 grid((unsigned)((g.M + BM - 1) / BM), (unsigned)((g.N + BN - 1) / BN));
@@ -410,25 +374,18 @@ int yv3_train_conv0_dgrad(const float* dz, const float* w, float* dx_nchw, int B
 }
 
 size_t yv3_train_conv_wgrad_workspace_bytes(int B, int H, int W, int cin, int cout, int k, int stride) {
-    if (!conv_shape_ok(B, H, W, cin, 0, cout, k, stride)) return 0;
-    Geo g = make_geo(B, H, W, cin, 0, cout, k, stride, 0);
-    int split; long long chunk;
-    const long long M = cout, N = (long long)k * k * cin, K = (long long)B * g.Ho * g.Wo;
-    wgrad_split(g, M, N, K, &split, &chunk);
-    return (size_t)split * M * N * sizeof(float);
+    return wgrad_workspace_bytes(wgrad_split, B, H, W, cin, cout, k, stride);
 }
 
 int yv3_train_conv_wgrad(const float* x, const float* x2, const float* dz, float* dw, int B, int H, int W, int cin, int cin_up,
                          int cout, int k, int stride, int x_nchw, void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !dz || !dw || !ws || (cin_up > 0 && !x2)) return YV3_EINVAL;
-    if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0) return YV3_EINVAL;
-    if (!conv_shape_ok(B, H, W, cin, cin_up, cout, k, stride) || (x_nchw && cin_up)) return YV3_ESHAPE;
+    if (int rc = conv_check(x && dz && dw && ws && (cin_up <= 0 || x2), B, H, W, cin, cin_up, cout, k, stride, x_nchw)) return rc;
     if (ws_bytes < yv3_train_conv_wgrad_workspace_bytes(B, H, W, cin, cout, k, stride)) return YV3_EWORKSPACE;
-    Geo g = make_geo(B, H, W, cin, cin_up, cout, k, stride, x_nchw);
+    Geo g = make_geo<Geo>(B, H, W, cin, cin_up, cout, k, stride, x_nchw);
     g.x = x; g.x2 = x2; g.dz = dz; g.out = (float*)ws;
     g.M = cout; g.N = (long long)k * k * cin; g.K = (long long)B * g.Ho * g.Wo;
     int split;
-    wgrad_split(g, g.M, g.N, g.K, &split, &g.kchunk);
+    wgrad_split(g.M, g.N, g.K, &split, &g.kchunk);
     dim3 grid((unsigned)((g.M + BM - 1) / BM), (unsigned)((g.N + BN - 1) / BN), (unsigned)split);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(conv_gemm<WGRAD>, grid, dim3(NT), 0, st, g);

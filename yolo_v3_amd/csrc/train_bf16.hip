@@ -1,6 +1,7 @@
-// BF16 training step (net.backprop_math = BF16): the convolution forward / dgrad / wgrad of csrc/train.hip with both operands rounded
-// to bf16 (round to nearest even) and the products accumulated in fp32 on v_mfma_f32_32x32x16_bf16.  Everything else of the step (the
-// BatchNorm statistics and backward, LeakyReLU, residual / route sums, upcat_bwd, the loss) stays on the fp32 kernels of train.hip.
+// The convolutions of net.backprop_math = BF16 and BF16_ACT (yolo_v3_amd/backprop.py's table MATH names each mode's entry points): the
+// forward / dgrad / wgrad of csrc/train.hip with both operands rounded to bf16 (round to nearest even) and the products accumulated in
+// fp32 on v_mfma_f32_32x32x16_bf16.  The rest of the step stays on the fp32 kernels of train.hip (BF16) or runs on train_bf16_act.hip's
+// (BF16_ACT).  train_conv.h holds what the entry points share with train.hip's; the kernels, GeoB and the split rule are this file's.
 //
 // The three products are those of train.hip's conv_gemm:
 //   FWD   z[p][co]       = sum_{tap,ci} x(p, tap, ci) * w[co][ci][tap]         M = B*Ho*Wo, N = cout, K = k*k*cin
@@ -29,11 +30,11 @@
 #include "yv3_common.h"
 #include "train_conv0_dgrad.h"
 #include "train_bf16_round.h"
+#include "train_conv.h"
 
 namespace {
 
-constexpr int NT = 256, TK = 32, LDK = TK + 8;
-enum { FWD = 0, DGRAD = 1, WGRAD = 2 };
+constexpr int TK = 32, LDK = TK + 8;   // (NT = 256 threads: train_conv.h)
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct GeoB {
@@ -306,29 +307,13 @@ __global__ __launch_bounds__(NT) void conv_bf16(GeoB g) {
     }
 }
 
-// dw[co][ci][kh][kw] = sum over the splits, in split order (fp64)
-__global__ void wgrad_reduce_bf16(const float* __restrict__ part, float* __restrict__ dw, int cout, int cin, int kk2, int split) {
-    const long long MN = (long long)cout * cin * kk2;
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= MN) return;
-    const int co = (int)(i / ((long long)cin * kk2));
-    const int r = (int)(i - (long long)co * cin * kk2);
-    const int ci = r / kk2, tap = r - ci * kk2;
-    const long long src = (long long)co * cin * kk2 + (long long)tap * cin + ci;
-    double s = 0.0;
-    for (int z = 0; z < split; ++z) s += (double)part[z * MN + src];
-    dw[i] = (float)s;
-}
-
 // wf[n][tap*cin + ci] (n < coutp) and wd[ci][tap*coutp + co] (co < coutp), zero where the channel is padding
 __global__ void pack_weight_bf16(const float* __restrict__ w, u16* __restrict__ wf, u16* __restrict__ wd, int cout, int coutp, int cin,
                                  int kk2) {
     const long long n = (long long)coutp * cin * kk2;
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int co = (int)(i / ((long long)cin * kk2));
-    const int r = (int)(i - (long long)co * cin * kk2);
-    const int ci = r / kk2, tap = r - ci * kk2;
+    YV3_WEIGHT_INDEX(i, cin, kk2);
     const u16 v = co < cout ? rne_bf16(w[i]) : (u16)0;
     if (wf) wf[(long long)co * cin * kk2 + (long long)tap * cin + ci] = v;
     if (wd) wd[(long long)ci * kk2 * coutp + (long long)tap * coutp + co] = v;
@@ -348,24 +333,15 @@ __global__ void to_bf16(const float* __restrict__ src, u16* __restrict__ dst, lo
 // ---- host side
 int round8(int c) { return (c + 7) & ~7; }
 
-bool shape_ok(int B, int H, int W, int cin, int cin_up, int cout, int k, int stride) {
-    if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || cin_up < 0) return false;
-    if (!(k == 1 || k == 3) || !(stride == 1 || stride == 2)) return false;
-    if (cin_up > 0 && (cin_up >= cin || (H & 1) || (W & 1))) return false;
-    return true;
-}
-
+// train_conv.h's geometry with the padded channel count of dz
 GeoB make_geo(int B, int H, int W, int cin, int cin_up, int cout, int k, int stride, int nchw) {
-    GeoB g = {};
-    g.B = B; g.H = H; g.W = W; g.cin = cin; g.cin_up = cin_up; g.cout = cout; g.coutp = round8(cout); g.k = k; g.stride = stride;
-    g.nchw = nchw;
-    g.pad = (k - 1) / 2;
-    g.Ho = (H + 2 * g.pad - k) / stride + 1;
-    g.Wo = (W + 2 * g.pad - k) / stride + 1;
+    GeoB g = make_geo<GeoB>(B, H, W, cin, cin_up, cout, k, stride, nchw);
+    g.coutp = round8(cout);
     return g;
 }
 
-int grid1(long long n) { long long b = (n + NT - 1) / NT; return (int)(b < 65536 ? (b > 0 ? b : 1) : 65536); }
+// the 16-byte gathers need whole groups of 8 channels in an NHWC input
+bool vec8_ok(int cin, int cin_up, int x_nchw) { return x_nchw || !((cin & 7) || (cin_up & 7)); }
 
 // the tile arrangement (waves along M x along N): 1x4 when M is small, 4x1 when N is, else 2x2 -- a function of the shape only
 void pick_tile(long long M, long long N, int* wm, int* wn) {
@@ -402,6 +378,19 @@ int launch_conv(const GeoB& g, int split, hipStream_t st) {
     return 0;
 }
 
+// the forward into fp32 z [+ bias], or (OUT_B16: whole groups of 8 output channels, no bias) into bf16 zb
+template <bool OUT_B16>
+int conv_fwd(const void* x, const void* x2, const void* wf, const float* bias, void* z, int B, int H, int W, int cin, int cin_up, int cout,
+             int k, int stride, int x_nchw, hipStream_t st) {
+    if (int rc = conv_check(x && wf && z && (cin_up <= 0 || x2), B, H, W, cin, cin_up, cout, k, stride, x_nchw)) return rc;
+    if ((OUT_B16 && (cout & 7)) || !vec8_ok(cin, cin_up, x_nchw)) return YV3_ESHAPE;
+    GeoB g = make_geo(B, H, W, cin, cin_up, cout, k, stride, x_nchw);
+    g.x = (const u16*)x; g.x2 = (const u16*)x2; g.wp = (const u16*)wf; g.bias = bias;
+    g.out = OUT_B16 ? nullptr : (float*)z; g.out_b = OUT_B16 ? (u16*)z : nullptr;
+    g.M = (long long)B * g.Ho * g.Wo; g.N = cout; g.K = (long long)k * k * cin;
+    return x_nchw ? launch_conv<FWD, false, OUT_B16>(g, 1, st) : launch_conv<FWD, true, OUT_B16>(g, 1, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -426,33 +415,17 @@ int yv3_train_pack_weight_bf16(const float* w, void* wf, void* wd, int cout, int
 
 int yv3_train_conv_fwd_bf16(const void* x, const void* x2, const void* wf, const float* bias, float* z,
                             int B, int H, int W, int cin, int cin_up, int cout, int k, int stride, int x_nchw, void* stream) {
-    if (!x || !wf || !z || (cin_up > 0 && !x2)) return YV3_EINVAL;
-    if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0) return YV3_EINVAL;
-    if (!shape_ok(B, H, W, cin, cin_up, cout, k, stride) || (x_nchw && cin_up)) return YV3_ESHAPE;
-    if (!x_nchw && ((cin & 7) || (cin_up & 7))) return YV3_ESHAPE;
-    GeoB g = make_geo(B, H, W, cin, cin_up, cout, k, stride, x_nchw);
-    g.x = (const u16*)x; g.x2 = (const u16*)x2; g.wp = (const u16*)wf; g.bias = bias; g.out = z;
-    g.M = (long long)B * g.Ho * g.Wo; g.N = cout; g.K = (long long)k * k * cin;
-    return x_nchw ? launch_conv<FWD, false>(g, 1, (hipStream_t)stream) : launch_conv<FWD, true>(g, 1, (hipStream_t)stream);
+    return conv_fwd<false>(x, x2, wf, bias, z, B, H, W, cin, cin_up, cout, k, stride, x_nchw, (hipStream_t)stream);
 }
 
 int yv3_train_conv_fwd_bf16o(const void* x, const void* x2, const void* wf, void* zb, int B, int H, int W, int cin, int cin_up, int cout,
                              int k, int stride, int x_nchw, void* stream) {
-    if (!x || !wf || !zb || (cin_up > 0 && !x2)) return YV3_EINVAL;
-    if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0) return YV3_EINVAL;
-    if (!shape_ok(B, H, W, cin, cin_up, cout, k, stride) || (x_nchw && cin_up) || (cout & 7)) return YV3_ESHAPE;
-    if (!x_nchw && ((cin & 7) || (cin_up & 7))) return YV3_ESHAPE;
-    GeoB g = make_geo(B, H, W, cin, cin_up, cout, k, stride, x_nchw);
-    g.x = (const u16*)x; g.x2 = (const u16*)x2; g.wp = (const u16*)wf; g.out_b = (u16*)zb;
-    g.M = (long long)B * g.Ho * g.Wo; g.N = cout; g.K = (long long)k * k * cin;
-    return x_nchw ? launch_conv<FWD, false, true>(g, 1, (hipStream_t)stream) : launch_conv<FWD, true, true>(g, 1, (hipStream_t)stream);
+    return conv_fwd<true>(x, x2, wf, nullptr, zb, B, H, W, cin, cin_up, cout, k, stride, x_nchw, (hipStream_t)stream);
 }
 
 int yv3_train_conv_dgrad_bf16(const void* dz, const void* wd, float* dx, int B, int H, int W, int cin, int cout, int k, int stride,
                               int accumulate, void* stream) {
-    if (!dz || !wd || !dx) return YV3_EINVAL;
-    if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0) return YV3_EINVAL;
-    if (!shape_ok(B, H, W, cin, 0, cout, k, stride)) return YV3_ESHAPE;
+    if (int rc = conv_check(dz && wd && dx, B, H, W, cin, 0, cout, k, stride, 0)) return rc;
     GeoB g = make_geo(B, H, W, cin, 0, cout, k, stride, 0);
     g.dz = (const u16*)dz; g.wp = (const u16*)wd; g.out = dx; g.accumulate = accumulate;
     g.M = (long long)B * H * W; g.N = cin; g.K = (long long)k * k * g.coutp;
@@ -465,20 +438,13 @@ int yv3_train_conv0_dgrad_bf16(const void* dz, const float* w, float* dx_nchw, i
 }
 
 size_t yv3_train_conv_wgrad_bf16_workspace_bytes(int B, int H, int W, int cin, int cout, int k, int stride) {
-    if (!shape_ok(B, H, W, cin, 0, cout, k, stride)) return 0;
-    GeoB g = make_geo(B, H, W, cin, 0, cout, k, stride, 0);
-    int split; long long chunk;
-    const long long M = cout, N = (long long)k * k * cin, K = (long long)B * g.Ho * g.Wo;
-    wgrad_split(M, N, K, &split, &chunk);
-    return (size_t)split * M * N * sizeof(float);
+    return wgrad_workspace_bytes(wgrad_split, B, H, W, cin, cout, k, stride);
 }
 
 int yv3_train_conv_wgrad_bf16(const void* x, const void* x2, const void* dz, float* dw, int B, int H, int W, int cin, int cin_up,
                               int cout, int k, int stride, int x_nchw, void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !dz || !dw || !ws || (cin_up > 0 && !x2)) return YV3_EINVAL;
-    if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0) return YV3_EINVAL;
-    if (!shape_ok(B, H, W, cin, cin_up, cout, k, stride) || (x_nchw && cin_up)) return YV3_ESHAPE;
-    if (!x_nchw && ((cin & 7) || (cin_up & 7))) return YV3_ESHAPE;
+    if (int rc = conv_check(x && dz && dw && ws && (cin_up <= 0 || x2), B, H, W, cin, cin_up, cout, k, stride, x_nchw)) return rc;
+    if (!vec8_ok(cin, cin_up, x_nchw)) return YV3_ESHAPE;
     if (ws_bytes < yv3_train_conv_wgrad_bf16_workspace_bytes(B, H, W, cin, cout, k, stride)) return YV3_EWORKSPACE;
     GeoB g = make_geo(B, H, W, cin, cin_up, cout, k, stride, x_nchw);
     g.x = (const u16*)x; g.x2 = (const u16*)x2; g.dz = (const u16*)dz; g.out = (float*)ws;
@@ -489,7 +455,7 @@ int yv3_train_conv_wgrad_bf16(const void* x, const void* x2, const void* dz, flo
     const int rc = x_nchw ? launch_conv<WGRAD, false>(g, split, st) : launch_conv<WGRAD, true>(g, split, st);
     if (rc) return rc;
     const long long n = g.M * g.N;
-    hipLaunchKernelGGL(wgrad_reduce_bf16, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, st, (const float*)ws, dw, cout, cin, k * k,
+    hipLaunchKernelGGL(wgrad_reduce, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, st, (const float*)ws, dw, cout, cin, k * k,
                        split);
     YV3_CHECK_LAUNCH();
     return 0;

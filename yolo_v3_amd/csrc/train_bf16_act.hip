@@ -1,5 +1,6 @@
-// BF16_ACT training step (net.backprop_math = BF16_ACT): the BatchNorm / activation / bias kernels of train.hip on activations that
-// exist in bf16 only.  The conv forward (train_bf16.hip, OUT_B16) stores zb = bf16(z32); here
+// The per-channel kernels of net.backprop_math = BF16_ACT (yolo_v3_amd/backprop.py's table MATH names each mode's entry points): the
+// BatchNorm / activation / bias kernels of train.hip on activations that exist in bf16 only.  The conv forward (train_bf16.hip,
+// OUT_B16) stores zb = bf16(z32); here
 //   bn_stats_bf16     reads zb                       -> mean, invstd, running statistics (fp32, fp64 sums)
 //   bn_act_fwd_bf16   reads zb [, bf16 res]          -> y = bf16(leaky(bn(zb)) [+ res])
 //   bn_act_bwd_bf16   reads zb, fp32 dy              -> dgamma, dbeta (fp32), dz = bf16(...)
