@@ -35,7 +35,8 @@ extern "C" {
 #define YV3_ERCCL    (-5)        /* yv3_gather_boxes: librccl not found, or ncclAllGather failed */
 #define YV3_ELIMIT   (-6)        /* input beyond a documented kernel limit (yv3_cocoeval)   */
 
-/* Tensor / math modes.  "Plane" tensors are NP bf16 planes [NP][B,H,W,C] (plane stride B*H*W*C).   */
+/* Tensor / math modes.  "Plane" tensors are NP 16-bit planes [NP][B,H,W,C] (plane stride B*H*W*C): bf16 for NP = 1 (YV3_BF16) and
+   3, fp16 for NP = 2 and for the one plane of YV3_F16.                                                                            */
 #define YV3_F32  0               /* fp32 NHWC tensors, exact fp32 MFMA (v_mfma_f32_32x32x2_f32)          */
 #define YV3_BF16 1               /* 1 bf16 plane, bf16 MFMA, fp32 accumulate                             */
 #define YV3_F32_BF16X3 2         /* 3 bf16 planes = exact split v = p0+p1+p2 of an fp32 value; every fp32
@@ -48,6 +49,15 @@ extern "C" {
                                     accumulation: ~4x fp32 epsilon per product at half the MFMA work of
                                     YV3_F32_BF16X3.  Callers should scale weights by a power of two so that
                                     max|w| is O(1) and fold the inverse into alpha (yolo_v3_amd.engine does) */
+
+/* (code 4 is the Python side's BF16_ACT training mode: not a tensor format, YV3_EDTYPE at every entry point here) */
+#define YV3_F16 5                /* 1 fp16 plane (11 significant bits, subnormals kept), v_mfma_f32_32x32x16_f16, fp32 accumulate: the
+                                    kernels, tiles and selection rules of YV3_BF16 (same bytes, same matrix rate) at 1/8 of its rounding
+                                    error.  Stored values are saturated to +-65504, which ORs bit 0 into *flags as for YV3_F32_F16X2;
+                                    callers scale each output channel's weights to max|w| in [1,2) by a power of two and fold the
+                                    inverse into alpha, as for YV3_F32_F16X2.  NOT in this mode: the Winograd forms (w_wino is ignored:
+                                    a transformed operand rounded to 11 bits is another precision class), stream-K (workspace is
+                                    ignored) and the four-wave 192x128 tile -- those are rules for two fp16 planes.                    */
 
 #define YV3_ACT_LINEAR 0
 #define YV3_ACT_LEAKY  1         /* LeakyReLU(0.1), reference darknet.py:41 */
@@ -62,8 +72,10 @@ const char* yv3_error_string(int code);
 
 /* OIHW fp32 [cout][cin][k][k]  ->  kernel layout for `dtype`; rows >= cout are 0.
  * YV3_F32: K-major [cout_pad][k][k][cin] fp32.  YV3_BF16 / YV3_F32_BF16X3: NP = 1 / 3 bf16 planes
- * pre-arranged tile by tile in the kernel's LDS image order; needs NP * cout_pad*k*k*cin * 2 bytes.
- * k = 1 or 3; k = 4 (plane dtypes only): the 4x4 Winograd-domain filters U = G g G^T of a 3x3 layer (yv3_conv_desc.w_wino). */
+ * pre-arranged tile by tile in the kernel's LDS image order; needs NP * cout_pad*k*k*cin * 2 bytes.  YV3_F32_F16X2 / YV3_F16: the same
+ * image in 2 / 1 fp16 planes (round to nearest even).
+ * k = 1 or 3; k = 4 (plane dtypes except YV3_F16, which has no Winograd form: YV3_ESHAPE): the 4x4 Winograd-domain filters U = G g G^T
+ * of a 3x3 layer (yv3_conv_desc.w_wino). */
 int yv3_pack_conv_weight(const float* w_oihw, void* w_packed, int cout, int cin, int k,
                          int cout_pad, int dtype, void* stream);
 
@@ -76,6 +88,10 @@ int yv3_fold_bn(const float* gamma, const float* bias, const float* mean, const 
  * conversion helpers for callers that hold fp32 tensors; not used inside the fused network plan. */
 int yv3_split_planes(const float* in, void* out, long long n, int np, void* stream);
 int yv3_merge_planes(const void* in, float* out, long long n, int np, void* stream);
+/* The same for the one fp16 plane of YV3_F16 (np = 1 above is bf16): out[i] = fp16(in[i]), round to nearest even, subnormals kept,
+ * saturated to +-65504 (infinities too; not reported: layout helper), NaN stays NaN; and back, exactly. */
+int yv3_split_plane_f16(const float* in, void* out, long long n, void* stream);
+int yv3_merge_plane_f16(const void* in, float* out, long long n, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Convolutions.  Replace conv_bn_relu.forward (darknet.py:43-44), res_layer.forward
@@ -85,12 +101,13 @@ int yv3_merge_planes(const void* in, float* out, long long n, int np, void* stre
 
 /* First layer, feature.mlist.0: 3 -> 32 channels, 3x3, stride 1, pad 1, + BN + leaky.
  * x is the caller's NCHW fp32 image batch [B,3,H,W] (values in [0,1]); y is NHWC [B,H,W,32] in
- * out_dtype (fp32, 1 / 3 bf16 planes, or 2 fp16 planes).
+ * out_dtype (fp32, 1 / 3 bf16 planes, 2 fp16 planes, or the one fp16 plane of YV3_F16).
  * w_tap_major is the OIHW weight permuted to [cin][kh][kw][cout] = [27][32] fp32;
  * alpha/beta from yv3_fold_bn.
  * flags (device pointer, may be NULL): YV3_F32_F16X2 runs this layer on the fp16 matrix cores with
  * inputs scaled by 2^4 and weights by 2^8; |x| > 4094 or |w| > 255 cannot be represented and OR bit 0
- * into *flags (the same sticky status word as yv3_conv_desc.flags). */
+ * into *flags (the same sticky status word as yv3_conv_desc.flags).  YV3_BF16 and YV3_F16 compute the layer the same way and round
+ * the result to one bf16 / one fp16 plane (YV3_F16: saturated to +-65504, which sets bit 0 too). */
 int yv3_conv0(const float* x_nchw, const float* w_tap_major, const float* alpha, const float* beta,
               void* y_nhwc, int B, int H, int W, int out_dtype, int* flags, void* stream);
 
@@ -109,6 +126,11 @@ int yv3_conv_front(const float* x_nchw, const float* w0_tap_major, const float* 
 int yv3_conv_front_bf16(const float* x_nchw, const float* w0_tap_major, const float* alpha0, const float* beta0,
                         const void* w1_packed, const float* alpha1, const float* beta1, void* y,
                         int B, int H, int W, int* flags, void* stream);
+/* The same for YV3_F16: the first layer as yv3_conv0(..., YV3_F16) computes it, w1_packed from yv3_pack_conv_weight(..., YV3_F16),
+ * y = one fp16 plane [B,H/2,W/2,64].  Bit-identical to yv3_conv0 followed by yv3_conv2d in YV3_F16. */
+int yv3_conv_front_f16(const float* x_nchw, const float* w0_tap_major, const float* alpha0, const float* beta0,
+                       const void* w1_packed, const float* alpha1, const float* beta1, void* y,
+                       int B, int H, int W, int* flags, void* stream);
 /* The same for YV3_F32 (exact fp32; csrc/conv_front_f32.hip): the first layer as yv3_conv0(..., YV3_F32) computes it (one fma chain
  * per output over (c, kh, kw) on the vector ALUs), w1_packed [64][3][3][32] fp32 from yv3_pack_conv_weight(..., YV3_F32),
  * y fp32 NHWC [B,H/2,W/2,64].  Bit-identical to yv3_conv0 followed by yv3_conv2d in YV3_F32.  H, W multiples of 16 / 32. */
@@ -129,6 +151,11 @@ int yv3_res_block64(const void* x, const void* w1_packed, const float* alpha1, c
 int yv3_res_block64_bf16(const void* x, const void* w1_packed, const float* alpha1, const float* beta1,
                          const void* w2_packed, const float* alpha2, const float* beta2, void* y,
                          int B, int H, int W, int* flags, void* stream);
+/* The same for YV3_F16 (x, y: one fp16 plane [B,H,W,64]; weights from yv3_pack_conv_weight(..., YV3_F16)); bit-identical to the two
+ * yv3_conv2d launches in YV3_F16. */
+int yv3_res_block64_f16(const void* x, const void* w1_packed, const float* alpha1, const float* beta1,
+                        const void* w2_packed, const float* alpha2, const float* beta2, void* y,
+                        int B, int H, int W, int* flags, void* stream);
 /* The same for YV3_F32 (exact fp32; csrc/conv_res64_f32.hip): x, y fp32 NHWC [B,H,W,64], H a multiple of 8, W of 16 (else
  * YV3_ESHAPE: run the two launches); w1_packed [32][64], w2_packed [64][3][3][32] from yv3_pack_conv_weight(..., YV3_F32).  Same
  * products in the same order as the two yv3_conv2d launches in YV3_F32: bit-identical to them. */
@@ -152,11 +179,11 @@ typedef struct yv3_conv_desc {
     int cout, cout_pad;     /* real and padded (multiple of 32) output channels                */
     int k, stride;          /* k in {1,3}; pad = (k-1)/2 (darknet.py:34-35); stride in {1,2}   */
     int act;                /* YV3_ACT_*                                                       */
-    int dtype;              /* YV3_F32 / YV3_BF16 / YV3_F32_BF16X3: format of x, x2, residual, w */
+    int dtype;              /* YV3_F32 / YV3_BF16 / YV3_F32_BF16X3 / YV3_F32_F16X2 / YV3_F16: format of x, x2, residual, w */
     int out_dtype;          /* format of y: == dtype, or YV3_F32 (head convs write fp32 logits) */
-    int* flags;             /* optional device int32: bit 0 is OR-ed in when a YV3_F32_F16X2 output had to be
-                               saturated (|value| > 65504), i.e. the fp16 planes cannot represent this
-                               layer -- rerun in YV3_F32_BF16X3 or YV3_F32.  NULL: not reported.
+    int* flags;             /* optional device int32: bit 0 is OR-ed in when a YV3_F32_F16X2 or YV3_F16 output had to be
+                               saturated (|value| > 65504), i.e. fp16 cannot represent this
+                               layer -- rerun in YV3_F32_BF16X3 or YV3_F32 (YV3_F16: YV3_BF16).  NULL: not reported.
                                Bit 1: internal scheduling error (stream-K hand-over timed out).           */
     void*  workspace;       /* optional device scratch of yv3_conv_workspace_bytes() bytes, ZERO-FILLED once by
                                the caller and then left alone: enables the persistent "stream-K" schedule of the

@@ -20,6 +20,7 @@ if os.environ.get("YV3_MEASURE") != "1":
 
 F32, BF16, F32X3, F32H2 = 0, 1, 2, 3
 BF16_ACT = 4          # net.backprop_math only: the BF16 training step with activations stored in bf16 only (backprop.py)
+F16 = 5               # YV3_F16: one fp16 plane on the BF16 kernels (inference only)
 ACT_LINEAR, ACT_LEAKY = 0, 1
 PP_EVAL, PP_PROB = 1, 2
 OPT_NO_PINGPONG, OPT_K3S1, OPT_WINO_EVEN, OPT_WINO_ALWAYS, OPT_TWO_LANES, OPT_WINO4_TILES = 1, 2, 4, 8, 16, 32
@@ -102,11 +103,15 @@ _SIGNATURES = {
     "yv3_fold_bn": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p]),
     "yv3_split_planes": (c_int, [c_void_p, c_void_p, c_longlong, c_int, c_void_p]),
     "yv3_merge_planes": (c_int, [c_void_p, c_void_p, c_longlong, c_int, c_void_p]),
+    "yv3_split_plane_f16": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p]),
+    "yv3_merge_plane_f16": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p]),
     "yv3_conv0": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "yv3_conv_front": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "yv3_conv_front_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "yv3_res_block64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "yv3_res_block64_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "yv3_conv_front_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "yv3_res_block64_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "yv3_conv_front_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "yv3_res_block64_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "yv3_conv2d": (c_int, [ctypes.POINTER(ConvDesc), c_void_p]),

@@ -31,7 +31,7 @@ static int check_desc(const yv3_conv_desc* d, bool need_output = true) {
 }
 
 static int plane_count(int dtype) {
-    return dtype == YV3_BF16 ? 1 : dtype == YV3_F32_F16X2 ? 2 : dtype == YV3_F32_BF16X3 ? 3 : 0;
+    return dtype == YV3_BF16 || dtype == YV3_F16 ? 1 : dtype == YV3_F32_F16X2 ? 2 : dtype == YV3_F32_BF16X3 ? 3 : 0;
 }
 
 // The dtype / output-format errors of yv3_conv2d: ONE function, called by the launch and by the form query, so that
@@ -60,7 +60,8 @@ static int conv2d(const yv3_conv_desc* d, int what, hipStream_t s, char* buf = n
         return c.rc ? c.rc : what == CONV_FORM ? c.form : what == CONV_LAUNCHES ? c.launches : what == CONV_KERNEL ? yv3_describe_f32(c, buf, buf_bytes) : yv3_conv2d_f32(d, c, s);
     }
     const yv3_planes_choice c = yv3_select_planes(d, np, ncu);
-    return c.rc ? c.rc : what == CONV_FORM ? c.form : what == CONV_LAUNCHES ? c.launches : what == CONV_KERNEL ? yv3_describe_planes(c, buf, buf_bytes) : yv3_conv2d_planes(d, np, c, s);
+    return c.rc ? c.rc : what == CONV_FORM ? c.form : what == CONV_LAUNCHES ? c.launches : what == CONV_KERNEL ? yv3_describe_planes(c, buf, buf_bytes) :
+           d->dtype == YV3_F16 ? yv3_conv2d_planes_f16(d, c, s) : yv3_conv2d_planes(d, np, c, s);      // (one plane either way: the element type picks the launcher)
 }
 extern "C" int yv3_conv2d(const yv3_conv_desc* d, void* stream) { return conv2d(d, CONV_LAUNCH, (hipStream_t)stream); }
 extern "C" int yv3_conv2d_form(const yv3_conv_desc* d) { return conv2d(d, CONV_FORM, nullptr); }

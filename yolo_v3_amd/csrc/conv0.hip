@@ -123,9 +123,11 @@ __device__ inline void split8(const float (&v)[8], h16x8& hi, h16x8& lo) {
     }
 }
 
-// BF16_OUT (YV3_BF16 mode): same arithmetic (fp32-class products, fp32 accumulate, as conv0_kernel<1> computes them on the
-// vector ALUs), the result rounded to ONE bf16 plane.
-template <bool BF16_OUT>
+// OUT: C0_OUT_F16X2 (YV3_F32_F16X2) the result split into fp16 hi + lo planes; C0_OUT_BF16 (YV3_BF16) / C0_OUT_F16 (YV3_F16): same
+// arithmetic (fp32-class products, fp32 accumulate, as conv0_kernel<1> computes them on the vector ALUs), the result rounded to ONE
+// bf16 plane / ONE fp16 plane (saturated to +-65504; a saturated value sets bit 0 of *flags).
+enum { C0_OUT_F16X2 = 0, C0_OUT_BF16 = 1, C0_OUT_F16 = 2 };
+template <int OUT>
 __global__ __launch_bounds__(256) void conv0_mfma_kernel(const float* __restrict__ x, const float* __restrict__ wt,
                                                         const float* __restrict__ alpha, const float* __restrict__ beta,
                                                         u16* __restrict__ y, int H, int W, long long plane_stride,
@@ -179,6 +181,7 @@ __global__ __launch_bounds__(256) void conv0_mfma_kernel(const float* __restrict
     __syncthreads();
 
     // ---- each wave owns a 32-column strip and walks the 8 rows
+    float amax = 0.f;                                        // (C0_OUT_F16: running max |v| of what this lane stores)
 #pragma unroll 2
     for (int row = 0; row < C0_TR; ++row) {
         const int base = row * C0_PITCH + wid * 32 + l31;
@@ -199,14 +202,18 @@ __global__ __launch_bounds__(256) void conv0_mfma_kernel(const float* __restrict
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(whi[ks], xhi[ks], acc, 0, 0, 0);
         }
         const int gy = r0 + row, gx = c0 + wid * 32 + l31;
-        if constexpr (BF16_OUT) {
+        if constexpr (OUT != C0_OUT_F16X2) {
             if (gy < H && gx < W) {
                 u32x4v qb[2];
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     float t0 = fmaf(acc[2 * q], al[2 * q], be[2 * q]), t1 = fmaf(acc[2 * q + 1], al[2 * q + 1], be[2 * q + 1]);
                     t0 = __builtin_fmaxf(t0, 0.1f * t0); t1 = __builtin_fmaxf(t1, 0.1f * t1);
-                    qb[q >> 2][q & 3] = yv3_pack_bf16x2(t0, t1);
+                    if constexpr (OUT == C0_OUT_F16) {
+                        amax = __builtin_fmaxf(amax, __builtin_fmaxf(__builtin_fabsf(t0), __builtin_fabsf(t1)));
+                        const f32x2v a = {__builtin_amdgcn_fmed3f(t0, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(t1, -65504.f, 65504.f)};
+                        qb[q >> 2][q & 3] = __builtin_bit_cast(unsigned, __builtin_convertvector(a, h16x2));
+                    } else qb[q >> 2][q & 3] = yv3_pack_bf16x2(t0, t1);
                 }
                 u16* o = y + (((size_t)b * H + gy) * W + gx) * 32 + 8 * lhi;
                 *reinterpret_cast<u32x4v*>(o) = qb[0];
@@ -231,6 +238,9 @@ __global__ __launch_bounds__(256) void conv0_mfma_kernel(const float* __restrict
             *reinterpret_cast<u32x4v*>(o + plane_stride + 16) = ql[1];
         }
     }
+    if constexpr (OUT == C0_OUT_F16) {
+        if (flags && __any(!(amax <= 65504.f)) && lane == 0) atomicOr(flags, 1);
+    }
 }
 
 }  // namespace
@@ -240,13 +250,16 @@ __global__ __launch_bounds__(256) void conv0_mfma_kernel(const float* __restrict
 extern "C" int yv3_conv0(const float* x_nchw, const float* w_tap_major, const float* alpha, const float* beta,
                          void* y_nhwc, int B, int H, int W, int out_dtype, int* flags, void* stream) {
     if (!x_nchw || !w_tap_major || !alpha || !beta || !y_nhwc || B <= 0 || H <= 0 || W <= 0) return YV3_EINVAL;
-    if (out_dtype == YV3_F32_F16X2 || out_dtype == YV3_BF16) {
+    if (out_dtype == YV3_F32_F16X2 || out_dtype == YV3_BF16 || out_dtype == YV3_F16) {
         const dim3 g((unsigned)yv3_ceil_div(W, C0_TC), (unsigned)yv3_ceil_div(H, C0_TR), (unsigned)B);
-        if (out_dtype == YV3_BF16)
-            hipLaunchKernelGGL(conv0_mfma_kernel<true>, g, dim3(256), 0, (hipStream_t)stream, x_nchw, w_tap_major, alpha, beta,
+        if (out_dtype == YV3_F16)
+            hipLaunchKernelGGL(conv0_mfma_kernel<C0_OUT_F16>, g, dim3(256), 0, (hipStream_t)stream, x_nchw, w_tap_major, alpha, beta,
+                               (u16*)y_nhwc, H, W, (long long)B * H * W * 32, flags);
+        else if (out_dtype == YV3_BF16)
+            hipLaunchKernelGGL(conv0_mfma_kernel<C0_OUT_BF16>, g, dim3(256), 0, (hipStream_t)stream, x_nchw, w_tap_major, alpha, beta,
                                (u16*)y_nhwc, H, W, (long long)B * H * W * 32, flags);
         else
-            hipLaunchKernelGGL(conv0_mfma_kernel<false>, g, dim3(256), 0, (hipStream_t)stream, x_nchw, w_tap_major, alpha, beta,
+            hipLaunchKernelGGL(conv0_mfma_kernel<C0_OUT_F16X2>, g, dim3(256), 0, (hipStream_t)stream, x_nchw, w_tap_major, alpha, beta,
                                (u16*)y_nhwc, H, W, (long long)B * H * W * 32, flags);
         YV3_CHECK_LAUNCH();
         return 0;

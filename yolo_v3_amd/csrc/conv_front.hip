@@ -72,7 +72,9 @@ struct FrontParams {
     int* flags;
 };
 
-template <int NP>
+// EL: the element type of the planes (conv_planes_common.h); NP = 1 with YV3_EL_F16 is YV3_F16 -- the first layer as in the other two
+// modes, rounded to ONE fp16 plane (saturated, status bit)
+template <int NP, int EL = plane_elem(NP)>
 __global__ __launch_bounds__(512) void conv_front_kernel(const FrontParams p) {
     constexpr int FW_CHUNK = FrontGeo<NP>::FW_CHUNK, FW_BYTES = FrontGeo<NP>::FW_BYTES, F_W_OFF = FrontGeo<NP>::F_W_OFF,
                   F_P_OFF = FrontGeo<NP>::F_P_OFF;
@@ -262,6 +264,9 @@ __global__ __launch_bounds__(512) void conv_front_kernel(const FrontParams p) {
                         const fh16x2 l = __builtin_convertvector(a - __builtin_convertvector(h, ff32x2), fh16x2);
                         qh[q >> 2][q & 3] = inimg ? __builtin_bit_cast(unsigned, h) : 0u;  // outside the image: the second conv's zero padding
                         ql[q >> 2][q & 3] = inimg ? __builtin_bit_cast(unsigned, l) : 0u;
+                    } else if constexpr (EL == YV3_EL_F16) {                               // one fp16 plane (as conv0.hip)
+                        if (inimg) amax = __builtin_fmaxf(amax, __builtin_fmaxf(__builtin_fabsf(t0), __builtin_fabsf(t1)));      // (as conv0.hip: stored values only)
+                        qh[q >> 2][q & 3] = inimg ? ElemOps<EL>::pack2(t0, t1) : 0u;
                     } else {                                                               // bf16, round to nearest even (as conv0.hip)
                         qh[q >> 2][q & 3] = inimg ? yv3_pack_bf16x2(t0, t1) : 0u;
                     }
@@ -308,7 +313,7 @@ __global__ __launch_bounds__(512) void conv_front_kernel(const FrontParams p) {
                     wf[pl] = *reinterpret_cast<const bf16x8v*>(lds + wa[ks] + tap * FW_CHUNK + pl * (64 * ROWB));
                     xf[pl] = *reinterpret_cast<const bf16x8v*>(lds + aoff + xa[ks][kw >> 1] + pl * FA_PLANE);
                 }
-                acc2 = mfma_unit<NP>(wf, xf, acc2);
+                acc2 = mfma_unit<NP, EL>(wf, xf, acc2);
             }
         }
         FTL(3);
@@ -352,10 +357,14 @@ __global__ __launch_bounds__(512) void conv_front_kernel(const FrontParams p) {
                 }
                 *reinterpret_cast<u32x4*>(yo) = qh;
                 *reinterpret_cast<u32x4*>(yo + p.ys) = ql;
-            } else {                                                    // one bf16 plane, as conv_planes_common.h's epilogue (PlaneOps<1>::pack2)
+            } else {                                                    // one plane, as conv_planes_common.h's epilogue (ElemOps<EL>::pack2)
+                if constexpr (EL == YV3_EL_F16) {
+#pragma unroll
+                    for (int h = 0; h < 4; ++h) amax = __builtin_fmaxf(amax, __builtin_fmaxf(__builtin_fabsf(v[2 * h]), __builtin_fabsf(v[2 * h + 1])));
+                }
                 u32x4 qb;
 #pragma unroll
-                for (int h = 0; h < 4; ++h) qb[h] = PlaneOps<1>::pack2(v[2 * h], v[2 * h + 1]);
+                for (int h = 0; h < 4; ++h) qb[h] = ElemOps<EL>::pack2(v[2 * h], v[2 * h + 1]);
                 *reinterpret_cast<u32x4*>(yo) = qb;
             }
         }
@@ -373,7 +382,7 @@ __global__ __launch_bounds__(512) void conv_front_kernel(const FrontParams p) {
 
 }  // namespace
 
-template <int NP>
+template <int NP, int EL = plane_elem(NP)>
 static int conv_front_launch(const float* x_nchw, const float* w0_tap_major, const float* alpha0, const float* beta0,
                              const void* w1_packed, const float* alpha1, const float* beta1, void* y,
                              int B, int H, int W, int* flags, void* stream) {
@@ -393,7 +402,7 @@ static int conv_front_launch(const float* x_nchw, const float* w0_tap_major, con
     static_assert(FrontGeo<NP>::F_LDS <= 160 * 1024, "LDS budget");
     const int ncu = yv3_num_cu();
     const int grid = p.total < ncu ? p.total : ncu;                      // persistent: one workgroup per CU
-    hipLaunchKernelGGL(conv_front_kernel<NP>, dim3(grid), dim3(512), FrontGeo<NP>::F_LDS, (hipStream_t)stream, p);
+    hipLaunchKernelGGL((conv_front_kernel<NP, EL>), dim3(grid), dim3(512), FrontGeo<NP>::F_LDS, (hipStream_t)stream, p);
     YV3_CHECK_LAUNCH();
     return 0;
 }
@@ -408,4 +417,10 @@ extern "C" int yv3_conv_front_bf16(const float* x_nchw, const float* w0_tap_majo
                                    const void* w1_packed, const float* alpha1, const float* beta1, void* y,
                                    int B, int H, int W, int* flags, void* stream) {
     return conv_front_launch<1>(x_nchw, w0_tap_major, alpha0, beta0, w1_packed, alpha1, beta1, y, B, H, W, flags, stream);
+}
+
+extern "C" int yv3_conv_front_f16(const float* x_nchw, const float* w0_tap_major, const float* alpha0, const float* beta0,
+                                  const void* w1_packed, const float* alpha1, const float* beta1, void* y,
+                                  int B, int H, int W, int* flags, void* stream) {
+    return conv_front_launch<1, YV3_EL_F16>(x_nchw, w0_tap_major, alpha0, beta0, w1_packed, alpha1, beta1, y, B, H, W, flags, stream);
 }

@@ -1,4 +1,5 @@
-// Shared pieces of the bf16-plane convolution kernels (conv_planes.hip, conv_planes_k3s1.hip).
+// Shared pieces of the 16-bit-plane convolution kernels (conv_planes_kernel.h: conv_planes.hip and conv_planes_f16.hip; conv_planes_k3s1.hip,
+// conv_planes_w4.hip, conv_front.hip, conv_res64.hip).
 #pragma once
 #include "yv3_common.h"
 
@@ -24,7 +25,7 @@ struct ConvParamsP {
     int* wsflags;
     size_t ws_bytes;
     int tb;                     // rows per packed weight tile
-    int* flags;                 // optional: bit 0 <- an fp16-plane output was saturated
+    int* flags;                 // optional: bit 0 <- an fp16 output (two planes or one) was saturated
     int tune[4];                // tuning experiments (yv3_conv_desc.tune)
     // Winograd launches (conv_planes_kernel<..., WINO>): rows of the GEMM are 2x2 output TILES; position xi's operand
     // matrix starts xi * xi_stride elements into each plane of x; the epilogue maps tile rows back to pixels
@@ -65,10 +66,15 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
 
-// Element type of the planes and the MFMA that consumes them.
-//   NP = 1, 3: bf16 (v_cvt_pk_bf16_f32 RN, v_mfma_f32_32x32x16_bf16)
-//   NP = 2   : fp16 (v_cvt_f16_f32 RN after saturating to +-65504, v_mfma_f32_32x32x16_f16)
-template <int NP> struct PlaneOps {
+// Element type of a plane tensor, apart from the plane count: conversion, pack / unpack, the MFMA that consumes it, saturation.
+//   YV3_EL_BF16: v_cvt_pk_bf16_f32 RN, v_mfma_f32_32x32x16_bf16
+//   YV3_EL_F16 : v_cvt_f16_f32 RN after saturating to +-65504 (the kernels then raise the status bit), v_mfma_f32_32x32x16_f16
+// The plane count says how many planes a tensor has and which partial products run (mfma_unit).  The modes before YV3_F16 tie the two
+// together -- one or three bf16 planes, two fp16 planes: plane_elem, the default of every kernel's element parameter; YV3_F16 is one
+// plane of YV3_EL_F16 (conv_planes_f16.hip).
+enum { YV3_EL_BF16 = 0, YV3_EL_F16 = 1 };
+constexpr int plane_elem(int np) { return np == 2 ? YV3_EL_F16 : YV3_EL_BF16; }
+template <int EL> struct ElemOps {
     static __device__ inline unsigned pack2(float lo, float hi) {
         unsigned r;
         asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
@@ -82,7 +88,7 @@ template <int NP> struct PlaneOps {
     static __host__ __device__ inline u16 cvt(float v) { return yv3_f2bf(v); }
     static __host__ __device__ inline float back(u16 h) { return yv3_bf2f(h); }
 };
-template <> struct PlaneOps<2> {
+template <> struct ElemOps<YV3_EL_F16> {
     static __device__ inline _Float16 sat(float v) { return (_Float16)__builtin_fminf(__builtin_fmaxf(v, -65504.f), 65504.f); }
     static __device__ inline unsigned pack2(float lo, float hi) {       // saturate, then one v_cvt_pk_f16_f32 (RNE)
         typedef _Float16 h2 __attribute__((ext_vector_type(2)));
@@ -108,12 +114,13 @@ template <> struct PlaneOps<2> {
     static __device__ inline u16 cvt(float v) { return __builtin_bit_cast(unsigned short, sat(v)); }
     static __device__ inline float back(u16 h) { return (float)__builtin_bit_cast(_Float16, h); }
 };
+template <int NP> using PlaneOps = ElemOps<plane_elem(NP)>;      // the element type the plane count implies
 
 // One "unit" = all partial products of one (weight tile, pixel tile) pair for one 16-deep k-step.
 //   NP = 3 (exact bf16 split, 8+8+8 bits): the six products of weight >= 2^-16, smallest first
 //   NP = 2 (fp16 split, 11+11(+1) bits)  : w1*x0, w0*x1, w0*x0 (the dropped w1*x1 is <= 2^-22 |w*x|)
-//   NP = 1                               : w0*x0
-template <int NP>
+//   NP = 1 (bf16, or fp16 with EL)       : w0*x0
+template <int NP, int EL = plane_elem(NP)>
 __device__ inline f32x16 mfma_unit(const bf16x8v* wf, const bf16x8v* xf, f32x16 c) {
     if constexpr (NP == 3) {
         c = PlaneOps<3>::mfma(wf[2], xf[0], c);
@@ -125,7 +132,7 @@ __device__ inline f32x16 mfma_unit(const bf16x8v* wf, const bf16x8v* xf, f32x16 
         c = PlaneOps<2>::mfma(wf[1], xf[0], c);
         c = PlaneOps<2>::mfma(wf[0], xf[1], c);
     }
-    return PlaneOps<NP>::mfma(wf[0], xf[0], c);
+    return ElemOps<EL>::mfma(wf[0], xf[0], c);
 }
 
 // bank-conflict swizzle for 64-byte rows read with ds_read_b128: four rows share a 256-byte bank row
@@ -141,7 +148,7 @@ template <int N> __device__ inline void wait_vmcnt() { asm volatile("s_waitcnt v
 // transpose tile fits, and fetch their residual rows round by round (registers).
 // WINO: row m of the tile is the 2x2 output tile m of a Winograd launch and `acc` holds its output (wi, wj): the row is
 // written to pixel (2 ty + wi, 2 tx + wj) (skipped beyond an odd picture's edge).
-template <int NP, int BM, int BN, int WM, int WN, bool OUT_F32, bool SYNC = true, int MTG = BM / WM / 32, bool WINO = false>
+template <int NP, int BM, int BN, int WM, int WN, bool OUT_F32, bool SYNC = true, int MTG = BM / WM / 32, bool WINO = false, int EL = plane_elem(NP)>
 __device__ __forceinline__ void epilogue_store(f32x16 (&acc)[BN / WN / 32][BM / WM / 32], const ConvParamsP& p,
                                                unsigned char* lds, int m0, int n0, int wid, int lane, int wi = 0, int wj = 0) {
     static_assert(!(WINO && OUT_F32), "Winograd launches write plane outputs");
@@ -342,7 +349,7 @@ __device__ __forceinline__ void epilogue_store(f32x16 (&acc)[BN / WN / 32][BM / 
                     if constexpr (PRE) q4 = rres[ps][pl];
                     else q4 = *reinterpret_cast<const u32x4*>(p.res + pl * p.ys + o);
 #pragma unroll
-                    for (int h = 0; h < 4; ++h) { v[2 * h] += PlaneOps<NP>::lo(q4[h]); v[2 * h + 1] += PlaneOps<NP>::hi(q4[h]); }
+                    for (int h = 0; h < 4; ++h) { v[2 * h] += ElemOps<EL>::lo(q4[h]); v[2 * h + 1] += ElemOps<EL>::hi(q4[h]); }
                 }
             }
             u16* yo = (u16*)p.y + o;
@@ -362,20 +369,24 @@ __device__ __forceinline__ void epilogue_store(f32x16 (&acc)[BN / WN / 32][BM / 
                     *reinterpret_cast<u32x4*>(yo + p.ys) = ql;
                 } else { asm volatile("" :: "v"(qh), "v"(ql)); }
             } else {
+                if constexpr (EL == YV3_EL_F16) {          // one fp16 plane: pack2 saturates, the flag follows below
+#pragma unroll
+                    for (int h = 0; h < 4; ++h) amax = __builtin_fmaxf(amax, __builtin_fmaxf(__builtin_fabsf(v[2 * h]), __builtin_fabsf(v[2 * h + 1])));
+                }
 #pragma unroll
                 for (int pl = 0; pl < NP; ++pl) {
                     u32x4 q4;
 #pragma unroll
                     for (int h = 0; h < 4; ++h) {
-                        q4[h] = PlaneOps<NP>::pack2(v[2 * h], v[2 * h + 1]);
-                        v[2 * h] -= PlaneOps<NP>::lo(q4[h]); v[2 * h + 1] -= PlaneOps<NP>::hi(q4[h]);
+                        q4[h] = ElemOps<EL>::pack2(v[2 * h], v[2 * h + 1]);
+                        v[2 * h] -= ElemOps<EL>::lo(q4[h]); v[2 * h + 1] -= ElemOps<EL>::hi(q4[h]);
                     }
                     *reinterpret_cast<u32x4*>(yo + pl * p.ys) = q4;
                 }
             }
         }
     }
-    if constexpr (NP == 2) {
+    if constexpr (EL == YV3_EL_F16) {
         if (p.flags && __any(!(amax <= 65504.f)) && lane == 0) atomicOr(p.flags, 1);
     }
 }

@@ -20,7 +20,7 @@
 
 namespace {
 
-template <int NP, int BM, int BN, int WM, int WN>
+template <int NP, int BM, int BN, int WM, int WN, int EL = plane_elem(NP)>
 __global__ __launch_bounds__(64 * WM * WN) void conv_planes_k3s1_kernel(const ConvParamsP p) {
     constexpr int NW = WM * WN;
     constexpr int WTM = BM / WM, WTN = BN / WN;
@@ -214,24 +214,24 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_planes_k3s1_kernel(const Co
                     }
                     const bf16x8v* wf = &frag[ks][i * NP];
                     f32x16 c = acc[i][j];
-                    c = mfma_unit<NP>(wf, xf, c);
+                    c = mfma_unit<NP, EL>(wf, xf, c);
                     acc[i][j] = c;
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
         }
     }
-    epilogue_store<NP, BM, BN, WM, WN, false>(acc, p, lds, m0, n0, wid, lane);
+    epilogue_store<NP, BM, BN, WM, WN, false, true, BM / WM / 32, false, EL>(acc, p, lds, m0, n0, wid, lane);
 }
 
-template <int NP, int BM, int BN, int WM, int WN>
+template <int NP, int BM, int BN, int WM, int WN, int EL = plane_elem(NP)>
 int launch_k3s1(const ConvParamsP& p, hipStream_t s) {
     const int mtiles = (p.M + BM - 1) / BM;
     const dim3 grid((unsigned)(mtiles * p.ntiles));
     const size_t pipe = (size_t)2 * NP * (BM + 2 + BN) * ROWB;
     const size_t epi = (size_t)WN * BM * (BN / WN + 4) * 4;
     const size_t lds = pipe > epi ? pipe : epi;
-    hipLaunchKernelGGL((conv_planes_k3s1_kernel<NP, BM, BN, WM, WN>), grid, dim3(64 * WM * WN), lds, s, p);
+    hipLaunchKernelGGL((conv_planes_k3s1_kernel<NP, BM, BN, WM, WN, EL>), grid, dim3(64 * WM * WN), lds, s, p);
     YV3_CHECK_LAUNCH();
     return 0;
 }
@@ -248,4 +248,14 @@ int yv3_conv2d_planes_k3s1(const ConvParamsP& p, int np, yv3_planes_kernel kerne
         default: return YV3_EINVAL;
     }
 #undef YV3_K3
+}
+
+// the same for one fp16 plane (YV3_F16)
+int yv3_conv2d_planes_k3s1_f16(const ConvParamsP& p, yv3_planes_kernel kernel, hipStream_t s) {
+    switch (kernel) {
+        case YV3_PK_K3S1_256x128: return launch_k3s1<1, 256, 128, 4, 2, YV3_EL_F16>(p, s);
+        case YV3_PK_K3S1_128x128: return launch_k3s1<1, 128, 128, 4, 2, YV3_EL_F16>(p, s);
+        case YV3_PK_K3S1_128x64:  return launch_k3s1<1, 128, 64, 2, 2, YV3_EL_F16>(p, s);
+        default: return YV3_EINVAL;
+    }
 }

@@ -42,7 +42,8 @@ struct Res64Params {
     int* flags;
 };
 
-template <int NP>
+// EL: the element type of the planes (conv_planes_common.h); NP = 1 with YV3_EL_F16 is YV3_F16
+template <int NP, int EL = plane_elem(NP)>
 __global__ __launch_bounds__(512) void conv_res64_kernel(const Res64Params p) {
     constexpr int RX_CHUNK = ResGeo<NP>::RX_CHUNK, RW_BYTES = ResGeo<NP>::RW_BYTES, R_X_OFF = ResGeo<NP>::R_X_OFF,
                   R_I_OFF = ResGeo<NP>::R_I_OFF, R_W_OFF = ResGeo<NP>::R_W_OFF;
@@ -159,7 +160,7 @@ __global__ __launch_bounds__(512) void conv_res64_kernel(const Res64Params p) {
                     bf16x8v xf[NP];
 #pragma unroll
                     for (int pl = 0; pl < NP; ++pl) xf[pl] = *reinterpret_cast<const bf16x8v*>(lds + x1a[ks] + kc * RX_CHUNK + pl * RX_PLANE);
-                    acc = mfma_unit<NP>(wf1[kc][ks], xf, acc);
+                    acc = mfma_unit<NP, EL>(wf1[kc][ks], xf, acc);
                 }
             const int gy = r0 - 1 + rrr, gx = c0 - 1 + rcc;
             const bool inimg = rlive && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
@@ -173,7 +174,7 @@ __global__ __launch_bounds__(512) void conv_res64_kernel(const Res64Params p) {
                     if constexpr (NP == 2) {
                         amax = __builtin_fmaxf(amax, __builtin_fabsf(v[q]));
                         v[q] = __builtin_amdgcn_fmed3f(v[q], -65504.f, 65504.f);
-                    }
+                    } else if constexpr (EL == YV3_EL_F16) amax = __builtin_fmaxf(amax, __builtin_fabsf(v[q]));      // (pack2 saturates)
                 }
                 u32x2 qh, ql;
 #pragma unroll
@@ -181,7 +182,7 @@ __global__ __launch_bounds__(512) void conv_res64_kernel(const Res64Params p) {
                     if constexpr (NP == 2) {
                         qh[h] = PlaneOps<2>::pack2_nosat(v[2 * h], v[2 * h + 1]);
                         ql[h] = PlaneOps<2>::pack2_nosat(v[2 * h] - PlaneOps<2>::lo(qh[h]), v[2 * h + 1] - PlaneOps<2>::hi(qh[h]));
-                    } else { qh[h] = PlaneOps<1>::pack2(v[2 * h], v[2 * h + 1]); ql[h] = 0u; }
+                    } else { qh[h] = ElemOps<EL>::pack2(v[2 * h], v[2 * h + 1]); ql[h] = 0u; }
                     if (!inimg) { qh[h] = 0u; ql[h] = 0u; }       // outside the picture: the 3x3 conv's zero padding
                 }
                 if (rlive) {                                      // channels 8g + 4*lhi .. +3: 8 bytes of slot g
@@ -221,7 +222,7 @@ __global__ __launch_bounds__(512) void conv_res64_kernel(const Res64Params p) {
                     wf[pl] = *reinterpret_cast<const bf16x8v*>(lds + wa[ks] + tap * (NP * 64 * ROWB) + pl * (64 * ROWB));
                     xf[pl] = *reinterpret_cast<const bf16x8v*>(lds + xa[ks][kw] + kh * (RI_RP * ROWB) + pl * RI_PLANE);
                 }
-                acc2 = mfma_unit<NP>(wf, xf, acc2);
+                acc2 = mfma_unit<NP, EL>(wf, xf, acc2);
             }
         }
         RTL(3);
@@ -254,7 +255,7 @@ __global__ __launch_bounds__(512) void conv_res64_kernel(const Res64Params p) {
 #pragma unroll
             for (int pl = 0; pl < NP; ++pl)
 #pragma unroll
-                for (int h = 0; h < 4; ++h) { v[2 * h] += PlaneOps<NP>::lo(rres[ps][pl][h]); v[2 * h + 1] += PlaneOps<NP>::hi(rres[ps][pl][h]); }
+                for (int h = 0; h < 4; ++h) { v[2 * h] += ElemOps<EL>::lo(rres[ps][pl][h]); v[2 * h + 1] += ElemOps<EL>::hi(rres[ps][pl][h]); }
             if constexpr (NP == 2) {
 #pragma unroll
                 for (int h = 0; h < 4; ++h) amax = __builtin_fmaxf(amax, __builtin_fmaxf(__builtin_fabsf(v[2 * h]), __builtin_fabsf(v[2 * h + 1])));
@@ -269,9 +270,13 @@ __global__ __launch_bounds__(512) void conv_res64_kernel(const Res64Params p) {
                 *reinterpret_cast<u32x4*>(p.y + orow[ps]) = qh;
                 *reinterpret_cast<u32x4*>(p.y + p.ps + orow[ps]) = ql;
             } else {
+                if constexpr (EL == YV3_EL_F16) {
+#pragma unroll
+                    for (int h = 0; h < 4; ++h) amax = __builtin_fmaxf(amax, __builtin_fmaxf(__builtin_fabsf(v[2 * h]), __builtin_fabsf(v[2 * h + 1])));
+                }
                 u32x4 qb;
 #pragma unroll
-                for (int h = 0; h < 4; ++h) qb[h] = PlaneOps<1>::pack2(v[2 * h], v[2 * h + 1]);
+                for (int h = 0; h < 4; ++h) qb[h] = ElemOps<EL>::pack2(v[2 * h], v[2 * h + 1]);
                 *reinterpret_cast<u32x4*>(p.y + orow[ps]) = qb;
             }
         }
@@ -289,7 +294,7 @@ __global__ __launch_bounds__(512) void conv_res64_kernel(const Res64Params p) {
 
 }  // namespace
 
-template <int NP>
+template <int NP, int EL = plane_elem(NP)>
 static int res_block64_launch(const void* x, const void* w1_packed, const float* alpha1, const float* beta1,
                               const void* w2_packed, const float* alpha2, const float* beta2, void* y,
                               int B, int H, int W, int* flags, void* stream) {
@@ -307,7 +312,7 @@ static int res_block64_launch(const void* x, const void* w1_packed, const float*
     p.flags = flags;
     const int ncu = yv3_num_cu();
     const int grid = p.total < ncu ? p.total : ncu;                    // persistent: one workgroup per CU
-    hipLaunchKernelGGL(conv_res64_kernel<NP>, dim3(grid), dim3(512), ResGeo<NP>::R_LDS, (hipStream_t)stream, p);
+    hipLaunchKernelGGL((conv_res64_kernel<NP, EL>), dim3(grid), dim3(512), ResGeo<NP>::R_LDS, (hipStream_t)stream, p);
     YV3_CHECK_LAUNCH();
     return 0;
 }
@@ -322,4 +327,10 @@ extern "C" int yv3_res_block64_bf16(const void* x, const void* w1_packed, const 
                                     const void* w2_packed, const float* alpha2, const float* beta2, void* y,
                                     int B, int H, int W, int* flags, void* stream) {
     return res_block64_launch<1>(x, w1_packed, alpha1, beta1, w2_packed, alpha2, beta2, y, B, H, W, flags, stream);
+}
+
+extern "C" int yv3_res_block64_f16(const void* x, const void* w1_packed, const float* alpha1, const float* beta1,
+                                   const void* w2_packed, const float* alpha2, const float* beta2, void* y,
+                                   int B, int H, int W, int* flags, void* stream) {
+    return res_block64_launch<1, YV3_EL_F16>(x, w1_packed, alpha1, beta1, w2_packed, alpha2, beta2, y, B, H, W, flags, stream);
 }

@@ -92,7 +92,7 @@ static inline size_t yv3_wino4_ws_bytes(int B, int H, int W, int cin) { return (
 // one kernel instantiation (the plane count NP, 3x3 / dual-source / fp32-output are properties of the descriptor, not choices: the
 // launchers take them from there).
 enum yv3_planes_kernel {
-    // conv_planes.hip launch_cfg<NP, BM, BN, WM, WN, ring, ...>: rows x channels, waves
+    // conv_planes_kernel.h launch_cfg<NP, BM, BN, WM, WN, ring, ...>: rows x channels, waves
     YV3_PK_256x128_W8,          // 8 waves; ring 2 (3 for fp16 planes).  fp16 planes: ping-pong loop (plain under YV3_OPT_NO_PINGPONG), stream-K by
                                 // the rule; one or three bf16 planes: plain loop
     YV3_PK_128x128_W8,          // 8 waves; ring 3 (4 for fp16 planes); loops and schedule as above
@@ -166,7 +166,7 @@ struct yv3_f32_choice {
 struct yv3_conv_shape { int Ho, Wo; long long M; };
 yv3_conv_shape yv3_conv_out_shape(const yv3_conv_desc* d);
 
-yv3_planes_choice yv3_select_planes(const yv3_conv_desc* d, int np, int ncu);     // np = planes per tensor: 1 bf16, 2 fp16 hi+lo, 3 bf16 x3
+yv3_planes_choice yv3_select_planes(const yv3_conv_desc* d, int np, int ncu);     // np = planes per tensor: 1 bf16 (or fp16: YV3_F16 takes YV3_BF16's choice), 2 fp16 hi+lo, 3 bf16 x3
 yv3_f32_choice yv3_select_f32(const yv3_conv_desc* d, int ncu);
 
 // One line (at most YV3_KERNEL_LINE_BYTES with its NUL) that holds every field of a choice that is not a function of the descriptor alone

@@ -32,6 +32,7 @@ static inline int yv3_num_cu() {
 // (conv_select.h; the workspace geometries YV3_SK_* / YV3_WINO_SK_* are there too), decides nothing -- the CU count stays with the selector --
 // and returns launch errors, or YV3_EINVAL for a choice it has no instantiation for.
 int yv3_conv2d_planes(const yv3_conv_desc* d, int np, const yv3_planes_choice& c, hipStream_t s);
+int yv3_conv2d_planes_f16(const yv3_conv_desc* d, const yv3_planes_choice& c, hipStream_t s);      // YV3_F16 (conv_planes_f16.hip)
 int yv3_conv2d_f32(const yv3_conv_desc* d, const yv3_f32_choice& c, hipStream_t s);
 
 // float -> bf16 bits, round to nearest even (NaN kept quiet)

@@ -279,7 +279,8 @@ class YoloNet(nn.Module):
         #                   within +-65504 (checked: a saturated value raises Yv3Error instead of passing silently)
         #   F32X3           exact 3-way bf16 split, 6 bf16 MFMAs per product   -- fp32 exponent range, ~1.6x slower
         #   F32             exact fp32 MFMA                                    -- ~2.7x slower
-        # _ffi.BF16 is the reduced-precision throughput mode (not a 1e-4 mode).
+        # _ffi.BF16 and _ffi.F16 are the reduced-precision throughput modes (not 1e-4 modes): one 16-bit plane, the same kernels and
+        # cost; F16 keeps 11 significant bits instead of 8 and needs activations within +-65504 (else it re-runs in BF16, once).
         self.math_mode = DEFAULT_MATH_MODE
         # net(x, target) as a differentiable training step (yolo_v3_amd/backprop.py): False keeps the no-grad loss
         self.backprop = False
@@ -293,10 +294,10 @@ class YoloNet(nn.Module):
     # ---- HIP execution
     def engine(self, dtype=None):
         dtype = self.math_mode if dtype is None else dtype
-        # a network whose activations once left the fp16 range of F32H2 runs in the fall-back mode from then on (engine.range_fallback;
+        # a network whose activations once left the fp16 range of F32H2 (or F16) runs in that mode's fall-back mode from then on (engine.range_fallback;
         # ``net.strict_range = True``: raise instead)
-        if dtype == _engine.F32H2 and self.__dict__.get("_range_fallback") is not None and not getattr(self, "strict_range", False):
-            dtype = self._range_fallback
+        if not getattr(self, "strict_range", False):
+            dtype = (self.__dict__.get("_range_fallback") or {}).get(dtype, dtype)       # (F32H2 -> F32X3, F16 -> BF16)
         eng = self._engines.get(dtype)
         if eng is None:
             eng = self._engines[dtype] = _engine.Engine(self, dtype)

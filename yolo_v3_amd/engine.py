@@ -20,10 +20,10 @@ import torch
 
 from . import _ffi, arch
 
-from ._ffi import ConvDesc, F32, BF16, F32X3, F32H2, ACT_LEAKY, ACT_LINEAR
+from ._ffi import ConvDesc, F32, BF16, F32X3, F32H2, F16, ACT_LEAKY, ACT_LINEAR
 
-_TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F32X3: torch.bfloat16, F32H2: torch.float16}   # element type of activation storage
-PLANES = {F32: 0, BF16: 1, F32X3: 3, F32H2: 2}   # 0: plain fp32 NHWC tensor; n > 0: n 16-bit planes [n][B,H,W,C]
+_TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F32X3: torch.bfloat16, F32H2: torch.float16, F16: torch.float16}   # element type of activation storage
+PLANES = {F32: 0, BF16: 1, F32X3: 3, F32H2: 2, F16: 1}   # 0: plain fp32 NHWC tensor; n > 0: n 16-bit planes [n][B,H,W,C]
 
 
 def alloc_act(B, h, w, c, dtype, device):
@@ -40,6 +40,9 @@ def to_planes(x_nhwc_f32, dtype):
         return x_nhwc_f32.float().contiguous()
     x = x_nhwc_f32.float().contiguous()
     out = torch.empty((np_,) + tuple(x.shape), device=x.device, dtype=_TORCH_DTYPE[dtype])
+    if dtype == F16:             # (yv3_split_planes' one plane is bf16)
+        _ffi.check(_ffi.lib().yv3_split_plane_f16(x.data_ptr(), out.data_ptr(), x.numel(), _ffi.stream_ptr()), "yv3_split_plane_f16")
+        return out
     _ffi.check(_ffi.lib().yv3_split_planes(x.data_ptr(), out.data_ptr(), x.numel(), np_, _ffi.stream_ptr()), "yv3_split_planes")
     return out
 
@@ -50,6 +53,9 @@ def from_planes(t, dtype):
     if np_ == 0 or t.dtype == torch.float32:
         return t
     out = torch.empty(tuple(t.shape[1:]), device=t.device, dtype=torch.float32)
+    if dtype == F16:
+        _ffi.check(_ffi.lib().yv3_merge_plane_f16(t.data_ptr(), out.data_ptr(), out.numel(), _ffi.stream_ptr()), "yv3_merge_plane_f16")
+        return out
     _ffi.check(_ffi.lib().yv3_merge_planes(t.data_ptr(), out.data_ptr(), out.numel(), np_, _ffi.stream_ptr()), "yv3_merge_planes")
     return out
 
@@ -58,12 +64,19 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+RANGE_FALLBACK = {F32H2: F32X3, F16: BF16}      # Engine.range_fallback: the mode that takes over after a RangeOverflow
+FALLBACK_TEXT = {          # (mode, what it falls back to, how to ask for that directly) of the one warning
+    F32H2: ("F32H2", "F32X3 (three bf16 planes: fp32 range, 24 bits, ~1.9x the time)", "F32X3 / F32"),
+    F16: ("F16", "BF16 (one bf16 plane: fp32 range, 8 bits instead of 11, the same time)", "BF16"),
+}
+
+
 class StreamKTimeout(_ffi.Yv3Error):
     """The kernels' status bit 1: a stream-K hand-over did not arrive (see Engine.raise_if_overflowed)."""
 
 
 class RangeOverflow(_ffi.Yv3Error):
-    """The kernels' status bit 0: a value left the fp16 range of the F32H2 planes (or BF16's first layer) and was saturated."""
+    """The kernels' status bit 0: a value left the fp16 range of the F32H2 planes, of F16's one plane (or BF16's first layer) and was saturated."""
 
 
 class PackedConv:
@@ -178,7 +191,8 @@ def pack_conv(module, spec, dtype, winograd=False, winograd4=True):
         alpha = None
         beta = bias.detach().float().contiguous().clone()
     w_orig, alpha_bn = w32, alpha
-    if dtype == F32H2 and spec.cin != 3:
+    if dtype in (F32H2, F16) and spec.cin != 3:
+        # (F16: the same scale -- one fp16 plane keeps its 11 bits for every weight of a row down to 2^-14 of the row's maximum)
         # fp16 planes keep a relative precision of 2^-22 only while the `lo` part is a normal fp16 number, i.e. for
         # |w| >= 2^-3 after scaling: bring EVERY OUTPUT CHANNEL's weights to max|w_row| in [1,2) with its own exact
         # power-of-two scale and fold the inverse into that channel's epilogue scale (also exact) -- rows whose
@@ -362,7 +376,7 @@ class Plan:
         ncu = ncu & ~7 if ncu >= 8 else 256
         # feature.mlist.0 + feature.mlist.1 run as ONE launch (csrc/conv_front.hip; exact fp32: csrc/conv_front_f32.hip); the first
         # layer's [B,H,W,32] activation is then never written (conv0_out stays allocated for the un-fused / layer-by-layer paths)
-        self.fused_front = bool(engine.fuse_front and dt in (F32H2, BF16, F32))
+        self.fused_front = bool(engine.fuse_front and dt in (F32H2, BF16, F32, F16))
         # ... and the first residual block (feature.mlist.2: 1x1 64->32 + 3x3 32->64 + add) as one more (csrc/conv_res64.hip,
         # csrc/conv_res64_f32.hip)
         self.fused_res64 = bool(self.fused_front and engine.fuse_res64)
@@ -702,13 +716,14 @@ class Engine:
                                                           p3.w.data_ptr(), p3.alpha.data_ptr(), p3.beta.data_ptr(), d3.y,
                                                           plan.B, plan.H // 2, plan.W // 2, _ffi.stream_ptr()), "yv3_res_block64_f32")
             return
-        front = _ffi.lib().yv3_conv_front if self.dtype == F32H2 else _ffi.lib().yv3_conv_front_bf16
+        lib = _ffi.lib()
+        front = {F32H2: lib.yv3_conv_front, BF16: lib.yv3_conv_front_bf16, F16: lib.yv3_conv_front_f16}[self.dtype]
         _ffi.check(front(x.data_ptr(), p0.w.data_ptr(), p0.alpha.data_ptr(), p0.beta.data_ptr(),
                                              p1.w.data_ptr(), p1.alpha.data_ptr(), p1.beta.data_ptr(), d1.y,
                                              plan.B, plan.H, plan.W, plan.flags.data_ptr(), _ffi.stream_ptr()), "yv3_conv_front")
         if plan.fused_res64:
             p2, p3, d3 = self.packed[2], self.packed[3], plan.descs[2]
-            res = _ffi.lib().yv3_res_block64 if self.dtype == F32H2 else _ffi.lib().yv3_res_block64_bf16
+            res = {F32H2: lib.yv3_res_block64, BF16: lib.yv3_res_block64_bf16, F16: lib.yv3_res_block64_f16}[self.dtype]
             _ffi.check(res(d1.y, p2.w.data_ptr(), p2.alpha.data_ptr(), p2.beta.data_ptr(),
                                                   p3.w.data_ptr(), p3.alpha.data_ptr(), p3.beta.data_ptr(), d3.y,
                                                   plan.B, plan.H // 2, plan.W // 2, plan.flags.data_ptr(), _ffi.stream_ptr()),
@@ -752,6 +767,9 @@ class Engine:
     OVERFLOW_MSG = ("an activation exceeded the fp16 range (|v| > 65504) and was saturated: math mode F32H2 cannot "
                     "represent this network/input; set net.math_mode = yolo_v3_amd.F32X3 (or F32) and rerun "
                     "(net.strict_range = False, the default, does that by itself)")
+    OVERFLOW_MSG_F16 = ("an activation exceeded the fp16 range (|v| > 65504) and was saturated: math mode F16 cannot represent this "
+                        "network/input; set net.math_mode = yolo_v3_amd.BF16 (the same cost, fp32's exponent range, 8 bits) or F32X3 / F32 "
+                        "and rerun (net.strict_range = False, the default, re-runs in BF16 by itself)")
     OVERFLOW_MSG_BF16 = ("the first layer of math mode BF16 runs on the fp16 matrix cores and needs |input| <= 4094 and "
                          "|weight| <= 255 (csrc/conv0.hip); this input / these weights exceed that and were saturated: "
                          "use net.math_mode = yolo_v3_amd.F32X3 (or F32)")
@@ -766,27 +784,31 @@ class Engine:
                 raise StreamKTimeout("a stream-K accumulator hand-over timed out: the schedule needs all of its workgroups resident at once "
                                      "and something else (another stream / thread / process running small batches) held part of the GPU.  "
                                      "Callers that share the GPU set net.stream_k = False (or net.deterministic = True)")
-            raise RangeOverflow(self.OVERFLOW_MSG_BF16 if self.dtype == BF16 else self.OVERFLOW_MSG)
+            raise RangeOverflow({BF16: self.OVERFLOW_MSG_BF16, F16: self.OVERFLOW_MSG_F16}.get(self.dtype, self.OVERFLOW_MSG))
 
     def range_fallback(self):
-        """After a RangeOverflow in the default mode: the engine that takes over -- F32X3, the same plane pipeline on three bf16
-        planes (fp32's exponent range, 24 significant bits) -- or None when there is none to fall back to (``net.strict_range = True``:
-        the caller wants the error; BF16: a reduced-precision mode the caller chose).  The choice is remembered on the network
-        (``YoloNet.engine`` hands out the fall-back engine wherever F32H2 is asked for from now on) and announced once."""
-        if self.dtype != F32H2 or getattr(self.net, "strict_range", False):
+        """After a RangeOverflow: the engine that takes over (RANGE_FALLBACK) -- for the default mode F32X3, the same plane pipeline on
+        three bf16 planes (fp32's exponent range, 24 significant bits); for F16, BF16 (the same cost class with fp32's exponent range:
+        the caller chose a reduced-precision mode) -- or None when there is none to fall back to (``net.strict_range = True``: the
+        caller wants the error; BF16: a reduced-precision mode the caller chose).  The choice is remembered on the network
+        (``net._range_fallback``: {mode asked for: mode that runs}; ``YoloNet.engine`` hands out the fall-back engine wherever this
+        engine's mode is asked for from now on) and announced once."""
+        to = RANGE_FALLBACK.get(self.dtype)
+        if to is None or getattr(self.net, "strict_range", False):
             return None
         import warnings
-        if getattr(self.net, "_range_fallback", None) is None:
-            warnings.warn("yolo_v3_amd: an activation left the fp16 range of math mode F32H2 (|v| > 65504); this network now runs in "
-                          "F32X3 (three bf16 planes: fp32 range, 24 bits, ~1.9x the time) -- set net.math_mode = F32X3 / F32 to avoid the "
-                          "first, discarded pass, or net.strict_range = True to get an error instead", RuntimeWarning)
-            self.net._range_fallback = F32X3
-        return self.net.engine(F32X3)
+        chosen = self.net.__dict__.setdefault("_range_fallback", {})
+        if self.dtype not in chosen:
+            warnings.warn("yolo_v3_amd: an activation left the fp16 range of math mode %s (|v| > 65504); this network now runs in %s -- "
+                          "set net.math_mode = %s to avoid the first, discarded pass, or net.strict_range = True to get an error instead"
+                          % FALLBACK_TEXT[self.dtype], RuntimeWarning)
+            chosen[self.dtype] = to
+        return self.net.engine(to)
 
     def checks_status(self):
-        """Does a forward of this engine have a kernel status word to look at?  F32H2 / BF16: fp16 saturation (+ stream-K hand-over);
+        """Does a forward of this engine have a kernel status word to look at?  F32H2 / F16 / BF16: fp16 saturation (+ stream-K hand-over);
         F32: only the F(4x4) stage's even schedule can set it (hand-over time-out on a shared GPU) -- not with ``net.stream_k = False``."""
-        return self.dtype in (F32H2, BF16) or (self.dtype == F32 and self.winograd and self.winograd4 and self.stream_k is not False)
+        return self.dtype in (F32H2, BF16, F16) or (self.dtype == F32 and self.winograd and self.winograd4 and self.stream_k is not False)
 
     def disable_stream_k(self):
         """After a StreamKTimeout: this engine stops using the stream-K schedule (plans are rebuilt without its workspace; holders
