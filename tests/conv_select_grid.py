@@ -131,7 +131,7 @@ def wino_ws_bytes(lib, dtype, B, size):
 
 def make_desc(lib, cfg, size, B, layer):
     """The descriptor engine.make_desc builds for this layer (fused decode on the plane modes' heads), with dummy pointers."""
-    dtype, options, tune, variant = ALL_CONFIGS[cfg]
+    dtype, options, tune, variant = ALL_CONFIGS[cfg] if cfg in ALL_CONFIGS else WIDE_HEAD_CONFIGS[cfg]
     variant = (variant or "").split("+")
     sp, H, W, cin_up = layer
     d = _ffi.ConvDesc()
@@ -154,7 +154,7 @@ def make_desc(lib, cfg, size, B, layer):
     if not sp.bn:
         d.out_dtype = F32
         if dtype != F32:                                   # fused decode: the logits are not materialised
-            d.y, d.dec_out, d.dec_stride, d.dec_out_batch_stride = None, PTR, float(size) / ho, 85 * 3 * ho * wo
+            d.y, d.dec_out, d.dec_stride, d.dec_out_batch_stride = None, PTR, float(size) / ho, sp.cout * ho * wo
             for i in range(6):
                 d.dec_anchors[i] = float(arch.DEFAULT_ANCHORS[i])
     sk_auto = B * (size // 32) ** 2 <= 1536 and not (options & _ffi.OPT_TWO_LANES)                   # engine.SK_AUTO_CELLS
@@ -174,6 +174,28 @@ def make_desc(lib, cfg, size, B, layer):
         if cin_up:
             d.x2_plane_stride = 2 * B * H * W * (sp.cin - cin_up)
     return d
+
+
+# ----------------------------------------------------------------------------- heads wider than 256 channels (tests/golden/conv_select_wide_heads.json)
+F16 = _ffi.F16
+WIDE_HEAD_CLASSES = (81, 82, 91, 123, 166, 300)          # cout = 3 * (5 + C) = 258, 261, 288, 384, 513, 915
+WIDE_HEAD_BATCHES = (2, 32, 65)                          # 13 x 13 pixels each: M = 338, 5408, and 10985 -- 86 row tiles of 128 x 3 channel tiles of
+#                                                          cout 384 = 258 GEMM tiles, the first batch that fills one round of 256 CUs in exact fp32
+WIDE_HEAD_CONFIGS = dict({k: CONFIGS[k] for k in ("f32", "f32.tune0=13", "f32.tune0=14", "f32h2", "f32x3", "bf16")}, f16=(F16, 0, (0, 0, 0), None))
+
+
+def wide_head_desc(lib, cfg, C, B):
+    """The descriptor engine.make_desc builds for the 13 x 13 head (cin 256 here, as the kernel tests') of a network with C classes at 416 x 416."""
+    sp = arch.ConvSpec("head%d" % C, 256, 3 * (5 + C), 1, 1, False, False)
+    return make_desc(lib, cfg, 416, B, (sp, 13, 13, 0))
+
+
+def wide_heads_table(lib, kernels=()):
+    """{"cus", "kernels", "heads": {"config/C/M": token}}: the table's token form (see table()) for every math mode, class count and batch above."""
+    kernels = list(kernels)
+    heads = {"%s/%d/%d" % (cfg, C, B * 169): _token(query(lib, wide_head_desc(lib, cfg, C, B)), kernels)
+             for cfg in WIDE_HEAD_CONFIGS for C in WIDE_HEAD_CLASSES for B in WIDE_HEAD_BATCHES}
+    return {"cus": 256, "heads": heads, "kernels": kernels}
 
 
 def classes(size):
