@@ -11,7 +11,12 @@ input-gradient kernel alone (yv3_train_conv0_dgrad[_bf16]) beside layer 0's wgra
 around 50 launches that rotate over enough dz buffers to exceed the 256 MiB Infinity Cache, and the rate over the bytes the kernel
 must move (dz read once, dx written).
 
-    python tools/train_bench.py [--batches 8 16] [--rounds 7] [--math f32 bf16 bf16_act] [--input-grad]
+--state backbone_eval_frozen instead times the fine-tuning step on a frozen eval-mode Darknet-53 (tests/train_states.py: heads trainable
+in train mode) with net.frozen_prefix off and on -- the 52 frozen convolutions on the training kernels, or on the inference engine --
+interleaved in the same way, for each --math, with the kernel-class split and the held memory of both, and the device memory the
+prefix engine keeps for good (its packed weights and one plan per (B, H, W)).
+
+    python tools/train_bench.py [--batches 8 16] [--rounds 7] [--math f32 bf16 bf16_act] [--input-grad] [--state backbone_eval_frozen]
 """
 import argparse
 import json
@@ -26,6 +31,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 from tests import train_ref as T                      # noqa: E402
+from tests import train_states as S                   # noqa: E402
 from tests import yolo_loss_ref as R                  # noqa: E402
 from tests.helpers import trained_like_stream         # noqa: E402
 from yolo_v3_amd import YoloNet, WeightManager, synth, arch, backprop, _ffi, F32, BF16, BF16_ACT  # noqa: E402
@@ -33,6 +39,10 @@ from yolo_v3_amd import YoloNet, WeightManager, synth, arch, backprop, _ffi, F32
 MATH = {"f32": F32, "bf16": BF16, "bf16_act": BF16_ACT}
 
 DEV = "cuda:0"
+# kernels only the inference engine launches (net.frozen_prefix): its convolutions, their Winograd input transforms, the widening of a
+# handed-over bf16 plane
+PREFIX_KERNELS = ("conv_igemm_f32", "conv_gemm1x1_f32", "conv_planes", "conv_front", "conv_res64", "conv_wino4", "wino4_input", "wino_input",
+                  "conv0_kernel", "conv0_mfma", "merge_planes")
 
 
 def timed(fn):
@@ -51,7 +61,7 @@ def kernel_classes(fn):
     cls = {}
     for ev in prof.key_averages():
         n = ev.key
-        k = ("input dgrad" if "conv0_dgrad" in n else "conv fwd" if "conv_gemm<0>" in n or "conv_bf16<0," in n else "conv dgrad" if "conv_gemm<1>" in n or "conv_bf16<1," in n
+        k = ("prefix (inference kernels)" if any(s in n for s in PREFIX_KERNELS) else "input dgrad" if "conv0_dgrad" in n else "conv fwd" if "conv_gemm<0>" in n or "conv_bf16<0," in n else "conv dgrad" if "conv_gemm<1>" in n or "conv_bf16<1," in n
              else "conv wgrad" if "conv_gemm<2>" in n or "conv_bf16<2," in n or "wgrad_reduce" in n
              else "cast" if "to_bf16" in n else "weight pack" if "pack_weight" in n
              else "BN / act" if any(s in n for s in ("channel_partials", "finalize", "bn_act", "eval_stats", "bias_bwd"))
@@ -147,12 +157,55 @@ def input_grad_cost(net, a):
     print(json.dumps(out))
 
 
+def frozen_prefix_cost(net, a):
+    """--state: the step under the state with net.frozen_prefix off / on, interleaved."""
+    S.STATES[a.state].apply(net)
+    n = backprop.frozen_prefix_ops(net)
+    out = {"state": a.state, "prefix_ops": n}
+    for B in a.batches:
+        x = torch.from_numpy(synth.images(B, 416, 7)).to(DEV)
+        tg = torch.from_numpy(R.random_rows(5, B, 30, 80, (0.03, 0.8)))
+        out[B] = {}
+        for m in a.math:
+            def step(on, math=MATH[m]):
+                net.backprop_math, net.frozen_prefix = math, on
+                net.zero_grad(set_to_none=True)
+                net(x, tg).backward()
+            fns = {"off_ms": lambda: step(False), "on_ms": lambda: step(True)}
+            net.repack()                                   # (the prefix engine of the batch before: its plan is not this one's)
+            torch.cuda.synchronize()
+            base = torch.cuda.memory_allocated()
+            for f in fns.values():
+                f()
+            times = {k: [] for k in fns}
+            for _ in range(a.rounds):
+                for k, f in fns.items():
+                    times[k].append(timed(f))
+            r = {k: round(float(np.median(v)), 3) for k, v in times.items()}
+            r["spread_ms"] = {k: [round(min(v), 3), round(max(v), 3)] for k, v in times.items()}
+            net.zero_grad(set_to_none=True)
+            torch.cuda.synchronize()
+            r["prefix_engine_MB"] = round((torch.cuda.memory_allocated() - base) / 1e6, 1)      # packed weights + the plan's buffers
+            for on in (False, True):
+                net.frozen_prefix = on
+                r["held_MB_" + ("on" if on else "off")] = held_mb(net, x, tg, MATH[m])
+                try:
+                    r["by_kernel_class_ms_" + ("on" if on else "off")] = kernel_classes(fns["on_ms" if on else "off_ms"])
+                except Exception as e:                   # (the profiler is a diagnostic only)
+                    r["by_kernel_class_ms_" + ("on" if on else "off")] = "profiler unavailable: %s" % e
+            out[B][m] = r
+            print(B, m, json.dumps(r), flush=True)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[8, 16])
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--math", nargs="+", choices=tuple(MATH), default=["f32"])
     ap.add_argument("--input-grad", action="store_true", help="time the step with net.input_grad off and on, and the layer-0 dgrad alone")
+    ap.add_argument("--state", choices=("all_train", "backbone_eval_frozen"), default="all_train",
+                    help="backbone_eval_frozen: time the fine-tuning step with net.frozen_prefix off and on")
     a = ap.parse_args()
     net = YoloNet((416, 416), numClass=80)
     WeightManager(net).load_stream(trained_like_stream(80))
@@ -160,6 +213,8 @@ def main():
     net.backprop = True
     if a.input_grad:
         return input_grad_cost(net, a)
+    if a.state != "all_train":
+        return frozen_prefix_cost(net, a)
     sd_gpu = {k: v.detach().clone() for k, v in net.state_dict().items()}
     out = {}
     for B in a.batches:

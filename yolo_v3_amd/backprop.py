@@ -31,7 +31,12 @@ in torch on the logits (``net.yoloK(lgK, img_dim, target)`` included) trains the
 
 The input gradient is opt-in (``net.input_grad = True``; an ``x`` that requires grad raises NotImplementedError otherwise).  The
 walk then runs down to layer 0, whose dgrad (conv0_dgrad) writes dL/dx in x's own NCHW layout, and ``x`` is a real input
-of the Function."""
+of the Function.
+
+``net.frozen_prefix = True`` (opt-in) runs the frozen eval-mode prefix of the net -- ``frozen_prefix_ops(net)`` leading ops, e.g. the
+52 of a frozen ``net.feature.eval()`` -- on the inference engine instead: a prefix engine (engine.Engine with n_conv) in the exact F32
+plan for F32 and in the BF16 plan for BF16 / BF16_ACT, whose outputs are copied into the run's buffers where a later op reads them
+(``_prefix``).  Everything from the first trainable or train-mode op on, the walk included, is as without the switch."""
 import numbers
 from collections import namedtuple
 
@@ -39,6 +44,7 @@ import torch
 import torch.nn as nn
 
 from . import _ffi
+from . import engine as _engine
 from . import yololayer as _yl
 
 
@@ -87,6 +93,32 @@ def graph(net):
     ops.append(_Op(net.up2.conv, h2, "up2"))
     predet(net.pre_det3, "pre_det3", r36, 2, src2="up2", cin_up=net.up2.conv.conv.out_channels)
     return ops
+
+
+FRONT_OPS = _engine.Engine.FRONT_CONVS     # the ops the inference plans run as the fused front: no prefix is shorter
+PREFIX_MODE = {_ffi.F32: _ffi.F32, _ffi.BF16: _ffi.BF16, _ffi.BF16_ACT: _ffi.BF16}      # net.backprop_math -> the prefix's inference mode
+
+
+def frozen_prefix_ops(net, input_grad=False):
+    """The number of leading ops of graph(net) that a training step may run on the inference engine (``net.frozen_prefix``): the
+    longest leading run in which no parameter requires grad and every BatchNorm is in eval mode -- there the training forward
+    computes what the inference engine computes, eval-mode BatchNorm folded into the conv epilogue, and no backward reaches it.  A
+    frozen head conv may be part of it.  0 when the input needs a gradient (`input_grad`), and when the run is shorter than the
+    fused front (FRONT_OPS), whose inner buffers the plans never write."""
+    return _prefix_len(graph(net), input_grad)
+
+
+def _prefix_len(ops, input_grad):
+    if input_grad:
+        return 0
+    n = 0
+    for op in ops:
+        c = op.conv
+        params = [c.weight, c.bias] if op.head else [c.weight, op.bn.weight, op.bn.bias]
+        if any(p.requires_grad for p in params) or (op.bn is not None and op.bn.training):
+            break
+        n += 1
+    return n if n >= FRONT_OPS else 0
 
 
 def _f32(t, what):
@@ -163,6 +195,8 @@ class _Run:
     def __init__(self, net, x, target, math=_ffi.F32, input_grad=False):
         self.net, self.x, self.target, self.math, self.input_grad = net, x, target, math, bool(input_grad)
         self.ops = graph(net)
+        # ops [0, prefix) run on the inference engine (net.frozen_prefix): they get a shape, need = False and no `saved` entry
+        self.prefix = _prefix_len(self.ops, self.input_grad) if getattr(net, "frozen_prefix", False) else 0
         self.saved = {}            # op index -> dict of tensors
         self.shape = {}            # buffer -> (B, H, W, C)
         self.need = {}             # buffer -> some parameter upstream of it needs a gradient
@@ -229,15 +263,45 @@ def _bn_act(lib, s, m, op, z, res, sv):
     return y
 
 
+def _prefix(run, m, bufs, bufs_b, logits):
+    """Ops [0, run.prefix) on the inference engine (net.frozen_prefix): one forward of the net's prefix engine in the inference mode
+    of PREFIX_MODE -- F32: the exact-fp32 plan; BF16 / BF16_ACT: the BF16 plan, which stores each activation once, in bf16, rounds
+    no z, and runs layer 0 as the inference front (the training kernels round x, z's operands and, in BF16_ACT, zb and y) -- then
+    the hand-over: every buffer a prefix op wrote and an op from run.prefix on reads is copied out of the plan, which the next
+    forward overwrites, in the form its reader expects (F32: fp32 in bufs; BF16_ACT: the bf16 plane in bufs_b; BF16: that and, for a
+    buffer read as a residual, its fp32 widening in bufs); a prefix head hands over its fp32 logits.  The prefix ops get their
+    shape and need = False, and nothing else: no saved entry, no weight pack, no z."""
+    n, ops = run.prefix, run.ops
+    eng = run.net.prefix_engine(PREFIX_MODE[run.math], n)
+    _, plan = eng.forward(run.x, logits=True)
+    read = {b for op in ops[n:] for b in (op.src, op.src2, op.res) if b is not None}
+    read_res = {op.res for op in ops[n:] if op.res is not None}
+    for op, sp in zip(ops[:n], eng.specs):
+        t = plan.layer_out[sp.name]
+        run.shape[op.out] = (plan.B,) + tuple(t.shape[-3:])
+        run.need[op.out] = False
+        if op.head:
+            bufs[op.out] = t.clone()
+            logits[op.head_idx] = (bufs[op.out], t.shape[1], t.shape[2])
+        elif op.out in read and m.bf16_operands:
+            bufs_b[op.out] = t[0].view(torch.int16).clone()
+            if m.cast_twins and op.out in read_res:                      # (fp32 y beside its bf16 copy: residuals are read from y)
+                bufs[op.out] = _engine.from_planes(t, eng.dtype)
+        elif op.out in read:
+            bufs[op.out] = t.clone()
+
+
 def net_forward(run, want_grad):
     """The training forward of the whole net up to the heads -> their logits [(fp32 NHWC tensor, h, w)] * 3; with want_grad the
-    run keeps what the walk needs."""
+    run keeps what the walk needs.  With run.prefix = n > 0 the inference engine runs ops [0, n) (_prefix)."""
     lib, s = _ffi.lib(), _ffi.stream_ptr()
     m, x = MATH[run.math], run.x
     act = m.act_dtype == torch.int16           # activations in bf16 only: bufs holds x and the head logits, bufs_b the rest
     B, _, H, W = x.shape
     bufs = {"x": x}
-    bufs_b = {"x": _bf16(lib, s, x, x.numel(), 1, 1, "x")} if m.bf16_operands else None     # bf16 conv inputs
+    bufs_b = None                              # bf16 conv inputs (the inference front reads x itself)
+    if m.bf16_operands:
+        bufs_b = {} if run.prefix else {"x": _bf16(lib, s, x, x.numel(), 1, 1, "x")}
     src = bufs_b if m.bf16_operands else bufs  # what the convs read
     outs = bufs_b if act else bufs             # where a conv_bn_relu's output (a later op's residual) lives
     last = {}                                  # buffer -> index of the last op that reads it in the forward
@@ -247,7 +311,9 @@ def net_forward(run, want_grad):
     run.shape["x"] = (B, H, W, 3)
     run.need["x"] = run.input_grad
     logits = [None] * 3
-    for i, op in enumerate(run.ops):
+    if run.prefix:
+        _prefix(run, m, bufs, bufs_b, logits)
+    for i, op in enumerate(run.ops[run.prefix:], run.prefix):
         c = op.conv
         params = [c.weight] + ([c.bias] if op.head else [op.bn.weight, op.bn.bias])
         run.need[op.out] = any(p.requires_grad for p in params) or run.need[op.src] or \
@@ -396,7 +462,7 @@ def walk(run, dlogits, scale=None):
 
     grads.update({op.out: dlogits[op.head_idx] for op in run.ops if op.head and dlogits[op.head_idx] is not None})
     for i in range(len(run.ops) - 1, -1, -1):
-        op, sv = run.ops[i], run.saved[i]
+        op, sv = run.ops[i], run.saved.get(i)     # (none for an op of the frozen prefix: its output is never needed)
         dy = grads.pop(op.out, None)
         if dy is None or not run.need[op.out]:
             continue

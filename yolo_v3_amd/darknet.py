@@ -290,8 +290,22 @@ class YoloNet(nn.Module):
         # True: the training path (net(x, target) with backprop, net.logits(x)) also fills x.grad when x requires grad; False: such
         # an x raises NotImplementedError
         self.input_grad = False
+        # True: the training path runs the net's frozen eval-mode prefix (backprop.frozen_prefix_ops(net) leading convolutions: no
+        # trainable parameter, BatchNorm in .eval()) on the inference kernels -- backprop_math F32: the exact F32 plan; BF16 and
+        # BF16_ACT: the BF16 plan -- and the rest as before; False, or no such prefix: the training kernels run every layer
+        self.frozen_prefix = False
+        self._prefix_engines = {}
 
     # ---- HIP execution
+    def prefix_engine(self, dtype, n_conv):
+        """The engine of the first n_conv convolutions in math mode dtype (engine.Engine's n_conv), cached per (dtype, n_conv): its
+        packed weights and plans follow those layers' tensors only."""
+        cache = self.__dict__.setdefault("_prefix_engines", {})
+        eng = cache.get((dtype, n_conv))
+        if eng is None:
+            eng = cache[(dtype, n_conv)] = _engine.Engine(self, dtype, n_conv)
+        return eng
+
     def engine(self, dtype=None):
         dtype = self.math_mode if dtype is None else dtype
         # a network whose activations once left the fp16 range of F32H2 (or F16) runs in that mode's fall-back mode from then on (engine.range_fallback;
@@ -315,6 +329,7 @@ class YoloNet(nn.Module):
         ``net.weight_check = "checksum"`` (engine.Engine._signature)."""
         for eng in self._engines.values():
             eng.invalidate()
+        self.__dict__.setdefault("_prefix_engines", {}).clear()         # (held by nobody else: rebuilt on the next training step)
 
     def load_state_dict(self, state_dict, *args, **kwargs):
         out = super().load_state_dict(state_dict, *args, **kwargs)
@@ -325,6 +340,7 @@ class YoloNet(nn.Module):
     def __getstate__(self):
         state = self.__dict__.copy()
         state["_engines"] = {}
+        state["_prefix_engines"] = {}
         state.pop("_range_fallback", None)
         state.pop("_detectors", None)
         state.pop("_sharded_detectors", None)

@@ -315,7 +315,8 @@ def out_hw(h, w, k, stride):
 
 
 class Plan:
-    """Buffers + kernel descriptors for one (B, H, W)."""
+    """Buffers + kernel descriptors for one (B, H, W).  A plan of a prefix engine (``engine.n_conv`` < 75) holds the buffers and
+    launches of the first n_conv convolutions only, its head convs in the ``logits=True`` form: no detections, no decode."""
 
     @staticmethod
     def geometry(engine, H, W):
@@ -332,7 +333,8 @@ class Plan:
             raise _ffi.Yv3Error("input height/width must be multiples of 32 (got %dx%d)" % (H, W))
         self.B, self.H, self.W = B, H, W
         dev, dt = engine.device, engine.dtype
-        packed = engine.packed
+        packed, specs, n_conv = engine.packed, engine.all_specs, engine.n_conv
+        logits = bool(logits or n_conv < len(specs))
         nc = engine.num_class
         attrib = 5 + nc
         keep = []            # every buffer the descriptors point to
@@ -383,8 +385,10 @@ class Plan:
         self.first_desc = 3 if self.fused_res64 else (1 if self.fused_front else 0)
 
         def conv(i, x, h, w, residual=None, x2=None, cin_up=0, out_dtype=None):
+            ho, wo = out_hw(h, w, specs[i].k, specs[i].stride)
+            if i >= n_conv:           # past a prefix engine's last convolution: the geometry only
+                return None, ho, wo
             pc = packed[i]
-            ho, wo = out_hw(h, w, pc.spec.k, pc.spec.stride)
             head = out_dtype == F32 and dt != F32
             y = None if (head and self.fused_decode) else buf(ho, wo, pc.spec.cout, dt if out_dtype is None else out_dtype)
             if head:
@@ -436,11 +440,11 @@ class Plan:
         h1 = branch(cur, h, w)
         u1, _, _ = conv(i, h1, h, w); i += 1                                      # up1.conv (13x13)
         t61, h61, w61 = r61
-        h2 = branch(u1, h61, w61, x2=t61, cin_up=packed[i - 1].spec.cout)         # nearest x2 + cat fused
+        h2 = branch(u1, h61, w61, x2=t61, cin_up=specs[i - 1].cout)         # nearest x2 + cat fused
         u2, _, _ = conv(i, h2, h61, w61); i += 1                                  # up2.conv (26x26)
         t36, h36, w36 = r36
-        branch(u2, h36, w36, x2=t36, cin_up=packed[i - 1].spec.cout)
-        assert i == len(packed) == 75 and self.desc_spec[:3] == [1, 2, 3]
+        branch(u2, h36, w36, x2=t36, cin_up=specs[i - 1].cout)
+        assert i == len(specs) == 75 and len(packed) == n_conv and self.desc_spec[:3] == [1, 2, 3]
 
         self._keep = keep
         self.n_desc = len(descs)
@@ -449,9 +453,11 @@ class Plan:
         self.N = sum(self.rows)
         self.attrib = attrib
         self._dets_ptr = None
+        self.decode_args = []
+        if n_conv < len(specs):
+            return
         # decode parameters (yololayer.py:36-38): stride = H_img / nH, anchors by mask
         anchors = engine.anchors
-        self.decode_args = []
         row0 = 0
         for (lg, hh, ww), mask in zip(self.logits, arch.ANCHOR_MASKS):
             flat = []
@@ -526,14 +532,22 @@ class Plan:
 
 
 class Engine:
-    """Packs a YoloNet's parameters and runs the static plan."""
+    """Packs a YoloNet's parameters and runs the static plan.  n_conv < 75 makes a prefix engine (the frozen eval-mode prefix of a
+    training step, yolo_v3_amd/backprop.py): it packs the first n_conv convolutions only, its signature is built from those layers'
+    tensors only -- a change of any other parameter, an optimizer step on the trainable rest, moves nothing -- and its plans hold
+    the first n_conv launches.  It covers at least the fused front (FRONT_CONVS)."""
+    FRONT_CONVS = 4                   # feature.mlist.0, .1 and the first residual block: two launches whose inner buffers are never written
 
-    def __init__(self, net, dtype=F32):
+    def __init__(self, net, dtype=F32, n_conv=75):
         self.net = net
         self.dtype = dtype
         self.num_class = net.numClass
         self.anchors = [float(a) for a in net.anchors_flat]
-        self.specs = arch.conv_specs(self.num_class)
+        self.all_specs = arch.conv_specs(self.num_class)
+        if not self.FRONT_CONVS <= n_conv <= len(self.all_specs):
+            raise _ffi.Yv3Error("an engine covers the first %d to %d convolutions, got %r" % (self.FRONT_CONVS, len(self.all_specs), n_conv))
+        self.n_conv = int(n_conv)
+        self.specs = self.all_specs[:self.n_conv]        # what this engine packs and runs
         self.packed = None
         self.device = None
         self._sig = None
@@ -730,7 +744,7 @@ class Engine:
                        "yv3_res_block64")
 
     def run_conv_sequence(self, plan, dets=None):
-        """The remaining convolutions (74, or 73 behind a fused front).  With a fused-decode plan `dets` (the detections
+        """The remaining convolutions (74, or 73 behind a fused front; a prefix engine: those of its n_conv).  With a fused-decode plan `dets` (the detections
         tensor the head convs write) is required and `run_decode` is a no-op."""
         if plan.fused_decode:
             if dets is None:
@@ -835,6 +849,8 @@ class Engine:
         at the start of the next call on the same plan); `Detector` checks the flag with its single D2H copy of the
         box counts either way.  F32X3 has fp32's exponent range and never waits; exact F32 waits the same way while its F(4x4,3x3) stage may use the
         even schedule (``checks_status``: a hand-over time-out on a shared GPU is the one status it can report; not under ``net.stream_k = False``)."""
+        if not logits and self.n_conv < len(self.all_specs):
+            raise _ffi.Yv3Error("a prefix engine computes no detections: call forward(x, logits=True) and read plan.layer_out")
         x = self.prepare_input(x)
         with torch.cuda.device(x.device):
             self.ensure_packed()
