@@ -692,6 +692,85 @@ int yv3_train_bn_act_bwd_bf16(const void* z, const float* dy, const float* mean,
 int yv3_train_bias_bwd_bf16(const float* dlogits, const float* scale, void* dout, float* dbias, long long P, int C, void* ws,
                             size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Baseline JPEG decode (csrc/jpeg_parse.cpp, csrc/jpeg_entropy.h, csrc/jpeg.hip): file bytes -> uint8 RGB [H][W][3], the bits
+ * libjpeg(-turbo)'s defaults give (integer "islow" IDCT, "fancy" chroma upsampling, fixed-point YCbCr -> RGB), for a batch of
+ * files in four launches.  The host parser accepts only what it positively recognises; every other file gets a reason and is
+ * the caller's to decode elsewhere (yolo_v3_amd.jpeg falls back to PIL).  Errors in the entropy-coded data are found on the
+ * device and reported per image in status[]; such an image's destination bytes are unspecified (inside its own extent).
+ * ------------------------------------------------------------------------------------------ */
+
+/* yv3_jpeg_info.reason: why yv3_jpeg_parse refuses a file (0 = accepted) */
+#define YV3_JPEG_OK            0
+#define YV3_JPEG_NOT_JPEG      1   /* no SOI                                                                   */
+#define YV3_JPEG_MALFORMED     2   /* a header segment that is cut short or contradicts itself                 */
+#define YV3_JPEG_PROGRESSIVE   3   /* SOF2                                                                     */
+#define YV3_JPEG_SOF           4   /* arithmetic, lossless or hierarchical frames (SOF3, 5..7, 9..11, 13..15)  */
+#define YV3_JPEG_PRECISION     5   /* samples or quantisation tables wider than 8 bits                         */
+#define YV3_JPEG_COMPONENTS    6   /* neither 1 nor 3 components (CMYK / YCCK)                                 */
+#define YV3_JPEG_COLORSPACE    7   /* 3 components not known to be YCbCr (Adobe APP14, or no JFIF and ids != 1,2,3) */
+#define YV3_JPEG_SAMPLING      8   /* luma not 1x1 / 2x1 / 2x2, or chroma not 1x1 (4:4:0, 4:1:1, ...)          */
+#define YV3_JPEG_MULTISCAN     9   /* the first scan does not hold all components, or something other than EOI follows it */
+#define YV3_JPEG_TABLES        10  /* a table the scan names is missing or invalid when SOS is reached         */
+#define YV3_JPEG_SIZE          11  /* a side of 0 or above 16384                                               */
+
+/* status[b] of yv3_jpeg_decode_batch (0 = decoded) */
+#define YV3_JPEG_S_INFO        1   /* the record is not one yv3_jpeg_parse accepts                              */
+#define YV3_JPEG_S_BOUNDS      2   /* the scan, the destination or the workspace share lies outside its buffer */
+#define YV3_JPEG_S_HUFFTABLE   3   /* a Huffman spec that is no prefix code                                     */
+#define YV3_JPEG_S_CODE        4   /* a bit pattern that is no code of the table                                */
+#define YV3_JPEG_S_OVERRUN     5   /* the data ended inside a unit                                              */
+#define YV3_JPEG_S_COEF        6   /* a run past coefficient 63, or a block past the unit's last one            */
+#define YV3_JPEG_S_MARKER      7   /* restart markers: wrong count or order, or a marker inside a unit          */
+#define YV3_JPEG_S_EXTRA       8   /* whole bytes left over at the end of a unit                                */
+#define YV3_JPEG_S_DC          9   /* a DC value outside 16 bits                                                */
+
+typedef struct yv3_jpeg_info {
+    long long scan_offset;            /* first entropy-coded byte, from the start of the file                                  */
+    long long scan_length;            /* bytes up to the marker that ends the scan (or to the end of a truncated file)         */
+    int width, height, ncomp;
+    int restart_interval;             /* MCUs per restart segment, 0 = none                                                    */
+    int reason;                       /* YV3_JPEG_*: 0 = every field is valid and the file is one the decoder takes            */
+    int has_exif;                     /* an APP1 "Exif" segment is present (the orientation is the caller's to read)           */
+    unsigned char h[4], v[4];         /* sampling factors per component, as in SOF                                             */
+    unsigned char tq[4], td[4], ta[4];/* quantiser index (SOF), DC and AC Huffman selector (SOS) per component                 */
+    unsigned char quant_defined[4];
+    unsigned char huff_defined[8];    /* tables 0..3: DC 0..3, tables 4..7: AC 0..3                                            */
+    unsigned char quant[4][64];       /* natural (row-major) order                                                             */
+    unsigned char huff_counts[8][16]; /* codes of length 1..16                                                                 */
+    unsigned char huff_values[8][256];
+} yv3_jpeg_info;
+
+/* Host only, no GPU: walks the markers of data[0, n) and fills *out.  Returns YV3_EINVAL for a null pointer, else 0 with
+ * out->reason set.  Accepted (reason 0): SOF0 / SOF1, 8-bit samples and tables, 1 component or 3 YCbCr components (a JFIF
+ * marker, or ids 1,2,3; no Adobe APP14), one interleaved scan over all components, luma 1x1 / 2x1 / 2x2 with chroma 1x1,
+ * sides <= 16384, every table defined before SOS.  No byte outside data[0, n) is read, whatever the bytes are. */
+int yv3_jpeg_parse(const unsigned char* data, size_t n, yv3_jpeg_info* out);
+
+typedef struct yv3_jpeg_batch_desc {
+    const unsigned char* src;         /* device: the files' bytes                                                              */
+    long long src_bytes;
+    const long long* src_offsets;     /* device [B]: file b starts at src + src_offsets[b] (any alignment; files may repeat)   */
+    const yv3_jpeg_info* infos;       /* device [B]: the parser's records -- what the kernels read and re-check                */
+    const yv3_jpeg_info* infos_host;  /* host [B]: the same records, for the argument checks and the launch geometry           */
+    unsigned char* dst;               /* device: image b = uint8 RGB [H][W][3] at dst + dst_offsets[b]                         */
+    long long dst_bytes;
+    const long long* dst_offsets;     /* device [B]: checked against dst_bytes on the device, in 64 bits                       */
+    int* status;                      /* device [B] out: YV3_JPEG_S_*                                                          */
+    int B;
+} yv3_jpeg_batch_desc;
+
+/* Host only: bytes of device workspace a batch of these (host) records needs -- per image the int16 coefficients, the uint8
+ * component planes and the restart-segment offsets.  0 on a bad argument; a record with reason != 0 adds nothing. */
+size_t yv3_jpeg_workspace_bytes(const yv3_jpeg_info* infos_host, int B);
+
+/* Enqueues the decode of B files on `stream`: layout, entropy decode (one workgroup per image, one lane per restart segment),
+ * IDCT, upsampling + colour.  ws must be 256-byte aligned (the kernels make 16-byte accesses at 256-aligned offsets from it).
+ * YV3_EINVAL (null pointer, ws not 256-aligned, B outside 1..65535, non-positive sizes), YV3_ESHAPE (a host record
+ * with reason != 0 or fields the parser cannot produce), YV3_EWORKSPACE -- all before any launch.  Integer arithmetic only:
+ * identical calls give identical bits. */
+int yv3_jpeg_decode_batch(const yv3_jpeg_batch_desc* desc, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

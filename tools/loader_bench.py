@@ -4,6 +4,10 @@ their label files in a temporary directory, bs 16, dim 416, whole epochs ending 
   defaults   read and decode in the calling thread, every epoch (what TrainBatches did before it had options)
   workers    workers=8: the next batches' files are decoded on threads
   resident   cache_bytes holding the whole list, measured from the second epoch on: no file is read, no pixel uploaded
+  defaults_gpu / workers_gpu   the first two with decode="gpu": the JPEGs are decoded on the GPU (yolo_v3_amd/jpeg.py), one batch ahead
+  *+step     the four above with a stand-in training step after every batch: fp32 matrix products on the current stream, sized at
+             start-up to --step-ms of device time and only enqueued (as a training loop enqueues its step), so that the setting's
+             ms per batch minus --step-ms is what the loader adds to a step it can overlap with
 Rounds are interleaved (one epoch of every setting per round); per setting the median, minimum and maximum of the per-epoch
 ms per batch, the batches per second of the median, the host's share (time inside ``next()``, before the synchronise) and the
 bytes uploaded per batch as the code counts them (``augment.counters``).  One JSON line per setting.
@@ -54,7 +58,30 @@ def write_files(root, seed=0, n_labels=8):
     return lst
 
 
-def epoch(loader):
+def make_step(step_ms):
+    """A function that enqueues about ``step_ms`` of matrix products on the current stream, and the device ms it measured for it."""
+    a = torch.randn(4096, 4096, device="cuda")
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(3):
+        a @ a
+    e0.record()
+    for _ in range(10):
+        a @ a
+    e1.record()
+    torch.cuda.synchronize()
+    reps = max(1, int(round(step_ms / (e0.elapsed_time(e1) / 10))))
+
+    def step():
+        for _ in range(reps):
+            a @ a
+    e0.record()
+    step()
+    e1.record()
+    torch.cuda.synchronize()
+    return step, e0.elapsed_time(e1)
+
+
+def epoch(loader, step=None):
     """One epoch: (wall ms per batch up to the synchronise, host ms per batch inside next(), upload bytes per batch)."""
     before = dict(aug.counters)
     torch.cuda.synchronize()
@@ -67,6 +94,8 @@ def epoch(loader):
         if batch is None:
             break
         n += 1
+        if step is not None:
+            step()
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     return wall * 1e3 / n, host * 1e3 / n, (aug.counters["upload_bytes"] - before["upload_bytes"]) / n
@@ -77,27 +106,35 @@ def main():
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workers", type=int, default=8)
+    ap.add_argument("--step-ms", type=float, default=80.0)
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as root:
         lst = write_files(root)
         make = lambda **kw: aug.TrainBatches(lst, BS, (DIM, DIM), seed=1, **kw)
-        loaders = {"defaults": make(), "workers": make(workers=a.workers), "resident": make(cache_bytes=make().decoded_bytes())}
+        loaders = {"defaults": make(), "workers": make(workers=a.workers), "resident": make(cache_bytes=make().decoded_bytes()),
+                   "defaults_gpu": make(decode="gpu"), "workers_gpu": make(workers=a.workers, decode="gpu")}
+        step, step_ms = make_step(a.step_ms)
+        steps = {}
+        for k in ("defaults", "workers", "defaults_gpu", "workers_gpu"):
+            loaders[k + "+step"] = make(workers=loaders[k].workers, decode=loaders[k].decode)
+            steps[k + "+step"] = step
         epoch(loaders["resident"])                         # the first epoch fills the arena
         assert loaders["resident"].resident_images() == N_IMAGES
         samples = {k: [] for k in loaders}
         for r in range(a.warmup + a.rounds):
             for k, loader in loaders.items():              # interleaved: every setting once per round
-                s = epoch(loader)
+                s = epoch(loader, steps.get(k))
                 if r >= a.warmup:
                     samples[k].append(s)
         for k, v in samples.items():
             wall = sorted(s[0] for s in v)
             med = float(np.median(wall))
             print(json.dumps({"setting": k, "bs": BS, "dim": DIM, "src": "%dx%d jpeg q90" % (W, H), "images": N_IMAGES,
-                              "workers": loaders[k].workers, "cache_bytes": loaders[k].cache_bytes,
+                              "workers": loaders[k].workers, "cache_bytes": loaders[k].cache_bytes, "decode": loaders[k].decode,
                               "ms_per_batch": round(med, 3), "min_ms": round(wall[0], 3), "max_ms": round(wall[-1], 3),
                               "batches_per_s": round(1e3 / med, 1), "host_ms_per_batch": round(float(np.median([s[1] for s in v])), 3),
-                              "upload_bytes_per_batch": int(np.median([s[2] for s in v])), "rounds": a.rounds}))
+                              "upload_bytes_per_batch": int(np.median([s[2] for s in v])), "rounds": a.rounds,
+                              "step_ms": round(step_ms, 3) if k in steps else None}))
 
 
 if __name__ == "__main__":

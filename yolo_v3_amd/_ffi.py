@@ -92,6 +92,32 @@ class YoloLossDesc(ctypes.Structure):
                 ("sums", c_void_p), ("counts", c_void_p), ("status", c_void_p)]
 
 
+JPEG_OK, JPEG_NOT_JPEG, JPEG_MALFORMED, JPEG_PROGRESSIVE, JPEG_SOF, JPEG_PRECISION, JPEG_COMPONENTS = range(7)
+JPEG_COLORSPACE, JPEG_SAMPLING, JPEG_MULTISCAN, JPEG_TABLES, JPEG_SIZE = range(7, 12)
+(JPEG_S_INFO, JPEG_S_BOUNDS, JPEG_S_HUFFTABLE, JPEG_S_CODE, JPEG_S_OVERRUN, JPEG_S_COEF, JPEG_S_MARKER, JPEG_S_EXTRA,
+ JPEG_S_DC) = range(1, 10)
+
+
+class JpegInfo(ctypes.Structure):
+    """struct yv3_jpeg_info (include/yv3.h)."""
+    _fields_ = [("scan_offset", c_longlong), ("scan_length", c_longlong),
+                ("width", c_int), ("height", c_int), ("ncomp", c_int), ("restart_interval", c_int),
+                ("reason", c_int), ("has_exif", c_int),
+                ("h", ctypes.c_ubyte * 4), ("v", ctypes.c_ubyte * 4),
+                ("tq", ctypes.c_ubyte * 4), ("td", ctypes.c_ubyte * 4), ("ta", ctypes.c_ubyte * 4),
+                ("quant_defined", ctypes.c_ubyte * 4), ("huff_defined", ctypes.c_ubyte * 8),
+                ("quant", ctypes.c_ubyte * 64 * 4), ("huff_counts", ctypes.c_ubyte * 16 * 8),
+                ("huff_values", ctypes.c_ubyte * 256 * 8)]
+
+
+class JpegBatchDesc(ctypes.Structure):
+    """struct yv3_jpeg_batch_desc (include/yv3.h)."""
+    _fields_ = [("src", c_void_p), ("src_bytes", c_longlong), ("src_offsets", c_void_p),
+                ("infos", c_void_p), ("infos_host", c_void_p),
+                ("dst", c_void_p), ("dst_bytes", c_longlong), ("dst_offsets", c_void_p),
+                ("status", c_void_p), ("B", c_int)]
+
+
 _SIGNATURES = {
     "yv3_version": (c_int, []),
     "yv3_conv_workspace_bytes": (ctypes.c_size_t, []),
@@ -164,6 +190,9 @@ _SIGNATURES = {
     "yv3_train_upcat_bwd": (c_int, [c_void_p] * 3 + [c_int] * 7 + [c_void_p]),
     "yv3_train_to_bf16": (c_int, [c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p]),
     "yv3_train_conv_fwd_bf16o": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
+    "yv3_jpeg_parse": (c_int, [c_void_p, c_size_t, ctypes.POINTER(JpegInfo)]),
+    "yv3_jpeg_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "yv3_jpeg_decode_batch": (c_int, [ctypes.POINTER(JpegBatchDesc), c_void_p, c_size_t, c_void_p]),
 }
 # a _bf16 twin takes its base entry's arguments, with bf16 tensors where the base has fp32 ones (all void* here)
 _SIGNATURES.update({twin: _SIGNATURES[twin.replace("_bf16", "")] for twin in (

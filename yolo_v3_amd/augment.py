@@ -344,6 +344,16 @@ def _load_source(img_path, lab_path):
     return evaluate.read_image_rgb(img_path), read_labels(lab_path)
 
 
+def _load_bytes(img_path, lab_path):
+    """``decode="gpu"``: a worker only reads the file and parses its header (a file the GPU decoder does not take is decoded
+    here by `read_image_rgb`, as in ``decode="pil"``; its exception, if any, is raised at its batch)."""
+    from . import jpeg
+    src = jpeg.Source(img_path)
+    if src.error is not None:
+        raise src.error
+    return src, read_labels(lab_path)
+
+
 class TrainBatches:
     """Training batches ``(x, target)`` from the reference's list file (one image path per line).
 
@@ -362,10 +372,20 @@ class TrainBatches:
     ``arena_admit`` until it is full; a resident image is never read or decoded again (its label rows stay on the host), and a
     batch of resident images reaches the kernels without any pixel copy.  ``decoded_bytes()`` is the budget that holds the list.
 
+    ``decode="gpu"`` (default ``"pil"``): the same batches, bit for bit, with the JPEGs decoded on the GPU (`yolo_v3_amd.jpeg`):
+    the host -- the workers, when there are any -- only reads the files' bytes and parses their headers; batch k+1's decode is
+    enqueued on a stream the loader owns before batch k is handed out, and batch k's consumer waits for batch k's own event
+    (measured against a step that fills every CU the decode did not overlap with it: DESIGN.md section 8f); with ``cache_bytes``
+    the kernels write straight into the arena.  Files the GPU decoder does not take go through `read_image_rgb` as before.  The
+    switch is not part of a ``state_dict``'s config: both settings give the same bits.
+
     ``state_dict()`` / ``load_state_dict()`` resume between two batches with the same data order."""
 
     def __init__(self, list_file, batch_size, dim, seed, shuffle=True, max_labels=MAX_LABELS, multiscale=None, dim_interval=10,
-                 workers=0, prefetch=2, cache_bytes=0, **aug):
+                 workers=0, prefetch=2, cache_bytes=0, decode="pil", **aug):
+        if decode not in ("pil", "gpu"):
+            raise ValueError("decode must be 'pil' or 'gpu'")
+        self.decode, self._side = decode, None
         with open(list_file, 'r') as f:
             self.img_list = [line.strip() for line in f.readlines() if line.strip()]
         self.label_list = [label_path(p) for p in self.img_list]
@@ -422,7 +442,8 @@ class TrainBatches:
     # ---- the host half --------------------------------------------------------------------------------------------------------
     def host_batches(self):
         """One epoch's batches as ``(images, labels, params, dim)``, everything ``augment_batch`` takes, without touching a GPU.
-        ``images[i]`` is None for a source that is resident in the arena (``params`` were drawn with its recorded shape)."""
+        ``images[i]`` is None for a source that is resident in the arena (``params`` were drawn with its recorded shape); with
+        ``decode="gpu"`` it is the undecoded `jpeg.Source` (``.shape`` from its header)."""
         for _, images, labels, params, dim in self._host_batches():
             yield images, labels, params, dim
 
@@ -437,6 +458,7 @@ class TrainBatches:
         order, seeds, dims = epoch_schedule(self.seed, epoch, n, bs, self.shuffle, self.multiscale, self.dim_interval)
         n_batches = len(self)
         pool, pending = None, {}                         # pending: batch -> one future (or None: resident) per image
+        load = _load_bytes if self.decode == "gpu" else _load_source
         if self.workers > 0:
             from concurrent.futures import ThreadPoolExecutor
             pool = ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix="yv3-decode")
@@ -446,11 +468,11 @@ class TrainBatches:
                 if pool is not None:
                     for q in range(k, min(k + self.prefetch, n_batches - 1) + 1):
                         if q not in pending:
-                            pending[q] = [None if j in self._resident else pool.submit(_load_source, self.img_list[j], self.label_list[j])
+                            pending[q] = [None if j in self._resident else pool.submit(load, self.img_list[j], self.label_list[j])
                                           for j in (int(j) for j in order[q * bs:(q + 1) * bs])]
                     loaded = [None if f is None else f.result() for f in pending.pop(k)]
                 else:
-                    loaded = [None if j in self._resident else _load_source(self.img_list[j], self.label_list[j]) for j in idx]
+                    loaded = [None if j in self._resident else load(self.img_list[j], self.label_list[j]) for j in idx]
                 images, labels, shapes = [], [], []
                 for j, got in zip(idx, loaded):
                     if got is None:
@@ -460,7 +482,7 @@ class TrainBatches:
                     else:
                         img, rows = got
                         images.append(img)
-                        shapes.append(img.shape[:2])
+                        shapes.append(tuple(img.shape[:2]))
                     labels.append(rows)
                 params = sample_params(seeds[k * bs:k * bs + len(idx)], shapes=shapes, **self.aug)
                 self._pos = (epoch, k + 1)
@@ -491,7 +513,73 @@ class TrainBatches:
                 out[i] = self._resident[j][0]
         return out
 
+    # ---- decode="gpu" ---------------------------------------------------------------------------------------------------------
+    def _launch(self, batch):
+        """Enqueue the decode of a host batch's sources on the loader's stream: those the arena admits (in batch order, by the
+        same rule and so at the same offsets as ``decode="pil"``) straight into it, the others into a buffer of the batch."""
+        from . import jpeg
+        idx, images, labels, params, dim = batch
+        new = [i for i, im in enumerate(images) if im is not None]
+        admitted, offsets = [], []
+        if self.cache_bytes > 0 and new:
+            offs, _ = arena_admit([images[i].nbytes for i in new], self.cache_bytes, self._arena_end)
+            for i, off in zip(new, offs):
+                if off is None:
+                    continue
+                if self._arena is None:
+                    self._arena = torch.empty(self.cache_bytes, dtype=torch.uint8, device="cuda")
+                    self._side.wait_stream(torch.cuda.current_stream())      # whatever used these bytes before has finished
+                admitted.append(i)
+                offsets.append(off)
+                self._arena_end = off + images[i].nbytes
+        rest = [i for i in new if i not in admitted]
+        jobs = []
+        if admitted:
+            jobs.append((admitted, jpeg.submit([images[i] for i in admitted], stream=self._side, dst=(self._arena, offsets))))
+        if rest:
+            jobs.append((rest, jpeg.submit([images[i] for i in rest], stream=self._side)))
+        return batch, admitted, jobs, self._pos
+
+    def _complete(self, launched):
+        batch, admitted, jobs, pos = launched
+        idx, images, labels, params, dim = batch
+        out = list(images)
+        for which, job in jobs:
+            for i, view in zip(which, job.finish()):         # raises what read_image_rgb raises for a file nobody can decode
+                out[i] = view
+        for i in admitted:
+            self._resident[idx[i]] = (out[i], labels[i])
+        for i, j in enumerate(idx):
+            if out[i] is None:
+                out[i] = self._resident[j][0]
+        self._pos = pos                                      # the host half runs one batch ahead: report the batch handed out
+        return augment_batch(out, labels, dim, params, self.max_labels)
+
+    def _iter_gpu(self):
+        if self._side is None:
+            self._side = torch.cuda.Stream(priority=-1)      # few, long-running workgroups (no measured effect under a CU-filling step)
+        host = self._host_batches()
+        try:
+            ahead = None
+            for batch in host:
+                launched = self._launch(batch)               # batch k+1 is enqueued before batch k is handed out
+                if ahead is not None:
+                    x = self._complete(ahead)
+                    ahead = launched
+                    yield x
+                    continue
+                ahead = launched
+            if ahead is not None:
+                yield self._complete(ahead)
+        finally:
+            host.close()
+
     def __iter__(self):
+        if self.decode == "gpu":
+            return self._iter_gpu()
+        return self._iter_pil()
+
+    def _iter_pil(self):
         host = self._host_batches()
         try:
             for idx, images, labels, params, dim in host:

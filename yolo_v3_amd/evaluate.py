@@ -242,13 +242,18 @@ def read_image_rgb(path):
         return np.asarray(im.convert("RGB"), dtype=np.uint8).copy()
 
 
-def generate_results_file(net, target_txt, classes_names, out, bs, dim, is_letterbox=False):
+def generate_results_file(net, target_txt, classes_names, out, bs, dim, is_letterbox=False, decode="pil"):
     """reference evaluate.py:208-219: the COCO-results file of a list of images -- ``target_txt`` is the reference's text file with one
     image path per line (a list of paths, or of ``(path, uint8 RGB [H,W,3] array)`` pairs, is accepted too).  Per batch of ``bs``
     images: the evaluation pipeline's input preparation on the GPU (``IaaLetterbox(dim)`` when ``is_letterbox`` else
     ``iaa.Scale(dim)``, then ``ToTensor``: `utils.letterbox_batch(variant="eval" | "scale")`), eval-mode detection (conf 0.005 / nms
-    0.45) and the writer.  ``dim`` = (w, h).  Returns the number of result entries written."""
+    0.45) and the writer.  ``dim`` = (w, h).  Returns the number of result entries written.
+
+    ``decode="gpu"``: each batch's files are decoded by `jpeg.decode_batch` instead of `read_image_rgb` in this thread -- the same
+    pixels (files the GPU decoder does not take still go through `read_image_rgb`), so the same file."""
     from .utils import letterbox_batch
+    if decode not in ("pil", "gpu"):
+        raise ValueError("decode must be 'pil' or 'gpu'")
     if isinstance(target_txt, str):
         with open(target_txt, 'r') as f:
             items = [line.strip() for line in f.readlines() if line.strip()]
@@ -260,7 +265,12 @@ def generate_results_file(net, target_txt, classes_names, out, bs, dim, is_lette
         for i in range(0, len(items), bs):
             chunk = items[i:i + bs]
             paths = [c if isinstance(c, str) else c[0] for c in chunk]
-            imgs = [read_image_rgb(c) if isinstance(c, str) else c[1] for c in chunk]
+            if decode == "gpu":
+                from . import jpeg
+                files = iter(jpeg.decode_batch([c for c in chunk if isinstance(c, str)]))
+                imgs = [next(files) if isinstance(c, str) else c[1] for c in chunk]
+            else:
+                imgs = [read_image_rgb(c) if isinstance(c, str) else c[1] for c in chunk]
             x, _ = letterbox_batch(imgs, dim, variant="eval" if is_letterbox else "scale")
             yield {"img": x, "org_img": imgs, "img_path": paths}       # (the writer needs only the ORIGINAL sizes: HWC arrays)
 

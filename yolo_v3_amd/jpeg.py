@@ -1,0 +1,272 @@
+"""Baseline JPEG decode on the GPU, bit for bit with PIL (libjpeg-turbo's defaults): ``csrc/jpeg_parse.cpp`` reads the headers on
+the host, ``csrc/jpeg.hip`` decodes a batch of files in four launches.
+
+``decode_batch(sources)`` returns what ``evaluate.read_image_rgb`` returns for every source, as GPU tensors.  A file the parser
+does not positively recognise (progressive, arithmetic, CMYK, 4:4:0 / 4:1:1, 12-bit, multi-scan, ... or no JPEG at all), a file
+whose EXIF orientation is not 1, a file whose entropy-coded data the device reports as damaged and a file that ends without its
+EOI marker are decoded by ``read_image_rgb`` itself -- same pixels, same exceptions.  Nothing here is a default anywhere:
+``TrainBatches(decode="gpu")`` and ``generate_results_file(decode="gpu")`` opt in.
+"""
+import ctypes
+import io
+import os
+
+import numpy as np
+import torch
+
+from . import _ffi
+
+_ALIGN = 256
+_INFO_BYTES = ctypes.sizeof(_ffi.JpegInfo)
+
+counters = {"calls": 0, "uploads": 0, "upload_bytes": 0, "status_reads": 0, "fallbacks": 0}     # for measurements and tests
+
+
+def _round_up(n, a=_ALIGN):
+    return (n + a - 1) // a * a
+
+
+def read_bytes(source):
+    """The bytes of a source: a path is read, ``bytes`` / ``bytearray`` / ``memoryview`` are taken as they are."""
+    if isinstance(source, (bytes, bytearray, memoryview)):
+        return bytes(source)
+    with open(os.fspath(source), "rb") as f:
+        return f.read()
+
+
+def parse(data):
+    """``yv3_jpeg_parse`` of ``data``: the ``_ffi.JpegInfo`` record (``reason`` 0 = a file the GPU decoder takes)."""
+    info = _ffi.JpegInfo()
+    _ffi.check(_ffi.lib().yv3_jpeg_parse(data, len(data), ctypes.byref(info)), "yv3_jpeg_parse")
+    return info
+
+
+def _pil(source, data):
+    """`evaluate.read_image_rgb` of the source: of the path itself when there is one (same errors, same messages)."""
+    from . import evaluate
+    counters["fallbacks"] += 1
+    if isinstance(source, (bytes, bytearray, memoryview)):
+        return evaluate.read_image_rgb(io.BytesIO(data))
+    return evaluate.read_image_rgb(source)
+
+
+def _orientation(data):
+    """The EXIF orientation, from PIL's header parse only (no pixel is decoded); 1 when PIL cannot tell."""
+    from PIL import Image
+    try:
+        with Image.open(io.BytesIO(data)) as im:
+            return int(im.getexif().get(0x0112, 1))
+    except Exception:
+        return 1
+
+
+class Source:
+    """One source ahead of the GPU: its bytes, its parsed record and, when it cannot go to the GPU decoder, either its pixels
+    from `read_image_rgb` (``pixels``) or the exception that raised (``error``).  Built on any thread (`TrainBatches`' workers)."""
+    __slots__ = ("source", "data", "info", "pixels", "error", "shape", "unterminated")
+
+    def __init__(self, source):
+        self.source, self.pixels, self.error = source, None, None
+        self.data = read_bytes(source)
+        self.info = parse(self.data)
+        f = self.info
+        gpu = f.reason == 0 and not (f.has_exif and _orientation(self.data) != 1)
+        # a scan that runs to the end of the file has no EOI: PIL raises on such a file, whatever the device makes of its bits
+        self.unterminated = gpu and f.scan_offset + f.scan_length >= len(self.data)
+        if gpu:
+            self.shape = (int(f.height), int(f.width))
+        else:
+            try:
+                self.pixels = _pil(source, self.data)
+                self.shape = tuple(self.pixels.shape[:2])
+            except Exception as e:                          # raised where the image is used, as read_image_rgb would there
+                self.error, self.shape = e, (0, 0)
+
+    @property
+    def on_gpu(self):
+        return self.pixels is None and self.error is None
+
+    @property
+    def nbytes(self):
+        return self.shape[0] * self.shape[1] * 3
+
+
+class Decoded(list):
+    """`decode_batch`'s result: a list of uint8 ``[H,W,3]`` GPU tensors.  ``fallback[i]``: image i took the PIL path;
+    ``reasons[i]``: ``("parser", reason)``, ``("exif", None)``, ``("device", status)``, ``("truncated", None)`` or None."""
+    fallback = ()
+    reasons = ()
+
+
+class Job:
+    """A decode in flight on ``stream``, with an event recorded right after its own work.  `finish` waits for that event on the
+    host, reads the statuses once, routes damaged files through PIL and makes the current stream wait for the event too."""
+
+    def __init__(self, items, views, reasons, status_host, event, stream, keep):
+        self.items, self.views, self.reasons = items, views, reasons
+        self._status_host, self._event, self._stream, self._keep = status_host, event, stream, keep
+        self._finished = False
+
+    def finish(self, errors="raise"):
+        if not self._finished:
+            self._finished = True
+            self._event.synchronize()                        # this job's own kernels, not whatever the stream got after them
+            redo = False
+            if self._status_host is not None:
+                counters["status_reads"] += 1
+                status = self._status_host.numpy()
+                k = 0
+                for i, it in enumerate(self.items):
+                    if not it.on_gpu:
+                        continue
+                    st = int(status[k])
+                    k += 1
+                    if st == 0 and not it.unterminated:
+                        continue
+                    self.reasons[i] = ("device", st) if st else ("truncated", None)
+                    try:
+                        px = _pil(it.source, it.data)
+                    except Exception as e:
+                        it.error = e
+                        continue
+                    t = torch.from_numpy(px)
+                    with torch.cuda.stream(self._stream):
+                        if tuple(px.shape) == tuple(self.views[i].shape):
+                            self.views[i].copy_(t)           # into the slot the device left unspecified
+                        else:
+                            self.views[i] = t.to(self.views[i].device)
+                    redo = True
+            if redo:                                         # the copies above: a fresh event after them
+                self._event = torch.cuda.Event()
+                self._event.record(self._stream)
+        out = Decoded()
+        for i, it in enumerate(self.items):
+            if it.error is not None:
+                if errors == "raise":
+                    raise it.error
+                out.append(it.error)
+            else:
+                out.append(self.views[i])
+        out.fallback = [r is not None for r in self.reasons]
+        out.reasons = list(self.reasons)
+        cur = torch.cuda.current_stream(self._keep[0].device)
+        if cur != self._stream:
+            cur.wait_event(self._event)                      # the consumer waits for this job alone: a later job's decode on the
+            for t in self._keep:                             # same stream (the next batch's) keeps running beside the consumer
+                t.record_stream(cur)
+        return out
+
+
+def submit(sources, device=None, stream=None, dst=None):
+    """Enqueue the decode of ``sources`` (paths, ``bytes`` or prepared `Source` objects) on ``stream`` (default: the current one)
+    and return the `Job`.  One device allocation holds, in this order, the upload -- records, offsets, the files' bytes and the
+    pixels of the images PIL already decoded -- and the images the kernels write, each at a 256-aligned offset; it is filled by
+    ONE host-to-device copy.  ``dst = (tensor, offsets)``: image i is decoded into the uint8 1-D ``tensor`` (`TrainBatches`'
+    arena) at ``offsets[i]`` instead, for every i (None entries are not allowed: split the batch)."""
+    if not torch.cuda.is_available():
+        raise _ffi.Yv3Error("no GPU available: this package has no CPU path")
+    dev = torch.device(device if device is not None else "cuda")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    items = [s if isinstance(s, Source) else Source(s) for s in sources]
+    stream = stream if stream is not None else torch.cuda.current_stream(dev)
+    counters["calls"] += 1
+    lib = _ffi.lib()
+    gpu = [i for i, it in enumerate(items) if it.on_gpu]
+    host_px = [i for i, it in enumerate(items) if it.pixels is not None]
+    B = len(gpu)
+    reasons = [None] * len(items)
+    for i, it in enumerate(items):
+        if not it.on_gpu:
+            reasons[i] = ("parser", int(it.info.reason)) if it.info.reason else ("exif", None)
+
+    # layout of the allocation: infos | src offsets | dst offsets | status | file bytes | PIL pixels || decoded images
+    o_info = 0
+    o_soff = _round_up(o_info + B * _INFO_BYTES)
+    o_doff = _round_up(o_soff + B * 8)
+    o_stat = _round_up(o_doff + B * 8)
+    o_src = _round_up(o_stat + B * 4)
+    src_off, pos = [], o_src
+    for i in gpu:
+        src_off.append(pos - o_src)
+        pos += len(items[i].data)                           # files are packed back to back: any byte offset will do
+    src_bytes = max(pos - o_src, 1)
+    pos = _round_up(pos)
+    px_off = {}
+    for i in host_px:
+        if dst is None:
+            px_off[i] = pos
+            pos = _round_up(pos + items[i].nbytes)
+    upload = pos
+    own_off = {}
+    if dst is None:
+        for i in gpu:
+            own_off[i] = pos
+            pos = _round_up(pos + items[i].nbytes)
+    total = max(pos, 1)
+
+    with torch.cuda.device(dev), torch.cuda.stream(stream):
+        buf = torch.empty(total, dtype=torch.uint8, device=dev)
+        staging = torch.empty(max(upload, 1), dtype=torch.uint8, pin_memory=True)
+        host = staging.numpy()
+        infos = (_ffi.JpegInfo * max(B, 1))()
+        for k, i in enumerate(gpu):
+            infos[k] = items[i].info
+            d = items[i].data
+            host[o_src + src_off[k]:o_src + src_off[k] + len(d)] = np.frombuffer(d, dtype=np.uint8)
+        if B:
+            host[o_info:o_info + B * _INFO_BYTES] = np.frombuffer(infos, dtype=np.uint8, count=B * _INFO_BYTES)
+            host[o_soff:o_soff + B * 8].view(np.int64)[:] = src_off
+        if dst is None:
+            dst_t, dst_off = buf, [own_off[i] for i in gpu]
+            views = [None] * len(items)
+            for i, it in enumerate(items):
+                if it.error is None:
+                    off = own_off[i] if it.on_gpu else px_off[i]
+                    views[i] = buf[off:off + it.nbytes].view(it.shape[0], it.shape[1], 3)
+            for i in host_px:
+                host[px_off[i]:px_off[i] + items[i].nbytes] = items[i].pixels.reshape(-1)
+        else:
+            dst_t, offsets = dst
+            if dst_t.dtype != torch.uint8 or dst_t.dim() != 1 or not dst_t.is_contiguous() or dst_t.device != dev:
+                raise _ffi.Yv3Error("dst must be a contiguous 1-D uint8 tensor on the decoding device")
+            if len(offsets) != len(items) or any(o is None or o < 0 or o + it.nbytes > dst_t.numel() for o, it in zip(offsets, items)):
+                raise _ffi.Yv3Error("dst offsets: one in-range offset per image")
+            dst_off = [int(offsets[i]) for i in gpu]
+            views = [None if it.error is not None else dst_t[int(o):int(o) + it.nbytes].view(it.shape[0], it.shape[1], 3)
+                     for o, it in zip(offsets, items)]
+        if B:
+            host[o_doff:o_doff + B * 8].view(np.int64)[:] = dst_off
+        if upload:
+            buf[:upload].copy_(staging[:upload], non_blocking=True)
+            counters["uploads"] += 1
+            counters["upload_bytes"] += upload
+        if dst is not None:
+            for i in host_px:                               # PIL's pixels of a refused file go to the arena by a copy of their own
+                views[i].copy_(torch.from_numpy(items[i].pixels), non_blocking=False)
+        keep = [buf]
+        status_host = None
+        if B:
+            ws_bytes = lib.yv3_jpeg_workspace_bytes(ctypes.addressof(infos), B)
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+            base = buf.data_ptr()
+            desc = _ffi.JpegBatchDesc(src=base + o_src, src_bytes=src_bytes, src_offsets=base + o_soff, infos=base + o_info,
+                                      infos_host=ctypes.addressof(infos), dst=dst_t.data_ptr(), dst_bytes=dst_t.numel(),
+                                      dst_offsets=base + o_doff, status=base + o_stat, B=B)
+            _ffi.check(lib.yv3_jpeg_decode_batch(ctypes.byref(desc), ws.data_ptr(), ws.numel(), stream.cuda_stream),
+                       "yv3_jpeg_decode_batch")
+            status_host = torch.empty(B, dtype=torch.int32, pin_memory=True)
+            status_host.copy_(buf[o_stat:o_stat + B * 4].view(torch.int32), non_blocking=True)
+        event = torch.cuda.Event()                          # after this job's upload, kernels and status copy, and nothing else
+        event.record(stream)
+    return Job(items, views, reasons, status_host, event, stream, keep)
+
+
+def decode_batch(sources, device=None, errors="raise"):
+    """uint8 RGB ``[H,W,3]`` GPU tensors of ``sources`` (paths or ``bytes``), each what `evaluate.read_image_rgb` returns for it,
+    as views into one allocation at 256-aligned offsets: a `Decoded` list whose ``fallback`` says which images took the PIL path.
+    One upload (records + file bytes) and one status read per call.  ``errors="raise"`` (default): an image PIL cannot read
+    raises what `read_image_rgb` raises; ``"keep"``: the exception takes the image's place in the list."""
+    if errors not in ("raise", "keep"):
+        raise ValueError("errors must be 'raise' or 'keep'")
+    return submit(sources, device=device).finish(errors)
