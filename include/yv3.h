@@ -696,8 +696,9 @@ int yv3_train_bias_bwd_bf16(const float* dlogits, const float* scale, void* dout
  * Baseline JPEG decode (csrc/jpeg_parse.cpp, csrc/jpeg_entropy.h, csrc/jpeg.hip): file bytes -> uint8 RGB [H][W][3], the bits
  * libjpeg(-turbo)'s defaults give (integer "islow" IDCT, "fancy" chroma upsampling, fixed-point YCbCr -> RGB), for a batch of
  * files in four launches.  The host parser accepts only what it positively recognises; every other file gets a reason and is
- * the caller's to decode elsewhere (yolo_v3_amd.jpeg falls back to PIL).  Errors in the entropy-coded data are found on the
- * device and reported per image in status[]; such an image's destination bytes are unspecified (inside its own extent).
+ * the caller's to decode elsewhere (yolo_v3_amd.jpeg falls back to PIL).  Errors in the entropy-coded data, and coefficients
+ * no 8-bit encoder writes, are found on the device and reported per image in status[]; such an image's destination bytes are
+ * unspecified (inside its own extent).  Status 0 means libjpeg's bytes.
  * ------------------------------------------------------------------------------------------ */
 
 /* yv3_jpeg_info.reason: why yv3_jpeg_parse refuses a file (0 = accepted) */
@@ -724,6 +725,10 @@ int yv3_train_bias_bwd_bf16(const float* dlogits, const float* scale, void* dout
 #define YV3_JPEG_S_MARKER      7   /* restart markers: wrong count or order, or a marker inside a unit          */
 #define YV3_JPEG_S_EXTRA       8   /* whole bytes left over at the end of a unit                                */
 #define YV3_JPEG_S_DC          9   /* a DC value outside 16 bits                                                */
+#define YV3_JPEG_S_RANGE       10  /* a block outside the range in which every libjpeg IDCT gives the same bytes: a dequantised
+                                      coefficient or a column-pass output outside +-16383, or a sample outside [-512, 511]
+                                      before the +128 (no 8-bit encoder writes such a block; libjpeg's 16-bit SIMD words and its
+                                      masked range-limit index then wrap, each build its own way)                 */
 
 typedef struct yv3_jpeg_info {
     long long scan_offset;            /* first entropy-coded byte, from the start of the file                                  */

@@ -47,8 +47,9 @@ static int host_decode(const unsigned char* data, size_t n, yv3_jpeg_info* info,
     for (int c = 0; c < g.ncomp; ++c)
         for (int by = 0; by < g.bh[c]; ++by)
             for (int bx = 0; bx < g.bw[c]; ++bx)
-                yv3_jpeg_idct_block(coef.data() + ((size_t)g.base[c] + (size_t)by * g.bw[c] + bx) * 64, info->quant[info->tq[c]],
-                                    planes.data() + (size_t)g.base[c] * 64 + ((size_t)by * 8 * g.bw[c] + bx) * 8, g.bw[c] * 8);
+                if (yv3_jpeg_idct_block(coef.data() + ((size_t)g.base[c] + (size_t)by * g.bw[c] + bx) * 64, yv3_jpeg_quant_of(info, c),
+                                        planes.data() + (size_t)g.base[c] * 64 + ((size_t)by * 8 * g.bw[c] + bx) * 8, g.bw[c] * 8))
+                    return YV3_JPEG_S_RANGE;
     rgb->resize((size_t)info->width * info->height * 3);
     for (int y = 0; y < info->height; ++y)
         for (int x = 0; x < info->width; ++x) {

@@ -95,7 +95,7 @@ class YoloLossDesc(ctypes.Structure):
 JPEG_OK, JPEG_NOT_JPEG, JPEG_MALFORMED, JPEG_PROGRESSIVE, JPEG_SOF, JPEG_PRECISION, JPEG_COMPONENTS = range(7)
 JPEG_COLORSPACE, JPEG_SAMPLING, JPEG_MULTISCAN, JPEG_TABLES, JPEG_SIZE = range(7, 12)
 (JPEG_S_INFO, JPEG_S_BOUNDS, JPEG_S_HUFFTABLE, JPEG_S_CODE, JPEG_S_OVERRUN, JPEG_S_COEF, JPEG_S_MARKER, JPEG_S_EXTRA,
- JPEG_S_DC) = range(1, 10)
+ JPEG_S_DC, JPEG_S_RANGE) = range(1, 11)
 
 
 class JpegInfo(ctypes.Structure):

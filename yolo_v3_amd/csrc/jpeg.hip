@@ -7,7 +7,9 @@
 //                    footprint that would keep other images' workgroups off the CU), all lanes zero the image's coefficients and
 //                    find its restart markers, then one lane decodes each restart segment (jpeg_entropy.h; a file without DRI
 //                    is one segment, one lane): the parallelism is the many images in flight
-//   idct_kernel      one lane per 8x8 block: dequantise, jidctint's two passes, +128, clamp -> the component's uint8 plane
+//   idct_kernel      one lane per 8x8 block: dequantise, jidctint's two passes, +128, clamp -> the component's uint8 plane; a block
+//                    outside the range in which every libjpeg build computes the same bytes (jpeg_pixel.h) raises the image's
+//                    status to YV3_JPEG_S_RANGE
 //   colour_kernel    one lane per 4 output pixels: fancy upsampling of the chroma planes (h2v1 / h2v2), YCbCr -> RGB, 12 bytes
 //                    as three dword stores where the destination allows it
 // An image whose status is not 0 after any stage is skipped by the later ones: its destination bytes are not written.
@@ -141,21 +143,25 @@ __global__ __launch_bounds__(256) void entropy_kernel(const unsigned char* __res
     if (t == 0) { slots[b].status = s_status; status[b] = s_status; }
 }
 
-__global__ __launch_bounds__(256) void idct_kernel(const yv3_jpeg_info* __restrict__ infos, const yv3_jpeg_slot* __restrict__ slots,
-                                                   unsigned char* __restrict__ ws) {
+__global__ __launch_bounds__(256) void idct_kernel(const yv3_jpeg_info* __restrict__ infos, yv3_jpeg_slot* slots,
+                                                   unsigned char* __restrict__ ws, int* __restrict__ status) {
     __shared__ yv3_jpeg_geom g;
     __shared__ unsigned char quant[3][64];
     const int b = blockIdx.y, t = threadIdx.x;
-    const yv3_jpeg_slot slot = slots[b];
-    if (slot.status) return;
     const yv3_jpeg_info* f = infos + b;
     __shared__ int s_geom;
-    if (t == 0) s_geom = yv3_jpeg_geometry(f, &g);         // status 0: layout_kernel accepted this record
-    if (t < 192) quant[t >> 6][t & 63] = f->quant[f->tq[t >> 6] & 3][t & 63];
+    // Other workgroups of this image may raise its status while this one starts, so ONE lane reads it for the whole workgroup:
+    // lanes that read it themselves could disagree, and some would leave before the barrier that publishes g.
+    if (t == 0) {
+        const int st = __hip_atomic_load(&slots[b].status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_geom = st ? st : yv3_jpeg_geometry(f, &g);       // status 0: layout_kernel accepted this record
+    }
+    if (t < 192) quant[t >> 6][t & 63] = yv3_jpeg_quant_of(f, t >> 6)[t & 63];      // (inside the record whatever its bytes are)
+    const long long coef_off = slots[b].coef_off, plane_off = slots[b].plane_off;   // layout_kernel's, never written after it
     __syncthreads();
     if (s_geom) return;
-    const short* coef = (const short*)(ws + slot.coef_off);
-    unsigned char* planes = ws + slot.plane_off;
+    const short* coef = (const short*)(ws + coef_off);
+    unsigned char* planes = ws + plane_off;
     for (int blk = blockIdx.x * 256 + t; blk < g.nblocks; blk += gridDim.x * 256) {
         const int c = (g.ncomp == 3 && blk >= g.base[2]) ? 2 : (g.ncomp == 3 && blk >= g.base[1]) ? 1 : 0;
         const int local = blk - g.base[c];
@@ -165,7 +171,11 @@ __global__ __launch_bounds__(256) void idct_kernel(const yv3_jpeg_info* __restri
 #pragma unroll
         for (int i = 0; i < 8; ++i) in.v[i] = p[i];
         union { uint2 v[8]; unsigned char s[64]; } out;
-        yv3_jpeg_idct_block(in.s, quant[c], out.s, 8);
+        if (yv3_jpeg_idct_block(in.s, quant[c], out.s, 8)) {
+            // the image is dropped: colour_kernel skips it, and workgroups of this kernel that see the status early may return
+            atomicMax(&slots[b].status, YV3_JPEG_S_RANGE);
+            atomicMax(&status[b], YV3_JPEG_S_RANGE);
+        }
         const long long pitch = (long long)g.bw[c] * 8;
         unsigned char* o = planes + (long long)g.base[c] * 64 + (long long)by * 8 * pitch + (long long)bx * 8;
 #pragma unroll
@@ -241,7 +251,7 @@ extern "C" int yv3_jpeg_decode_batch(const yv3_jpeg_batch_desc* desc, void* ws, 
     hipLaunchKernelGGL(entropy_kernel, dim3(B), dim3(256), 0, s, desc->src, desc->src_offsets, desc->infos, slots, wsb, desc->status);
     YV3_CHECK_LAUNCH();
     const int gx_idct = (int)(max_blocks / 256 + 1 < 4096 ? max_blocks / 256 + 1 : 4096);
-    hipLaunchKernelGGL(idct_kernel, dim3(gx_idct, B), dim3(256), 0, s, desc->infos, slots, wsb);
+    hipLaunchKernelGGL(idct_kernel, dim3(gx_idct, B), dim3(256), 0, s, desc->infos, slots, wsb, desc->status);
     YV3_CHECK_LAUNCH();
     const int gx_col = (int)(max_groups / 256 + 1 < 4096 ? max_groups / 256 + 1 : 4096);
     hipLaunchKernelGGL(colour_kernel, dim3(gx_col, B), dim3(256), 0, s, desc->infos, slots, (const unsigned char*)wsb, desc->dst,

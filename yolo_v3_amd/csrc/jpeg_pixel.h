@@ -44,19 +44,35 @@ YV3_HD void yv3_jpeg_idct_1d(const int* d, int shift, int* o) {
     o[3] = (int)(tmp13 + tmp0 + rnd) >> shift; o[4] = (int)(tmp13 - tmp0 + rnd) >> shift;
 }
 
-// coef[64] int16 (natural order) * quant[64] -> out: 8 rows of 8 samples, `stride` bytes apart.  Coefficients of a valid
-// 8-bit file keep every intermediate far inside 32 bits; damaged ones may wrap (unsigned arithmetic where a shift could
-// overflow), which gives other pixels, never an access outside the block.
-YV3_HD void yv3_jpeg_idct_block(const short* coef, const unsigned char* quant, unsigned char* out, long long stride) {
+// The range in which every libjpeg IDCT gives the same bytes.  libjpeg-turbo's SIMD jidctint keeps the dequantised
+// coefficients and the column pass's outputs in 16-bit words and adds pairs of them as words; the C jidctint masks its
+// range-limit index to 10 bits.  Outside these bounds each build wraps its own way; inside them all agree with 32-bit
+// arithmetic and a clamp.  Blocks of real 8-bit samples stay far inside (coefficients within 1024, column pass within
+// 6000, samples within 400 of the level shift), so only damaged or hand-made data is refused.
+#define YV3_JPEG_WORD_LIMIT 16383          // |dequantised coefficient|, |column-pass output|: the sum of two fits a word
+#define YV3_JPEG_SAMPLE_MIN (-512)         // row-pass output before the +128
+#define YV3_JPEG_SAMPLE_MAX 511
+
+// 1 when v lies outside [-YV3_JPEG_WORD_LIMIT, YV3_JPEG_WORD_LIMIT]
+YV3_HD unsigned yv3_jpeg_off_word(int v) { return (unsigned)v + YV3_JPEG_WORD_LIMIT > 2u * YV3_JPEG_WORD_LIMIT; }
+
+// The quantiser table of component c (the same selection for the kernel and the host program)
+YV3_HD const unsigned char* yv3_jpeg_quant_of(const yv3_jpeg_info* f, int c) { return f->quant[f->tq[c] & 3]; }
+
+// coef[64] int16 (natural order) * quant[64] -> out: 8 rows of 8 samples, `stride` bytes apart.  Returns 0, or
+// YV3_JPEG_S_RANGE for a block outside the range above: its samples are then not libjpeg's and the image is not to be used.
+// (Unsigned arithmetic where a shift could overflow: such a block gives other samples, never an access outside the block.)
+YV3_HD int yv3_jpeg_idct_block(const short* coef, const unsigned char* quant, unsigned char* out, long long stride) {
     int ws[64];
+    unsigned off = 0;
     YV3_UNROLL
     for (int x = 0; x < 8; ++x) {
         int d[8], o[8];
         YV3_UNROLL
-        for (int y = 0; y < 8; ++y) d[y] = (int)coef[8 * y + x] * (int)quant[8 * y + x];
+        for (int y = 0; y < 8; ++y) { d[y] = (int)coef[8 * y + x] * (int)quant[8 * y + x]; off |= yv3_jpeg_off_word(d[y]); }
         yv3_jpeg_idct_1d(d, 11, o);
         YV3_UNROLL
-        for (int y = 0; y < 8; ++y) ws[8 * y + x] = o[y];
+        for (int y = 0; y < 8; ++y) { ws[8 * y + x] = o[y]; off |= yv3_jpeg_off_word(o[y]); }
     }
     YV3_UNROLL
     for (int y = 0; y < 8; ++y) {
@@ -64,10 +80,12 @@ YV3_HD void yv3_jpeg_idct_block(const short* coef, const unsigned char* quant, u
         yv3_jpeg_idct_1d(ws + 8 * y, 18, o);
         YV3_UNROLL
         for (int x = 0; x < 8; ++x) {
+            off |= (unsigned)(o[x] - YV3_JPEG_SAMPLE_MIN) > (unsigned)(YV3_JPEG_SAMPLE_MAX - YV3_JPEG_SAMPLE_MIN);
             const int s = o[x] + 128;                 // |o| < 2^14 after the shift by 18
             out[y * stride + x] = (unsigned char)(s < 0 ? 0 : s > 255 ? 255 : s);
         }
     }
+    return off ? YV3_JPEG_S_RANGE : 0;
 }
 
 // Chroma sample of output pixel (x, y) from plane p (row pitch `pitch`, true size cw x ch) under sampling hmax x vmax relative

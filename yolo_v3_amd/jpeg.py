@@ -3,8 +3,9 @@ the host, ``csrc/jpeg.hip`` decodes a batch of files in four launches (DESIGN.md
 
 ``decode_batch(sources)`` returns what ``evaluate.read_image_rgb`` returns for every source, as GPU tensors.  A file the parser
 does not positively recognise (progressive, arithmetic, CMYK, 4:4:0 / 4:1:1, 12-bit, multi-scan, ... or no JPEG at all), a file
-whose EXIF orientation is not 1, a file whose entropy-coded data the device reports as damaged and a file that ends without its
-EOI marker are decoded by ``read_image_rgb`` itself -- same pixels, same exceptions.  Nothing here is a default anywhere:
+whose EXIF orientation is not 1, a file whose entropy-coded data the device reports as damaged or as holding coefficients outside
+the range in which every libjpeg computes the same bytes (``JPEG_S_RANGE``) and a file that ends without its EOI marker are
+decoded by ``read_image_rgb`` itself -- same pixels, same exceptions.  Nothing here is a default anywhere:
 ``TrainBatches(decode="gpu")`` and ``generate_results_file(decode="gpu")`` opt in.
 """
 import ctypes
