@@ -59,6 +59,17 @@ extern "C" {
                                     a transformed operand rounded to 11 bits is another precision class), stream-K (workspace is
                                     ignored) and the four-wave 192x128 tile -- those are rules for two fp16 planes.                    */
 
+#define YV3_I8 6                 /* int8 NHWC tensors with one fp32 scale per tensor (x ~ s * q, q in [-127, 127]; -128 is never produced),
+                                    v_mfma_i32_32x32x32_i8, exact int32 accumulation (csrc/conv_planes_i8.hip).  One "plane"
+                                    [1][B,H,W,C] of bytes.  Weights are int8 per output channel with the input scale(s) folded in; the
+                                    epilogue is  t = fmaf((float)acc, alpha[co], beta[co]); v = max(t, 0.1 t) (YV3_ACT_LEAKY);
+                                    v = fmaf((float)q_res, s_res, v) with a residual; q = clip(rint(v * inv_s_out), -127, 127).
+                                    cin, cin_up and cin - cin_up must be multiples of 64, cout of 8.  out_dtype: YV3_I8, or YV3_BF16 --
+                                    the same integers q written as one bf16 plane (exact), what a YV3_BF16 head conv reads.  Tiles, main
+                                    loops and selection rules are YV3_BF16's, applied to the layer's BYTES (an int8 layer of C input
+                                    channels is a bf16 layer of C/2); no Winograd form, no stream-K, no k3s1 / w4 variants (those
+                                    options are ignored).  Batch slices (x / x2 / y_plane_stride) are YV3_ESHAPE.                        */
+
 #define YV3_ACT_LINEAR 0
 #define YV3_ACT_LEAKY  1         /* LeakyReLU(0.1), reference darknet.py:41 */
 
@@ -74,6 +85,8 @@ const char* yv3_error_string(int code);
  * YV3_F32: K-major [cout_pad][k][k][cin] fp32.  YV3_BF16 / YV3_F32_BF16X3: NP = 1 / 3 bf16 planes
  * pre-arranged tile by tile in the kernel's LDS image order; needs NP * cout_pad*k*k*cin * 2 bytes.  YV3_F32_F16X2 / YV3_F16: the same
  * image in 2 / 1 fp16 planes (round to nearest even).
+ * YV3_I8: w_oihw holds ALREADY QUANTISED integers in [-127, 127] as fp32 (the caller quantises); they are arranged as
+ * int8 in the same LDS image (64-byte rows = 64 K elements; cin a multiple of 64); needs cout_pad*k*k*cin bytes; k = 1 or 3.
  * k = 1 or 3; k = 4 (plane dtypes except YV3_F16, which has no Winograd form: YV3_ESHAPE): the 4x4 Winograd-domain filters U = G g G^T
  * of a 3x3 layer (yv3_conv_desc.w_wino). */
 int yv3_pack_conv_weight(const float* w_oihw, void* w_packed, int cout, int cin, int k,
@@ -90,6 +103,9 @@ int yv3_split_planes(const float* in, void* out, long long n, int np, void* stre
 int yv3_merge_planes(const void* in, float* out, long long n, int np, void* stream);
 /* The same for the one fp16 plane of YV3_F16 (np = 1 above is bf16): out[i] = fp16(in[i]), round to nearest even, subnormals kept,
  * saturated to +-65504 (infinities too; not reported: layout helper), NaN stays NaN; and back, exactly. */
+/* YV3_I8 boundary: one bf16 plane [n] -> int8 [n], q = clip(rint(x * inv_s), -127, 127) (ties to even; NaN -> 0), inv_s = 1.0f / s
+ * computed by the caller.  n a multiple of 8, both pointers 16- / 8-byte aligned. */
+int yv3_quantize_bf16_i8(const void* in, void* out, long long n, float inv_s, void* stream);
 int yv3_split_plane_f16(const float* in, void* out, long long n, void* stream);
 int yv3_merge_plane_f16(const void* in, float* out, long long n, void* stream);
 
@@ -179,8 +195,8 @@ typedef struct yv3_conv_desc {
     int cout, cout_pad;     /* real and padded (multiple of 32) output channels                */
     int k, stride;          /* k in {1,3}; pad = (k-1)/2 (darknet.py:34-35); stride in {1,2}   */
     int act;                /* YV3_ACT_*                                                       */
-    int dtype;              /* YV3_F32 / YV3_BF16 / YV3_F32_BF16X3 / YV3_F32_F16X2 / YV3_F16: format of x, x2, residual, w */
-    int out_dtype;          /* format of y: == dtype, or YV3_F32 (head convs write fp32 logits) */
+    int dtype;              /* YV3_F32 / YV3_BF16 / YV3_F32_BF16X3 / YV3_F32_F16X2 / YV3_F16 / YV3_I8: format of x, x2, residual, w */
+    int out_dtype;          /* format of y: == dtype, or YV3_F32 (head convs write fp32 logits); YV3_I8: or YV3_BF16 */
     int* flags;             /* optional device int32: bit 0 is OR-ed in when a YV3_F32_F16X2 or YV3_F16 output had to be
                                saturated (|value| > 65504), i.e. fp16 cannot represent this
                                layer -- rerun in YV3_F32_BF16X3 or YV3_F32 (YV3_F16: YV3_BF16).  NULL: not reported.
@@ -251,6 +267,9 @@ typedef struct yv3_conv_desc {
        split depends on B: the same image is then summed in a different (fixed per shape) order at different batch sizes / positions;
        YV3_OPT_WINO4_TILES keeps one item per workgroup.  A hand-over that times out sets bit 1 of *flags. */
     const void*  w_wino4;
+    /* YV3_I8 only (ignored by every other dtype): the residual tensor's scale and 1.0f / (the output tensor's scale), computed once on the
+       host; alpha / beta hold the layer's per-channel multiplier m = sw * alpha_bn and shift b. */
+    float        s_res, inv_s_out;
 } yv3_conv_desc;
 
 #define YV3_OPT_NO_PINGPONG 1u    /* fp16-plane 8-wave tiles: single-phase main loop instead of the two-group ping-pong */

@@ -4,7 +4,8 @@ warm-up, timed with device events; prints the median and range of images/s per m
     python tools/mode_ab.py --modes BF16,F16 --size 416 --batch 64 --rounds 9 [--steps 8] [--warmup 3] [--accuracy]
 
 --accuracy adds, per mode, the relative L2 error of the three heads' logits against the fp32 oracle (CPU) on two images and the boxes
-line (oracle.boxdelta at IOU >= 0.5) of `detect` against the oracle's boxes."""
+line (oracle.boxdelta at IOU >= 0.5) of `detect` against the oracle's boxes.  I8 is calibrated on the timed batch before anything is timed
+(and, for --accuracy, on the two accuracy images)."""
 import argparse
 import json
 import os
@@ -19,7 +20,7 @@ if REPO not in sys.path:
 
 from yolo_v3_amd import _ffi, synth, Detector, YoloNet, WeightManager, detect          # noqa: E402
 
-MODES = {"F32": _ffi.F32, "BF16": _ffi.BF16, "F32X3": _ffi.F32X3, "F32H2": _ffi.F32H2, "F16": _ffi.F16}
+MODES = {"F32": _ffi.F32, "BF16": _ffi.BF16, "F32X3": _ffi.F32X3, "F32H2": _ffi.F32H2, "F16": _ffi.F16, "I8": _ffi.I8}
 
 
 def load_net(size):
@@ -48,6 +49,8 @@ def accuracy(net, stream, names):
         ref = oc.head_logits(sd, x)
         want = oc.postprocess(torch.cat(oc.yolonet_forward(sd, x), 1), 80, 0.5, 0.4)
     out, asked = {}, net.math_mode
+    if "I8" in names:
+        net.calibrate_int8([x.cuda()])
     for name in names:
         mode = MODES[name]
         with torch.no_grad():
@@ -79,6 +82,8 @@ def main():
     torch.cuda.set_device(0)
     net, stream = load_net(args.size)
     x = torch.from_numpy(synth.images(args.batch, args.size, 7)).cuda()
+    if "I8" in names:
+        net.calibrate_int8([x])
     dets = {n: Detector(net, args.batch, args.size, args.size, 0.5, 0.4, dtype=MODES[n], lanes=args.lanes) for n in names}
     with torch.no_grad():
         for n in names:

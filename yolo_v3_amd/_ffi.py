@@ -21,6 +21,7 @@ if os.environ.get("YV3_MEASURE") != "1":
 F32, BF16, F32X3, F32H2 = 0, 1, 2, 3
 BF16_ACT = 4          # net.backprop_math only: the BF16 training step with activations stored in bf16 only (backprop.py)
 F16 = 5               # YV3_F16: one fp16 plane on the BF16 kernels (inference only)
+I8 = 6                # YV3_I8: calibrated int8 activations and weights, int32 accumulation (inference only; needs net.int8_scales)
 ACT_LINEAR, ACT_LEAKY = 0, 1
 PP_EVAL, PP_PROB = 1, 2
 OPT_NO_PINGPONG, OPT_K3S1, OPT_WINO_EVEN, OPT_WINO_ALWAYS, OPT_TWO_LANES, OPT_WINO4_TILES = 1, 2, 4, 8, 16, 32
@@ -60,7 +61,7 @@ class ConvDesc(ctypes.Structure):
                 ("dec_anchors", c_float * 6), ("options", ctypes.c_uint), ("big_tile_min", c_int), ("tune", c_int * 4),
                 ("x_plane_stride", c_longlong), ("x2_plane_stride", c_longlong), ("y_plane_stride", c_longlong),
                 ("w_wino", c_void_p), ("alpha_wino", c_void_p), ("wino_ws", c_void_p), ("wino_ws_bytes", ctypes.c_size_t),
-                ("w_wino4", c_void_p)]
+                ("w_wino4", c_void_p), ("s_res", c_float), ("inv_s_out", c_float)]
 
 
 COCO_MAX_MAXDETS = 8
@@ -130,6 +131,7 @@ _SIGNATURES = {
     "yv3_split_planes": (c_int, [c_void_p, c_void_p, c_longlong, c_int, c_void_p]),
     "yv3_merge_planes": (c_int, [c_void_p, c_void_p, c_longlong, c_int, c_void_p]),
     "yv3_split_plane_f16": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p]),
+    "yv3_quantize_bf16_i8": (c_int, [c_void_p, c_void_p, c_longlong, c_float, c_void_p]),
     "yv3_merge_plane_f16": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p]),
     "yv3_conv0": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "yv3_conv_front": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -31,7 +31,7 @@ static int check_desc(const yv3_conv_desc* d, bool need_output = true) {
 }
 
 static int plane_count(int dtype) {
-    return dtype == YV3_BF16 || dtype == YV3_F16 ? 1 : dtype == YV3_F32_F16X2 ? 2 : dtype == YV3_F32_BF16X3 ? 3 : 0;
+    return dtype == YV3_BF16 || dtype == YV3_F16 || dtype == YV3_I8 ? 1 : dtype == YV3_F32_F16X2 ? 2 : dtype == YV3_F32_BF16X3 ? 3 : 0;
 }
 
 // The dtype / output-format errors of yv3_conv2d: ONE function, called by the launch and by the form query, so that
@@ -42,6 +42,7 @@ static int check_dtype(const yv3_conv_desc* d) {
         if (d->dec_out) return YV3_EDTYPE;                     // the fused decode lives in the plane kernels' epilogue
         return 0;
     }
+    if (d->dtype == YV3_I8) return (d->out_dtype == YV3_I8 || d->out_dtype == YV3_BF16) && !d->dec_out ? 0 : YV3_EDTYPE;   // (the quantised integers as int8, or as one bf16 plane)
     if (plane_count(d->dtype)) return d->out_dtype != YV3_F32 && d->out_dtype != d->dtype ? YV3_EDTYPE : 0;
     return YV3_EDTYPE;
 }
@@ -59,9 +60,10 @@ static int conv2d(const yv3_conv_desc* d, int what, hipStream_t s, char* buf = n
         const yv3_f32_choice c = yv3_select_f32(d, ncu);
         return c.rc ? c.rc : what == CONV_FORM ? c.form : what == CONV_LAUNCHES ? c.launches : what == CONV_KERNEL ? yv3_describe_f32(c, buf, buf_bytes) : yv3_conv2d_f32(d, c, s);
     }
-    const yv3_planes_choice c = yv3_select_planes(d, np, ncu);
+    const yv3_planes_choice c = d->dtype == YV3_I8 ? yv3_select_planes_i8(d, ncu) : yv3_select_planes(d, np, ncu);
     return c.rc ? c.rc : what == CONV_FORM ? c.form : what == CONV_LAUNCHES ? c.launches : what == CONV_KERNEL ? yv3_describe_planes(c, buf, buf_bytes) :
-           d->dtype == YV3_F16 ? yv3_conv2d_planes_f16(d, c, s) : yv3_conv2d_planes(d, np, c, s);      // (one plane either way: the element type picks the launcher)
+           d->dtype == YV3_F16 ? yv3_conv2d_planes_f16(d, c, s) : d->dtype == YV3_I8 ? yv3_conv2d_planes_i8(d, c, s) :
+           yv3_conv2d_planes(d, np, c, s);      // (one plane either way: the element type picks the launcher)
 }
 extern "C" int yv3_conv2d(const yv3_conv_desc* d, void* stream) { return conv2d(d, CONV_LAUNCH, (hipStream_t)stream); }
 extern "C" int yv3_conv2d_form(const yv3_conv_desc* d) { return conv2d(d, CONV_FORM, nullptr); }

@@ -31,6 +31,10 @@ struct ConvParamsP {
     // matrix starts xi * xi_stride elements into each plane of x; the epilogue maps tile rows back to pixels
     long long xi_stride;
     int wH, wW, wth, wtw;       // output height / width, tile grid
+    // YV3_I8 launches (conv_planes_i8.hip; Cin / Cup / K then count 16-bit units = byte pairs, Cout channels): the residual tensor's scale,
+    // 1 / the output tensor's scale, and whether the quantised integers are written as one bf16 plane instead of int8
+    float s_res, inv_s_out;
+    int out_bf16;
 };
 
 // (the stream-K workspace geometry YV3_SK_* and the Winograd stages' hand-over area YV3_WINO_SK_* are in conv_select.h: the selector counts with them)
@@ -72,7 +76,9 @@ typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
 // The plane count says how many planes a tensor has and which partial products run (mfma_unit).  The modes before YV3_F16 tie the two
 // together -- one or three bf16 planes, two fp16 planes: plane_elem, the default of every kernel's element parameter; YV3_F16 is one
 // plane of YV3_EL_F16 (conv_planes_f16.hip).
-enum { YV3_EL_BF16 = 0, YV3_EL_F16 = 1 };
+//   YV3_EL_I8  : two int8 per 16-bit unit, v_mfma_i32_32x32x32_i8 -- the same 16 bytes per lane and k-step at twice the K; the accumulator
+//                registers hold int32 bit patterns (zero is the same bits), the epilogue converts them (conv_planes_i8.hip)
+enum { YV3_EL_BF16 = 0, YV3_EL_F16 = 1, YV3_EL_I8 = 2 };
 constexpr int plane_elem(int np) { return np == 2 ? YV3_EL_F16 : YV3_EL_BF16; }
 template <int EL> struct ElemOps {
     static __device__ inline unsigned pack2(float lo, float hi) {
@@ -113,6 +119,21 @@ template <> struct ElemOps<YV3_EL_F16> {
     }
     static __device__ inline u16 cvt(float v) { return __builtin_bit_cast(unsigned short, sat(v)); }
     static __device__ inline float back(u16 h) { return (float)__builtin_bit_cast(_Float16, h); }
+};
+template <> struct ElemOps<YV3_EL_I8> {
+    typedef int i32x4v __attribute__((ext_vector_type(4)));
+    typedef int i32x16v __attribute__((ext_vector_type(16)));
+    static __device__ inline f32x16 mfma(bf16x8v a, bf16x8v b, f32x16 c) {
+        return __builtin_bit_cast(f32x16, __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4v, a), __builtin_bit_cast(i32x4v, b),
+                                                                                __builtin_bit_cast(i32x16v, c), 0, 0, 0));
+    }
+    // byte h of an 8-byte row piece as the integer it holds
+    static __device__ inline float elem(u32x2 q, int h) { return (float)(int)(signed char)((q[h >> 2] >> (8 * (h & 3))) & 0xffu); }
+    // q = clip(rint(v), -127, 127) (ties to even; -128 is never produced)
+    static __device__ inline float quant(float v) { return __builtin_amdgcn_fmed3f(__builtin_rintf(v), -127.f, 127.f); }
+    static __device__ inline unsigned pack4(float a, float b, float c, float d) {
+        return ((unsigned)(int)a & 0xffu) | (((unsigned)(int)b & 0xffu) << 8) | (((unsigned)(int)c & 0xffu) << 16) | ((unsigned)(int)d << 24);
+    }
 };
 template <int NP> using PlaneOps = ElemOps<plane_elem(NP)>;      // the element type the plane count implies
 
@@ -222,8 +243,13 @@ __device__ __forceinline__ void epilogue_store(f32x16 (&acc)[BN / WN / 32][BM / 
                     const long long px = rowpix(m0 + wm * WTM + jg * GR + ps * RPP + lane / LPR);
                     const int n = n0 + wn * WTN + (lane % LPR) * 8;
                     const long long o = (px >= 0 && n < p.Cout) ? px * p.Cout + n : 0;      // clamped, unused if out of range
+                    if constexpr (EL == YV3_EL_I8) {             // 8 channels of a row are 8 bytes
+                        const u32x2 r8 = *reinterpret_cast<const u32x2*>(reinterpret_cast<const unsigned char*>(p.res) + o);
+                        rres[ps][0] = u32x4{r8[0], r8[1], 0u, 0u};
+                    } else {
 #pragma unroll
-                    for (int pl = 0; pl < NP; ++pl) rres[ps][pl] = *reinterpret_cast<const u32x4*>(p.res + pl * p.ys + o);
+                        for (int pl = 0; pl < NP; ++pl) rres[ps][pl] = *reinterpret_cast<const u32x4*>(p.res + pl * p.ys + o);
+                    }
                 }
             }
         }
@@ -283,7 +309,9 @@ __device__ __forceinline__ void epilogue_store(f32x16 (&acc)[BN / WN / 32][BM / 
                     f32x4 v;
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        const float t = fmaf(acc[i][j][4 * g + q], alv[i][g][q], bev[i][g][q]);
+                        float a = acc[i][j][4 * g + q];
+                        if constexpr (EL == YV3_EL_I8) a = (float)__builtin_bit_cast(int, a);      // exact int32 sum -> fp32, round to nearest even
+                        const float t = fmaf(a, alv[i][g][q], bev[i][g][q]);
                         v[q] = __builtin_fmaxf(t, slope * t);
                     }
                     *reinterpret_cast<f32x4*>(tile + (jj * 32 + l31) * EP + nl) = v;
@@ -342,46 +370,65 @@ __device__ __forceinline__ void epilogue_store(f32x16 (&acc)[BN / WN / 32][BM / 
             const f32x4 v1 = *reinterpret_cast<const f32x4*>(tile + r * EP + cg + 4);
             float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
             const long long o = px * p.Cout + n;
-            if (p.res) {
+            if constexpr (EL == YV3_EL_I8) {
+                // v = fmaf(q_res, s_res, v); q = clip(rint(v * inv_s_out), -127, 127): 8 bytes per lane, or the same integers as 8 bf16
+                if (p.res) {
+                    const u32x2 r8 = {rres[ps][0][0], rres[ps][0][1]};
 #pragma unroll
-                for (int pl = 0; pl < NP; ++pl) {       // planes sum back to the exact fp32 value
+                    for (int h = 0; h < 8; ++h) v[h] = fmaf(ElemOps<EL>::elem(r8, h), p.s_res, v[h]);
+                }
+#pragma unroll
+                for (int h = 0; h < 8; ++h) v[h] = ElemOps<EL>::quant(v[h] * p.inv_s_out);
+                if (p.out_bf16) {
                     u32x4 q4;
-                    if constexpr (PRE) q4 = rres[ps][pl];
-                    else q4 = *reinterpret_cast<const u32x4*>(p.res + pl * p.ys + o);
 #pragma unroll
-                    for (int h = 0; h < 4; ++h) { v[2 * h] += ElemOps<EL>::lo(q4[h]); v[2 * h + 1] += ElemOps<EL>::hi(q4[h]); }
+                    for (int h = 0; h < 4; ++h) q4[h] = ElemOps<YV3_EL_BF16>::pack2(v[2 * h], v[2 * h + 1]);
+                    *reinterpret_cast<u32x4*>((u16*)p.y + o) = q4;
+                } else {
+                    *reinterpret_cast<u32x2*>((unsigned char*)p.y + o) = u32x2{ElemOps<EL>::pack4(v[0], v[1], v[2], v[3]), ElemOps<EL>::pack4(v[4], v[5], v[6], v[7])};
                 }
-            }
-            u16* yo = (u16*)p.y + o;
-            if constexpr (NP == 2) {
-#pragma unroll
-                for (int h = 0; h < 4; ++h) amax = __builtin_fmaxf(amax, __builtin_fmaxf(__builtin_fabsf(v[2 * h]), __builtin_fabsf(v[2 * h + 1])));
-                u32x4 qh, ql;
-#pragma unroll
-                for (int h = 0; h < 4; ++h) {
-                    v[2 * h] = __builtin_amdgcn_fmed3f(v[2 * h], -65504.f, 65504.f);           // saturate (and flag, below)
-                    v[2 * h + 1] = __builtin_amdgcn_fmed3f(v[2 * h + 1], -65504.f, 65504.f);
-                    qh[h] = PlaneOps<2>::pack2_nosat(v[2 * h], v[2 * h + 1]);
-                    ql[h] = PlaneOps<2>::pack2_nosat(v[2 * h] - PlaneOps<2>::lo(qh[h]), v[2 * h + 1] - PlaneOps<2>::hi(qh[h]));
-                }
-                if (!(YV3_IO_ABL(p) & 1)) {                  // (measurement builds only: IO ablation)
-                    *reinterpret_cast<u32x4*>(yo) = qh;
-                    *reinterpret_cast<u32x4*>(yo + p.ys) = ql;
-                } else { asm volatile("" :: "v"(qh), "v"(ql)); }
             } else {
-                if constexpr (EL == YV3_EL_F16) {          // one fp16 plane: pack2 saturates, the flag follows below
+                if (p.res) {
+#pragma unroll
+                    for (int pl = 0; pl < NP; ++pl) {       // planes sum back to the exact fp32 value
+                        u32x4 q4;
+                        if constexpr (PRE) q4 = rres[ps][pl];
+                        else q4 = *reinterpret_cast<const u32x4*>(p.res + pl * p.ys + o);
+#pragma unroll
+                        for (int h = 0; h < 4; ++h) { v[2 * h] += ElemOps<EL>::lo(q4[h]); v[2 * h + 1] += ElemOps<EL>::hi(q4[h]); }
+                    }
+                }
+                u16* yo = (u16*)p.y + o;
+                if constexpr (NP == 2) {
 #pragma unroll
                     for (int h = 0; h < 4; ++h) amax = __builtin_fmaxf(amax, __builtin_fmaxf(__builtin_fabsf(v[2 * h]), __builtin_fabsf(v[2 * h + 1])));
-                }
-#pragma unroll
-                for (int pl = 0; pl < NP; ++pl) {
-                    u32x4 q4;
+                    u32x4 qh, ql;
 #pragma unroll
                     for (int h = 0; h < 4; ++h) {
-                        q4[h] = ElemOps<EL>::pack2(v[2 * h], v[2 * h + 1]);
-                        v[2 * h] -= ElemOps<EL>::lo(q4[h]); v[2 * h + 1] -= ElemOps<EL>::hi(q4[h]);
+                        v[2 * h] = __builtin_amdgcn_fmed3f(v[2 * h], -65504.f, 65504.f);           // saturate (and flag, below)
+                        v[2 * h + 1] = __builtin_amdgcn_fmed3f(v[2 * h + 1], -65504.f, 65504.f);
+                        qh[h] = PlaneOps<2>::pack2_nosat(v[2 * h], v[2 * h + 1]);
+                        ql[h] = PlaneOps<2>::pack2_nosat(v[2 * h] - PlaneOps<2>::lo(qh[h]), v[2 * h + 1] - PlaneOps<2>::hi(qh[h]));
                     }
-                    *reinterpret_cast<u32x4*>(yo + pl * p.ys) = q4;
+                    if (!(YV3_IO_ABL(p) & 1)) {                  // (measurement builds only: IO ablation)
+                        *reinterpret_cast<u32x4*>(yo) = qh;
+                        *reinterpret_cast<u32x4*>(yo + p.ys) = ql;
+                    } else { asm volatile("" :: "v"(qh), "v"(ql)); }
+                } else {
+                    if constexpr (EL == YV3_EL_F16) {          // one fp16 plane: pack2 saturates, the flag follows below
+#pragma unroll
+                        for (int h = 0; h < 4; ++h) amax = __builtin_fmaxf(amax, __builtin_fmaxf(__builtin_fabsf(v[2 * h]), __builtin_fabsf(v[2 * h + 1])));
+                    }
+#pragma unroll
+                    for (int pl = 0; pl < NP; ++pl) {
+                        u32x4 q4;
+#pragma unroll
+                        for (int h = 0; h < 4; ++h) {
+                            q4[h] = ElemOps<EL>::pack2(v[2 * h], v[2 * h + 1]);
+                            v[2 * h] -= ElemOps<EL>::lo(q4[h]); v[2 * h + 1] -= ElemOps<EL>::hi(q4[h]);
+                        }
+                        *reinterpret_cast<u32x4*>(yo + pl * p.ys) = q4;
+                    }
                 }
             }
         }

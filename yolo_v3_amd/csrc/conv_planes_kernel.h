@@ -23,7 +23,7 @@
 //
 // This header holds the kernel, its launcher and the weight / layout kernels as templates over the plane count NP and the element type EL
 // (conv_planes_common.h); conv_planes.hip instantiates them for the bf16 planes and the fp16 hi+lo planes, conv_planes_f16.hip for one
-// fp16 plane (YV3_F16).
+// fp16 plane (YV3_F16), conv_planes_i8.hip for int8 (YV3_I8: two elements per 16-bit unit, v_mfma_i32_32x32x32_i8, a quantising epilogue).
 #pragma once
 #include <stdlib.h>
 #include <type_traits>
@@ -796,7 +796,8 @@ int launch_cfg(const ConvParamsP& p, bool k3, bool dual, bool out_f32, const yv3
     hipLaunchKernelGGL((conv_planes_kernel<NP, BM, BN, WM, WN, NSTAGE, K3_, DUAL_, OF_, false, false, MINW, MTG, false, ROLL, EL>), grid, block, lds, s, q); } while (0)
     if (out_f32) {
         if (k3 || dual) return YV3_ESHAPE;                   // fp32 outputs are the 1x1 head convs
-        YV3_LAUNCH(false, false, true);
+        if constexpr (EL == YV3_EL_I8) return YV3_EDTYPE;    // (int8 layers write int8 or bf16; the head convs are YV3_BF16 launches)
+        else YV3_LAUNCH(false, false, true);
     } else if (k3) YV3_LAUNCH(true, false, false);
     else if (dual) YV3_LAUNCH(false, true, false);
     else YV3_LAUNCH(false, false, false);
@@ -890,6 +891,7 @@ inline ConvParamsP conv_planes_params(const yv3_conv_desc* d, const yv3_planes_c
     if (d->y_plane_stride > 0) p.ys = d->y_plane_stride;
     p.tb = d->cout_pad < 128 ? d->cout_pad : 128;
     p.ntiles = c.ntiles;
+    p.s_res = 0.f; p.inv_s_out = 0.f; p.out_bf16 = 0;               // (YV3_I8 launches set them: conv_planes_i8.hip)
     return p;
 }
 

@@ -237,6 +237,23 @@ yv3_planes_choice yv3_select_planes(const yv3_conv_desc* d, int np, int ncu_) {
     return pick(YV3_PK_128x32, npad / 32);      // (fp16 planes: +6 % on the 208x208 1x1 layer with the 2-deep ring)
 }
 
+// YV3_I8 (conv_planes_i8.hip).  An int8 K chunk is 64 elements = the 64-byte row of a 32-element bf16 chunk, so every count the rules
+// above make (K chunks, tiles, rounds of the chip) is that of the bf16 layer with half the input channels: the same rules decide.  Left out of
+// the descriptor they see: the opt-in k3s1 kernel, the Winograd operands and the stream-K workspace (rules for other modes anyway).
+yv3_planes_choice yv3_select_planes_i8(const yv3_conv_desc* d, int ncu) {
+    yv3_planes_choice bad = {};
+    bad.rc = YV3_ESHAPE;
+    if (d->cin % 64 || d->cin_up % 64 || (d->cin - d->cin_up) % 64 || d->cout % 8 || d->cout_pad % 32) return bad;
+    if (d->x_plane_stride > 0 || d->x2_plane_stride > 0 || d->y_plane_stride > 0) return bad;       // (no batch slices)
+    yv3_conv_desc h = *d;
+    h.cin = d->cin / 2; h.cin_up = d->cin_up / 2;
+    h.dtype = YV3_BF16; h.out_dtype = YV3_BF16;
+    h.options &= ~(YV3_OPT_K3S1 | YV3_OPT_WINO_EVEN | YV3_OPT_WINO_ALWAYS);
+    h.w_wino = nullptr; h.alpha_wino = nullptr; h.wino_ws = nullptr; h.wino_ws_bytes = 0; h.w_wino4 = nullptr;
+    h.workspace = nullptr; h.workspace_bytes = 0; h.dec_out = nullptr;
+    return yv3_select_planes(&h, 1, ncu);
+}
+
 // =========================================================================================== exact fp32
 
 // The even schedule of an F(4x4) launch: n_full whole-item workgroups + the other items cut into `parts` ranges of 6 / parts patch rows (parts = 1:

@@ -167,6 +167,9 @@ struct yv3_conv_shape { int Ho, Wo; long long M; };
 yv3_conv_shape yv3_conv_out_shape(const yv3_conv_desc* d);
 
 yv3_planes_choice yv3_select_planes(const yv3_conv_desc* d, int np, int ncu);     // np = planes per tensor: 1 bf16 (or fp16: YV3_F16 takes YV3_BF16's choice), 2 fp16 hi+lo, 3 bf16 x3
+// YV3_I8: the shape checks of the int8 kernels, then the one-bf16-plane choice for the layer's BYTES (an int8 layer of C input channels stages
+// the rows of a bf16 layer of C/2) without the forms and kernels that have no int8 instantiation
+yv3_planes_choice yv3_select_planes_i8(const yv3_conv_desc* d, int ncu);
 yv3_f32_choice yv3_select_f32(const yv3_conv_desc* d, int ncu);
 
 // One line (at most YV3_KERNEL_LINE_BYTES with its NUL) that holds every field of a choice that is not a function of the descriptor alone

@@ -5,6 +5,7 @@
 
 int yv3_pack_weight_planes(const float* w_oihw, void* w_packed, int cout, int cin, int k, int cout_pad, int np, hipStream_t s);
 int yv3_pack_weight_plane_f16(const float* w_oihw, void* w_packed, int cout, int cin, int k, int cout_pad, hipStream_t s);
+int yv3_pack_weight_i8(const float* w_oihw, void* w_packed, int cout, int cin, int k, int cout_pad, hipStream_t s);
 
 namespace {
 
@@ -49,6 +50,7 @@ extern "C" int yv3_pack_conv_weight(const float* w_oihw, void* w_packed, int cou
     if (dtype == YV3_BF16) return yv3_pack_weight_planes(w_oihw, w_packed, cout, cin, k, cout_pad, 1, s);
     if (dtype == YV3_F32_F16X2) return yv3_pack_weight_planes(w_oihw, w_packed, cout, cin, k, cout_pad, 2, s);
     if (dtype == YV3_F16) return k == 4 ? YV3_ESHAPE : yv3_pack_weight_plane_f16(w_oihw, w_packed, cout, cin, k, cout_pad, s);      // (no Winograd form)
+    if (dtype == YV3_I8) return k == 4 ? YV3_ESHAPE : yv3_pack_weight_i8(w_oihw, w_packed, cout, cin, k, cout_pad, s);      // (already quantised integers)
     if (dtype == YV3_F32)
         hipLaunchKernelGGL(pack_weight_kernel<float>, dim3(blocks), dim3(256), 0, s, w_oihw, (float*)w_packed, cout, cin, k, total);
     else

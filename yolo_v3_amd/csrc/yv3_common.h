@@ -33,6 +33,7 @@ static inline int yv3_num_cu() {
 // and returns launch errors, or YV3_EINVAL for a choice it has no instantiation for.
 int yv3_conv2d_planes(const yv3_conv_desc* d, int np, const yv3_planes_choice& c, hipStream_t s);
 int yv3_conv2d_planes_f16(const yv3_conv_desc* d, const yv3_planes_choice& c, hipStream_t s);      // YV3_F16 (conv_planes_f16.hip)
+int yv3_conv2d_planes_i8(const yv3_conv_desc* d, const yv3_planes_choice& c, hipStream_t s);       // YV3_I8 (conv_planes_i8.hip)
 int yv3_conv2d_f32(const yv3_conv_desc* d, const yv3_f32_choice& c, hipStream_t s);
 
 // float -> bf16 bits, round to nearest even (NaN kept quiet)

@@ -281,7 +281,12 @@ class YoloNet(nn.Module):
         #   F32             exact fp32 MFMA                                    -- ~2.7x slower
         # _ffi.BF16 and _ffi.F16 are the reduced-precision throughput modes (not 1e-4 modes): one 16-bit plane, the same kernels and
         # cost; F16 keeps 11 significant bits instead of 8 and needs activations within +-65504 (else it re-runs in BF16, once).
+        # _ffi.I8 is post-training quantisation: int8 activations (one scale per tensor, from calibrate_int8) and weights on the int8 matrix
+        # cores for the 68 conv_bn_relu layers behind the front; the front and the heads stay BF16 launches.  Inference only.
         self.math_mode = DEFAULT_MATH_MODE
+        # {conv name: activation scale} of math mode I8 (calibrate_int8, or a saved dict): a plain attribute -- pickled and deep-copied with
+        # the net, not a state_dict key
+        self.int8_scales = None
         # net(x, target) as a differentiable training step (yolo_v3_amd/backprop.py): False keeps the no-grad loss
         self.backprop = False
         # arithmetic of the training step's convolutions: F32 (exact fp32), BF16 (bf16 operands, fp32 accumulation) or BF16_ACT
@@ -295,6 +300,36 @@ class YoloNet(nn.Module):
         # BF16_ACT: the BF16 plan -- and the rest as before; False, or no such prefix: the training kernels run every layer
         self.frozen_prefix = False
         self._prefix_engines = {}
+
+    def __setattr__(self, name, value):
+        if name == "math_mode" and value == _ffi.I8 and not isinstance(value, bool):
+            _engine.int8_scales_checked(self, arch.conv_specs(self.numClass))      # Yv3Error: calibrate first
+        super().__setattr__(name, value)
+
+    # ---- I8 calibration
+    def _int8_calibration_outputs(self, x):
+        """{conv name: activation} of one batch in the exact F32 plan (its buffers: read them before the next call)."""
+        _, plan = self.engine(_ffi.F32).forward(x)
+        return plan.layer_out
+
+    def calibrate_int8(self, batches):
+        """Post-training calibration of math mode I8: runs every batch of `batches` (an iterable of [B, 3, H, W] fp32 tensors in [0, 1] on
+        the GPU) through the exact F32 plan, takes the running max of |x| of the front's output and of each int8 layer's output
+        (engine.int8_scale_names: 69 tensors) and stores ``self.int8_scales = {conv name: absmax / 127}`` (1.0 for a tensor that is zero
+        throughout).  Engines already packed for I8 re-pack on their next call.  Returns the dict."""
+        names = _engine.int8_scale_names(arch.conv_specs(self.numClass))
+        amax = None
+        for x in batches:
+            outs = self._int8_calibration_outputs(x)
+            cur = torch.stack([torch.amax(torch.abs(outs[n].detach().float())) for n in names])
+            amax = cur if amax is None else torch.maximum(amax, cur)
+        if amax is None:
+            raise _ffi.Yv3Error("calibrate_int8 needs at least one batch")
+        vals = amax.cpu().numpy().astype(np.float32)
+        if not np.isfinite(vals).all():
+            raise _ffi.Yv3Error("calibrate_int8: an activation is not finite (%s)" % ", ".join(n for n, v in zip(names, vals) if not np.isfinite(v)))
+        self.int8_scales = {n: (float(v / np.float32(127.0)) if v > 0 else 1.0) for n, v in zip(names, vals)}
+        return self.int8_scales
 
     # ---- HIP execution
     def prefix_engine(self, dtype, n_conv):

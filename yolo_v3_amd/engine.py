@@ -16,14 +16,15 @@ tensors.  Here the whole network is a static plan:
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _ffi, arch
 
-from ._ffi import ConvDesc, F32, BF16, F32X3, F32H2, F16, ACT_LEAKY, ACT_LINEAR
+from ._ffi import ConvDesc, F32, BF16, F32X3, F32H2, F16, I8, ACT_LEAKY, ACT_LINEAR
 
-_TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F32X3: torch.bfloat16, F32H2: torch.float16, F16: torch.float16}   # element type of activation storage
-PLANES = {F32: 0, BF16: 1, F32X3: 3, F32H2: 2, F16: 1}   # 0: plain fp32 NHWC tensor; n > 0: n 16-bit planes [n][B,H,W,C]
+_TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F32X3: torch.bfloat16, F32H2: torch.float16, F16: torch.float16, I8: torch.int8}   # element type of activation storage
+PLANES = {F32: 0, BF16: 1, F32X3: 3, F32H2: 2, F16: 1, I8: 1}   # 0: plain fp32 NHWC tensor; n > 0: n planes [n][B,H,W,C] (16-bit; I8: one plane of bytes)
 
 
 def alloc_act(B, h, w, c, dtype, device):
@@ -35,6 +36,8 @@ def alloc_act(B, h, w, c, dtype, device):
 
 def to_planes(x_nhwc_f32, dtype):
     """fp32 NHWC tensor -> the activation layout of `dtype` (exact for F32X3)."""
+    if dtype == I8:
+        raise _ffi.Yv3Error("an int8 tensor is integers and a scale: there is no layout conversion for I8")
     np_ = PLANES[dtype]
     if np_ == 0:
         return x_nhwc_f32.float().contiguous()
@@ -49,6 +52,8 @@ def to_planes(x_nhwc_f32, dtype):
 
 def from_planes(t, dtype):
     """Activation buffer of `dtype` -> fp32 NHWC tensor."""
+    if dtype == I8:
+        raise _ffi.Yv3Error("an int8 tensor is integers and a scale: there is no layout conversion for I8")
     np_ = PLANES[dtype]
     if np_ == 0 or t.dtype == torch.float32:
         return t
@@ -172,8 +177,92 @@ def pack_wino4(weight_f32, spec):
     return wp
 
 
-def pack_conv(module, spec, dtype, winograd=False, winograd4=True):
-    """Pack one conv (+BN) for the HIP kernels.  Parameters must already be on the GPU."""
+# ---- I8: calibrated int8 inference (tests/int8_ref.py restates the arithmetic in numpy)
+I8_FIRST = 4          # convolutions 0-3 (the fused front and res64 launches) and the three head convs stay BF16 launches
+
+
+def int8_graph(specs):
+    """{conv index: (source conv, route conv or None, cin_up, residual conv or None)} of all 75 convolutions by the architecture
+    (the walk of Plan.__init__): whose output a convolution reads -- for the two upsample + concat layers the upsampled source and
+    the route whose channels follow its cin_up -- and which tensor its epilogue adds."""
+    g, i, cur, routes = {0: (None, None, 0, None)}, 1, 0, {}
+    for stage, nblk in enumerate(arch.BACKBONE_BLOCKS):
+        g[i] = (cur, None, 0, None); cur = i; i += 1
+        for _ in range(nblk):
+            g[i] = (cur, None, 0, None)
+            g[i + 1] = (i, None, 0, cur)
+            cur = i + 1; i += 2
+        routes[stage] = cur
+
+    def branch(x, x2=None):
+        nonlocal i
+        cu = specs[x].cout if x2 is not None else 0
+        route = None
+        for j in range(7):
+            g[i] = (x, x2, cu, None) if (j == 0 and x2 is not None) else (x, None, 0, None)
+            x = i; i += 1
+            if j == 4:
+                route = x
+        return route
+
+    h1 = branch(cur)
+    g[i] = (h1, None, 0, None); u1 = i; i += 1
+    h2 = branch(u1, routes[3])
+    g[i] = (h2, None, 0, None); u2 = i; i += 1
+    branch(u2, routes[2])
+    assert i == len(specs)
+    return g
+
+
+def int8_layers(specs):
+    """Indices of the convolutions that run in int8: every conv_bn_relu from I8_FIRST on (68)."""
+    return [i for i, sp in enumerate(specs) if i >= I8_FIRST and sp.bn]
+
+
+def int8_scale_names(specs):
+    """Names of the calibrated tensors: the front's output (conv I8_FIRST - 1) and every int8 layer's output (69)."""
+    return [specs[I8_FIRST - 1].name] + [specs[i].name for i in int8_layers(specs)]
+
+
+def int8_scales_checked(net, specs):
+    """net.int8_scales as {name: float}, or Yv3Error: missing (not calibrated), incomplete, or not positive and finite."""
+    sc = getattr(net, "int8_scales", None)
+    if not sc:
+        raise _ffi.Yv3Error("math mode I8 needs activation scales: call net.calibrate_int8(batches) (or set net.int8_scales from a saved dict) first")
+    out = {}
+    for n in int8_scale_names(specs):
+        v = sc.get(n)
+        if v is None or not (0.0 < float(v) < float("inf")):
+            raise _ffi.Yv3Error("net.int8_scales[%r] = %r: every one of the %d calibrated tensors needs a positive finite scale -- call "
+                                "net.calibrate_int8(batches)" % (n, v, len(int8_scale_names(specs))))
+        out[n] = float(np.float32(v))
+    return out
+
+
+def int8_input_scales(specs, graph, scales, i):
+    """s_in(ci) of int8 layer i, fp32 [cin]: the source tensor's scale -- behind an upsample + concat the first cin_up channels carry the
+    upsampled tensor's and the rest the route's."""
+    src, src2, cu, _ = graph[i]
+    s_in = np.full(specs[i].cin, scales[specs[src].name], dtype=np.float32)
+    if src2 is not None:
+        s_in[cu:] = np.float32(scales[specs[src2].name])
+    return s_in
+
+
+def quantize_weight_i8(w, s_in):
+    """fp32 OIHW weights and the input scale per input channel -> (qw fp32 integers in [-127, 127], sw fp32 [cout]), all in fp32 on the
+    host: w' = w * s_in(ci); sw = max|w'[co]| / 127 (1 for an all-zero filter); qw = clip(rint(w' / sw), -127, 127)."""
+    w1 = (np.asarray(w, dtype=np.float32) * np.asarray(s_in, dtype=np.float32).reshape(1, -1, 1, 1)).astype(np.float32)
+    amax = np.abs(w1).reshape(w1.shape[0], -1).max(axis=1)
+    sw = np.where(amax > 0, amax / np.float32(127.0), np.float32(1.0)).astype(np.float32)
+    qw = np.clip(np.rint((w1 / sw.reshape(-1, 1, 1, 1)).astype(np.float32)), -127.0, 127.0).astype(np.float32)
+    return qw, sw
+
+
+def pack_conv(module, spec, dtype, winograd=False, winograd4=True, s_in=None, head_scale=None):
+    """Pack one conv (+BN) for the HIP kernels.  Parameters must already be on the GPU.  dtype I8 (s_in: the input scale per input
+    channel): int8 weights with s_in folded in, alpha = the epilogue multiplier m = sw * alpha_bn.  head_scale (a BF16 head conv behind
+    int8 layers): its input tensor's scale, folded into alpha -- the activations it reads are the integers themselves."""
     lib = _ffi.lib()
     weight, bn, bias = conv_params(module)
     _ffi.require_cuda(weight, "parameter %s" % spec.name)
@@ -190,6 +279,17 @@ def pack_conv(module, spec, dtype, winograd=False, winograd4=True):
     else:
         alpha = None
         beta = bias.detach().float().contiguous().clone()
+    if head_scale is not None:
+        alpha = torch.full((spec.cout,), float(np.float32(head_scale)), device=dev, dtype=torch.float32) if alpha is None else alpha * float(np.float32(head_scale))
+    if dtype == I8:
+        if s_in is None or bn is None or spec.cin % 64 or spec.cout % 64:
+            raise _ffi.Yv3Error("an int8 layer is a conv_bn_relu with input scales and channel counts that are multiples of 64 (%s)" % spec.name)
+        qw, sw = quantize_weight_i8(w32.cpu().numpy(), s_in)
+        m = (sw * alpha.cpu().numpy()).astype(np.float32)
+        wq = torch.from_numpy(qw).to(dev)
+        wp = torch.empty(spec.cout * spec.k * spec.k * spec.cin, device=dev, dtype=torch.int8)
+        _ffi.check(lib.yv3_pack_conv_weight(wq.data_ptr(), wp.data_ptr(), spec.cout, spec.cin, spec.k, spec.cout, I8, s), "yv3_pack_conv_weight")
+        return PackedConv(spec, wp, torch.from_numpy(m).to(dev), beta, spec.cout)
     w_orig, alpha_bn = w32, alpha
     if dtype in (F32H2, F16) and spec.cin != 3:
         # (F16: the same scale -- one fp16 plane keeps its 11 bits for every weight of a row down to 2^-14 of the row's maximum)
@@ -260,7 +360,7 @@ def batch_split(B, ho, wo, cout_pad, ncu):
 
 
 def make_desc(pc, x, y, B, H, W, residual=None, x2=None, cin_up=0, dtype=F32, out_dtype=None, flags=None, workspace=None,
-              batch=None, wino_ws=None, two_lanes=False, wino_always=False, wino4_tiles=False):
+              batch=None, wino_ws=None, two_lanes=False, wino_always=False, wino4_tiles=False, s_res=0.0, inv_s_out=0.0):
     """`batch` = (b0, nb): the descriptor covers images b0 .. b0+nb-1 of the [NP][B,...] plane tensors (plane dtypes only).
     `wino_always`: YV3_OPT_WINO_ALWAYS (``net.winograd = "always"``: the Winograd form on every eligible layer, whatever the
     tile count)."""
@@ -284,6 +384,7 @@ def make_desc(pc, x, y, B, H, W, residual=None, x2=None, cin_up=0, dtype=F32, ou
     d.act = ACT_LEAKY if sp.bn else ACT_LINEAR
     d.dtype = dtype
     d.out_dtype = dtype if out_dtype is None else out_dtype
+    d.s_res, d.inv_s_out = s_res, inv_s_out          # (I8 only: the residual tensor's scale, 1 / the output tensor's)
     d.flags = _ptr(flags)
     d.workspace = _ptr(workspace)
     d.workspace_bytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
@@ -364,7 +465,18 @@ class Plan:
                 need = max(need, max(_ffi.lib().yv3_wino4_workspace_bytes(B, H // f, W // f, c) for c, f in ((64, 4), (128, 8), (256, 16), (512, 32))))
             self.wino_ws = torch.zeros(need, device=dev, dtype=torch.uint8)       # (zero-filled: hand-over flags of the even schedule)
 
-        def buf(h, w, c, dtype=dt):
+        # I8: a mixed plan -- convolutions 0-3 and the heads are BF16 launches on bf16 planes, the 68 between them int8 launches on int8
+        # tensors (ldt: a layer's launch dtype); the front's output is quantised once (front_q), each head reads the integers of the
+        # layer before it, written as bf16 by that layer's epilogue
+        i8 = dt == I8
+        act_dt = BF16 if i8 else dt
+        i8_scales = engine.int8_scales if i8 else None
+        i8_graph = int8_graph(specs) if i8 else None
+
+        def ldt(i):
+            return I8 if (i8 and i >= I8_FIRST and specs[i].bn) else act_dt
+
+        def buf(h, w, c, dtype=act_dt):
             t = alloc_act(B, h, w, c, dtype, dev)
             keep.append(t)
             return t
@@ -378,10 +490,12 @@ class Plan:
         ncu = ncu & ~7 if ncu >= 8 else 256
         # feature.mlist.0 + feature.mlist.1 run as ONE launch (csrc/conv_front.hip; exact fp32: csrc/conv_front_f32.hip); the first
         # layer's [B,H,W,32] activation is then never written (conv0_out stays allocated for the un-fused / layer-by-layer paths)
-        self.fused_front = bool(engine.fuse_front and dt in (F32H2, BF16, F32, F16))
+        self.fused_front = bool(i8 or (engine.fuse_front and dt in (F32H2, BF16, F32, F16)))      # (I8: the front is always the two fused BF16 launches)
         # ... and the first residual block (feature.mlist.2: 1x1 64->32 + 3x3 32->64 + add) as one more (csrc/conv_res64.hip,
         # csrc/conv_res64_f32.hip)
-        self.fused_res64 = bool(self.fused_front and engine.fuse_res64)
+        self.fused_res64 = bool(i8 or (self.fused_front and engine.fuse_res64))
+        self.front_q = buf(H // 2, W // 2, specs[I8_FIRST - 1].cout, I8) if i8 else None
+        self.front_inv_s = float(np.float32(1.0) / np.float32(i8_scales[specs[I8_FIRST - 1].name])) if i8 else 0.0
         self.first_desc = 3 if self.fused_res64 else (1 if self.fused_front else 0)
 
         def conv(i, x, h, w, residual=None, x2=None, cin_up=0, out_dtype=None):
@@ -390,16 +504,24 @@ class Plan:
                 return None, ho, wo
             pc = packed[i]
             head = out_dtype == F32 and dt != F32
-            y = None if (head and self.fused_decode) else buf(ho, wo, pc.spec.cout, dt if out_dtype is None else out_dtype)
+            ld = ldt(i)
+            s_res = inv_s_out = 0.0
+            if ld == I8:
+                if i == I8_FIRST:
+                    x = self.front_q
+                inv_s_out = float(np.float32(1.0) / np.float32(i8_scales[pc.spec.name]))
+                if residual is not None:
+                    s_res = i8_scales[specs[i8_graph[i][3]].name]
+            y = None if (head and self.fused_decode) else buf(ho, wo, pc.spec.cout, ld if out_dtype is None else out_dtype)
             if head:
                 self.head_descs.append((len(descs), ho, wo))
             split = None
             if engine.batch_split and dt == F32H2 and pc.spec.k == 3 and not head and self.workspace is None:
                 split = batch_split(B, ho, wo, pc.cout_pad, ncu)
             for part in ([None] if split is None else [(0, split[0]), (split[0], split[1])]):
-                descs.append(make_desc(pc, x, y, B, h, w, residual, x2, cin_up, dt, out_dtype, self.flags, self.workspace, batch=part,
+                descs.append(make_desc(pc, x, y, B, h, w, residual, x2, cin_up, ld, out_dtype, self.flags, self.workspace, batch=part,
                                        wino_ws=self.wino_ws, two_lanes=two_lanes, wino_always=engine.wino_always,
-                                       wino4_tiles=engine.stream_k is False))
+                                       wino4_tiles=engine.stream_k is False, s_res=s_res, inv_s_out=inv_s_out))
                 self.desc_spec.append(i)
             if y is not None:
                 self.layer_out[pc.spec.name] = y
@@ -428,6 +550,8 @@ class Plan:
             for j in range(6):
                 if j == 0 and x2 is not None:
                     x, _, _ = conv(i, x, h, w, x2=x2, cin_up=cin_up)
+                elif j == 5 and i8:
+                    x, _, _ = conv(i, x, h, w, out_dtype=BF16)                 # the head's input: the same integers as one bf16 plane
                 else:
                     x, _, _ = conv(i, x, h, w)
                 i += 1
@@ -547,6 +671,9 @@ class Engine:
         if not self.FRONT_CONVS <= n_conv <= len(self.all_specs):
             raise _ffi.Yv3Error("an engine covers the first %d to %d convolutions, got %r" % (self.FRONT_CONVS, len(self.all_specs), n_conv))
         self.n_conv = int(n_conv)
+        if dtype == I8 and self.n_conv != len(self.all_specs):
+            raise _ffi.Yv3Error("I8 is an inference mode of the whole network: there is no int8 prefix engine")
+        self.int8_scales = None                          # I8: the checked copy of net.int8_scales the packed weights and plans were built from
         self.specs = self.all_specs[:self.n_conv]        # what this engine packs and runs
         self.packed = None
         self.device = None
@@ -637,6 +764,8 @@ class Engine:
         the 248 MB of weights and one host sync per forward) to the signature."""
         ts = self._param_tensors()
         sig = tuple((t.data_ptr(), t._version) for t in ts)
+        if self.dtype == I8:                # the scales are folded into the packed weights and written into the plans' descriptors
+            sig += (tuple(sorted(int8_scales_checked(self.net, self.all_specs).items())),)
         if getattr(self.net, "weight_check", "version") == "checksum" and ts and ts[0].is_cuda:
             # position-sensitive integer hash of the parameters' BIT patterns: sum_i bits_i * (i mod 65521 + 1) in wrapping
             # int64 per tensor, tensors combined with their index -- sees sign flips, swapped filters and swapped tensors
@@ -669,7 +798,20 @@ class Engine:
         _ffi.require_cuda(first, "YoloNet parameters (call net.cuda() first)")
         self.device = first.device
         with torch.cuda.device(self.device):
-            self.packed = [pack_conv(self.net.get_submodule(sp.name), sp, self.dtype, self.winograd, self.winograd4) for sp in self.specs]
+            if self.dtype == I8:
+                sc = self.int8_scales = int8_scales_checked(self.net, self.all_specs)
+                g = int8_graph(self.all_specs)
+
+                def pack(i, sp):
+                    mod = self.net.get_submodule(sp.name)
+                    if i < I8_FIRST:
+                        return pack_conv(mod, sp, BF16)
+                    if not sp.bn:
+                        return pack_conv(mod, sp, BF16, head_scale=sc[self.all_specs[g[i][0]].name])
+                    return pack_conv(mod, sp, I8, s_in=int8_input_scales(self.all_specs, g, sc, i))
+                self.packed = [pack(i, sp) for i, sp in enumerate(self.specs)]
+            else:
+                self.packed = [pack_conv(self.net.get_submodule(sp.name), sp, self.dtype, self.winograd, self.winograd4) for sp in self.specs]
         self._sig = sig
         self._plans = {}
         self.generation += 1          # holders of a Plan (Detector) must rebuild: descriptors point into `packed`
@@ -731,17 +873,20 @@ class Engine:
                                                           plan.B, plan.H // 2, plan.W // 2, _ffi.stream_ptr()), "yv3_res_block64_f32")
             return
         lib = _ffi.lib()
-        front = {F32H2: lib.yv3_conv_front, BF16: lib.yv3_conv_front_bf16, F16: lib.yv3_conv_front_f16}[self.dtype]
+        front = {F32H2: lib.yv3_conv_front, BF16: lib.yv3_conv_front_bf16, F16: lib.yv3_conv_front_f16, I8: lib.yv3_conv_front_bf16}[self.dtype]
         _ffi.check(front(x.data_ptr(), p0.w.data_ptr(), p0.alpha.data_ptr(), p0.beta.data_ptr(),
                                              p1.w.data_ptr(), p1.alpha.data_ptr(), p1.beta.data_ptr(), d1.y,
                                              plan.B, plan.H, plan.W, plan.flags.data_ptr(), _ffi.stream_ptr()), "yv3_conv_front")
         if plan.fused_res64:
             p2, p3, d3 = self.packed[2], self.packed[3], plan.descs[2]
-            res = {F32H2: lib.yv3_res_block64, BF16: lib.yv3_res_block64_bf16, F16: lib.yv3_res_block64_f16}[self.dtype]
+            res = {F32H2: lib.yv3_res_block64, BF16: lib.yv3_res_block64_bf16, F16: lib.yv3_res_block64_f16, I8: lib.yv3_res_block64_bf16}[self.dtype]
             _ffi.check(res(d1.y, p2.w.data_ptr(), p2.alpha.data_ptr(), p2.beta.data_ptr(),
                                                   p3.w.data_ptr(), p3.alpha.data_ptr(), p3.beta.data_ptr(), d3.y,
                                                   plan.B, plan.H // 2, plan.W // 2, plan.flags.data_ptr(), _ffi.stream_ptr()),
                        "yv3_res_block64")
+            if self.dtype == I8:              # the one boundary launch: the front's bf16 output -> the first int8 layer's input
+                _ffi.check(lib.yv3_quantize_bf16_i8(d3.y, plan.front_q.data_ptr(), plan.front_q.numel(), plan.front_inv_s, _ffi.stream_ptr()),
+                           "yv3_quantize_bf16_i8")
 
     def run_conv_sequence(self, plan, dets=None):
         """The remaining convolutions (74, or 73 behind a fused front; a prefix engine: those of its n_conv).  With a fused-decode plan `dets` (the detections
@@ -798,7 +943,7 @@ class Engine:
                 raise StreamKTimeout("a stream-K accumulator hand-over timed out: the schedule needs all of its workgroups resident at once "
                                      "and something else (another stream / thread / process running small batches) held part of the GPU.  "
                                      "Callers that share the GPU set net.stream_k = False (or net.deterministic = True)")
-            raise RangeOverflow({BF16: self.OVERFLOW_MSG_BF16, F16: self.OVERFLOW_MSG_F16}.get(self.dtype, self.OVERFLOW_MSG))
+            raise RangeOverflow({BF16: self.OVERFLOW_MSG_BF16, I8: self.OVERFLOW_MSG_BF16, F16: self.OVERFLOW_MSG_F16}.get(self.dtype, self.OVERFLOW_MSG))
 
     def range_fallback(self):
         """After a RangeOverflow: the engine that takes over (RANGE_FALLBACK) -- for the default mode F32X3, the same plane pipeline on
@@ -822,7 +967,7 @@ class Engine:
     def checks_status(self):
         """Does a forward of this engine have a kernel status word to look at?  F32H2 / F16 / BF16: fp16 saturation (+ stream-K hand-over);
         F32: only the F(4x4) stage's even schedule can set it (hand-over time-out on a shared GPU) -- not with ``net.stream_k = False``."""
-        return self.dtype in (F32H2, BF16, F16) or (self.dtype == F32 and self.winograd and self.winograd4 and self.stream_k is not False)
+        return self.dtype in (F32H2, BF16, F16, I8) or (self.dtype == F32 and self.winograd and self.winograd4 and self.stream_k is not False)
 
     def disable_stream_k(self):
         """After a StreamKTimeout: this engine stops using the stream-K schedule (plans are rebuilt without its workspace; holders
