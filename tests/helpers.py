@@ -103,8 +103,11 @@ def trained_like_stream(num_class=80, seed=20260935, b_obj=-2.0, b_cls=-2.0, hea
 # ----------------------------------------------------------------------------- layer-by-layer ("teacher-forced") runs
 def desc_inputs_by_pointer(plan):
     """``names(d) -> (x, x2, residual)``: the producing layer's name (or None) of each input pointer of a descriptor of `plan`.  `Plan` gives
-    every conv its own output buffer (``plan.layer_out[name]``, never reused), so a pointer identifies its producer."""
+    every conv its own output buffer (``plan.layer_out[name]``, never reused), so a pointer identifies its producer.  An I8 plan's
+    ``front_q`` -- the front's output as int8, written by the quantise launch from the third descriptor's output -- carries that layer's name."""
     ptr2name = {buf.data_ptr(): name for name, buf in plan.layer_out.items()}
+    if getattr(plan, "front_q", None) is not None:
+        ptr2name[plan.front_q.data_ptr()] = ptr2name[plan.descs[2].y]
 
     def names(d):
         return tuple(ptr2name[ptr] if ptr else None for ptr in (d.x, d.x2, d.residual))
@@ -136,6 +139,22 @@ def relaunch_desc(d, n, what, dtype=torch.float32, planes=1):
     assert bool(torch.isnan(y[n:]).all()), "%s: wrote past the end of y" % what
     holes = int(torch.isnan(y[:n]).sum())
     assert holes == 0, "%s: %d output elements not written" % (what, holes)
+    return y[:n]
+
+
+def relaunch_desc_i8(d, n, what):
+    """relaunch_desc for an int8 output: the buffer is filled with -128, which the int8 epilogue never produces, and has bytes of 85
+    behind it.  Every byte written, nothing behind.  Returns the [n] int8 elements."""
+    import ctypes
+    from yolo_v3_amd import _ffi
+    y = torch.full((n + CANARY,), -128, dtype=torch.int8, device="cuda")
+    y[n:] = 85
+    d.y = y.data_ptr()
+    _ffi.check(_ffi.lib().yv3_conv2d(ctypes.byref(d), _ffi.stream_ptr()), what)
+    torch.cuda.synchronize()
+    assert bool((y[n:] == 85).all()), "%s: wrote past the end of y" % what
+    holes = int((y[:n] == -128).sum())
+    assert holes == 0, "%s: %d output bytes not written (or -128 produced)" % (what, holes)
     return y[:n]
 
 

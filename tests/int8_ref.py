@@ -101,6 +101,46 @@ def conv_layer(xq, w, s_in, alpha, beta, s_out, stride=1, x2q=None, res_q=None, 
     return epilogue(acc, m, beta, s_out, res_q, s_res).astype(np.int8)
 
 
+def patch_index(pix, k, stride, H, W):
+    """Where the k x k input window of each output pixel lies.  pix: integer [P, 3] rows (b, yo, xo).  Returns (b, yi, xi, inside), each
+    [P, k, k]: the image, the input coordinates clamped into the H x W picture, and whether the tap lies inside it (pad (k-1)/2: taps
+    outside read zero).  Plain index arithmetic, so that a test can gather the windows wherever the tensor lives."""
+    pix = np.asarray(pix, dtype=np.int64).reshape(-1, 3)
+    pad = (k - 1) // 2
+    t = np.arange(k, dtype=np.int64)
+    yi = (pix[:, 1] * stride - pad)[:, None, None] + t[None, :, None] + 0 * t[None, None, :]
+    xi = (pix[:, 2] * stride - pad)[:, None, None] + t[None, None, :] + 0 * t[None, :, None]
+    inside = (yi >= 0) & (yi < H) & (xi >= 0) & (xi < W)
+    b = np.broadcast_to(pix[:, 0][:, None, None], yi.shape)
+    return b, np.clip(yi, 0, H - 1), np.clip(xi, 0, W - 1), inside
+
+
+def gather_patches(xq, pix, k, stride, x2q=None):
+    """The input windows [P, k, k, C] int8 of output pixels `pix` from the layer's int8 NHWC input: xq, or (x2q given) nearest x2 of xq
+    followed by x2q's channels -- read from the two sources directly, without building the concatenated tensor."""
+    H, W = (x2q if x2q is not None else xq).shape[1:3]
+    b, yi, xi, inside = patch_index(pix, k, stride, H, W)
+    if x2q is None:
+        p = xq[b, yi, xi]
+    else:
+        p = np.concatenate((xq[b, yi // 2, xi // 2], x2q[b, yi, xi]), axis=3)
+    return (p * inside[..., None]).astype(np.int8)
+
+
+def layer_at_pixels(patches, w, s_in, alpha, beta, s_out, res_q=None, s_res=None, qw_sw=None):
+    """One int8 layer from its fp32 parameters on a set of output pixels: patches [P, k, k, C] int8 (gather_patches), res_q [P, O] int8 or
+    None -> [P, O] fp32 integers in [-127, 127], what conv_layer gives at those pixels.  qw_sw: quantize_weights(w, s_in), when the
+    caller keeps it."""
+    qw, sw = qw_sw if qw_sw is not None else quantize_weights(w, s_in)
+    O = qw.shape[0]
+    m = (sw * np.asarray(alpha, dtype=F32)).astype(F32)
+    P = patches.shape[0]
+    wm = np.asarray(qw, dtype=np.float64).transpose(0, 2, 3, 1).reshape(O, -1)           # (kh, kw, ci), as the patches are laid out
+    acc = patches.reshape(P, -1).astype(np.float64) @ wm.T
+    assert np.abs(acc).max(initial=0) < 2.0 ** 31
+    return epilogue(acc.astype(np.int64).astype(np.int32), m, beta, s_out, res_q, s_res)
+
+
 def fold_bn(gamma, bias, mean, var, eps=1e-5):
     """alpha = gamma / sqrt(var + eps), beta = bias - mean * alpha, separate fp32 roundings."""
     a = (np.asarray(gamma, dtype=F32) / np.sqrt((np.asarray(var, dtype=F32) + F32(eps)).astype(F32)).astype(F32)).astype(F32)

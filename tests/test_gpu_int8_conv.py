@@ -1,9 +1,11 @@
 """The I8 math mode's kernels through the C-ABI, bit for bit against the definition (tests/int8_ref.py): the int8
 implicit-GEMM convolution on v_mfma_i32_32x32x32_i8 -- random int8 inputs and weights over the full range, +-127 included, at the
 smallest shapes at which each path can still go wrong, on the tile the selector picks and on every forced one-plane tile -- its
-bf16-output form, and the bf16 -> int8 quantise kernel.  Integer sums are exact, so a wrong lane map, halo, stride or K order cannot
+bf16-output form, and the bf16 -> int8 quantise kernel; then every tile again on grids of 11 to 48 workgroups (GRID_CASES: three or more
+row tiles, up to eight channel tiles, a remapped workgroup index), each forced launch held to the tile it asked for.  Integer sums are exact, so a wrong lane map, halo, stride or K order cannot
 hide inside a tolerance."""
 import ctypes
+import time
 
 import numpy as np
 import pytest
@@ -155,6 +157,65 @@ def test_int8_conv_bitwise(name, kw):
         seen.add(line)
         _same(layer.launch(big_tile_min=1, what=name + " big_tile_min 1"), want, "%s big_tile_min 1 (%s)" % (name, line))
     print("i8 conv | %s | forced tiles run: %s" % (name, sorted(seen)))
+
+
+# Many tiles in both directions: three or more row tiles of every tile height (the last one ragged), two to eight channel tiles, 12 to 48
+# workgroups -- yv3_xcd_remap permutes the workgroup index from 8 workgroups on, and with a count that is no multiple of 8 both of its
+# branches run.  On these shapes the selector accepts every code of CODES and big_tile_min = 1 (256 CUs, checked on the host): the test
+# asserts the tile it asked for, so a declined code cannot pass on the default's tile.
+TILE_OF_CODE = {1: "256x128_W8", 2: "128x128_W8", 3: "128x128_W4", 5: "256x128_W4", 6: "256x256", 7: "256x128_W4_ROLL", 8: "256x256_ROLL",
+                9: "256x256_ROLL4", 11: "192x256_ROLL", 13: "256x256_PP3", 14: "256x256_PP4", 15: "192x256_PP3", 16: "192x256_PP4"}
+BF16_OUT_CODES = (14, 16)
+GRID_CASES = [
+    ("3x3_128to1024_res_grid", dict(cin=128, cout=1024, k=3, B=4, H=13, W=13, res=True), CODES),      # M = 676: 3 x 256 / 4 x 192 / 6 x 128 rows, 4 or 8 channel tiles
+    ("1x1_1024to512_grid", dict(cin=1024, cout=512, B=4, H=13, W=13), CODES),                         # 16 chunks of 64 on the 3-, 4- and 6-deep rings
+    ("1x1_256to512_grid", dict(cin=256, cout=512, B=5, H=13, W=13), CODES),                           # M = 845: four row tiles of 256; 4 chunks < the 6-deep ring
+    ("3x3_s2_64to256_grid", dict(cin=64, cout=256, k=3, stride=2, B=3, H=38, W=26), CODES),           # -> 19 x 13 (M = 741): stride 2, non-square, odd output sizes
+    ("1x1_upcat_128+256to256_grid", dict(cin=384, cout=256, cin_up=128, B=5, H=14, W=10), CODES),     # M = 700: the two-source gather across row tiles and images
+    ("3x3_512to1024_res_timed", dict(cin=512, cout=1024, k=3, B=4, H=13, W=13, res=True), BF16_OUT_CODES),   # K = 4608: DESIGN.md 8g's 1821 TOP/s layer
+    ("1x1_128to64_grid", dict(cin=128, cout=64, B=8, H=13, W=13), ()),                                # M = 1352: 11 workgroups of the one 64-channel tile (128x64)
+]
+
+
+def _tile(line):
+    return line.split()[0]
+
+
+@pytest.mark.parametrize("name,kw,codes", GRID_CASES, ids=[c[0] for c in GRID_CASES])
+def test_int8_conv_grid_bitwise(name, kw, codes):
+    """Every int8 tile on a grid of 12 to 48 workgroups, whole tensor against the definition: the selector's tile, every forced code and
+    big_tile_min = 1 with int8 output; the selector's tile and codes 14 and 16 (the ping-pong tiles of the timed plans) with bf16 output.
+    Each forced launch must run the tile it was asked for."""
+    t0 = time.time()
+    layer = Layer(seed=len(name) * 13 + 1, **kw)
+    acc, want = layer.ref()
+    t_ref = time.time() - t0
+    default = _ffi.conv2d_kernel(layer.desc(None))
+    print("i8 grid | %s | M = %d | %s | max |acc| %d | outputs at +-127: %.1f %% | distinct q: %d" % (
+        name, layer.B * layer.Ho * layer.Wo, default, int(np.abs(acc.astype(np.int64)).max()), 100.0 * float((np.abs(want) == 127).mean()), len(np.unique(want))))
+    assert len(np.unique(want)) > 20, "the reference output does not spread: the case checks nothing"
+    assert _ffi.conv2d_kernel(layer.desc(None, out_dtype=BF16)) == default
+    _same(layer.launch(what=name), want, name + " default (%s)" % default)
+    _same(layer.launch(BF16, what=name + " bf16 out"), want, name + " bf16 out (%s)" % default)
+    ran = [default]
+    for code in codes:
+        line = _ffi.conv2d_kernel(layer.desc(None, code=code))
+        assert _tile(line) == TILE_OF_CODE[code], "%s: code %d was declined: the selector gives %s" % (name, code, line)
+        ran.append(line)
+        _same(layer.launch(code=code, what="%s code %d" % (name, code)), want, "%s code %d (%s)" % (name, code, line))
+        if code in BF16_OUT_CODES:
+            assert _ffi.conv2d_kernel(layer.desc(None, out_dtype=BF16, code=code)) == line
+            _same(layer.launch(BF16, code=code, what="%s code %d bf16 out" % (name, code)), want, "%s code %d bf16 out (%s)" % (name, code, line))
+    if layer.cout % 128:
+        assert _tile(default) == "128x64" and not codes, default          # 64 output channels: the one tile there is
+    else:
+        line = _ffi.conv2d_kernel(layer.desc(None, big_tile_min=1))
+        assert _tile(line) == "256x128_W8_PP6", "%s: big_tile_min = 1 was declined: the selector gives %s" % (name, line)
+        ran.append(line)
+        _same(layer.launch(big_tile_min=1, what=name + " big_tile_min 1"), want, "%s big_tile_min 1 (%s)" % (name, line))
+        assert len(set(ran[1:])) == len(codes) + 1, ran
+    print("i8 grid | %s | %d launches, %.2f s (numpy reference %.2f s) | lines run: %s" % (
+        name, len(ran) + 1 + sum(c in BF16_OUT_CODES for c in codes), time.time() - t0, t_ref, "; ".join(ran)))
 
 
 def test_int8_conv_extreme_case_exercises_int_to_float_rounding():

@@ -100,6 +100,34 @@ def test_epilogue_clip_edges_and_ties():
     assert ir.quantize_act(np.array([0.5, 1.5, -0.5, -0.0, 1e9, -1e9, np.nan], dtype=F32), 1.0).tolist() == [0, 2, 0, 0, 127, -127, 0]
 
 
+def test_layer_at_pixels_equals_conv_layer():
+    """int8_ref.layer_at_pixels on gathered windows == int8_ref.conv_layer at those pixels, for every output pixel of three small layers:
+    3x3 with a residual (halos on all edges), 3x3 stride 2 on a non-square picture with odd output sizes, and the two-source 1x1."""
+    rng = np.random.default_rng(5)
+    for cin, cout, k, stride, B, H, W, res, cin_up in ((64, 64, 3, 1, 2, 5, 7, True, 0), (64, 128, 3, 2, 2, 10, 6, False, 0), (192, 64, 1, 1, 2, 6, 10, False, 64)):
+        x = rng.integers(-127, 128, size=(B, H // 2 if cin_up else H, W // 2 if cin_up else W, cin_up or cin)).astype(np.int8)
+        x2 = rng.integers(-127, 128, size=(B, H, W, cin - cin_up)).astype(np.int8) if cin_up else None
+        w = (rng.standard_normal((cout, cin, k, k)) * 0.05).astype(F32)
+        s_in = ir.input_scales(cin, 0.02, cin_up, 0.05 if cin_up else None)
+        alpha, beta = rng.uniform(0.5, 1.5, cout).astype(F32), rng.uniform(-1.0, 1.0, cout).astype(F32)
+        s_out = 0.0017 * np.sqrt(k * k * cin)                           # ~3 sigma of the activation at 127
+        pad = (k - 1) // 2
+        Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+        r = rng.integers(-127, 128, size=(B, Ho, Wo, cout)).astype(np.int8) if res else None
+        want = ir.conv_layer(x, w, s_in, alpha, beta, s_out, stride, x2, r, 0.03 if res else None)
+        assert want.shape == (B, Ho, Wo, cout) and len(np.unique(want)) > 50
+        pix = np.stack(np.meshgrid(np.arange(B), np.arange(Ho), np.arange(Wo), indexing="ij"), axis=-1).reshape(-1, 3)
+        pix = pix[rng.permutation(len(pix))]                             # any order, every pixel
+        patches = ir.gather_patches(x, pix, k, stride, x2)
+        assert patches.shape == (len(pix), k, k, cin) and patches.dtype == np.int8
+        got = ir.layer_at_pixels(patches, w, s_in, alpha, beta, s_out, r[pix[:, 0], pix[:, 1], pix[:, 2]] if res else None, 0.03 if res else None)
+        assert np.array_equal(got, want[pix[:, 0], pix[:, 1], pix[:, 2]].astype(F32)), (cin, cout, k, stride)
+        if k == 3:                                                       # the corner windows are zero outside the picture, and only there
+            b, yi, xi, inside = ir.patch_index(np.array([[0, 0, 0], [B - 1, Ho - 1, Wo - 1]]), k, stride, H, W)
+            assert not inside[0, 0].any() and not inside[0, :, 0].any() and inside[0, 1:, 1:].all()
+            assert inside[1].sum() == (4 if stride == 1 else 9)            # (stride 2 on an even picture: the last window ends at the last row)
+
+
 # ----------------------------------------------------------------------------- calibration and the mode's checks
 def _names():
     return engine.int8_scale_names(arch.conv_specs(3))
