@@ -795,6 +795,43 @@ size_t yv3_jpeg_workspace_bytes(const yv3_jpeg_info* infos_host, int B);
  * identical calls give identical bits. */
 int yv3_jpeg_decode_batch(const yv3_jpeg_batch_desc* desc, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The update step (csrc/optim.hip; yolo_v3_amd/optim.py): torch's clip_grad_norm_ and torch.optim.SGD over a list of fp32
+ * tensors, a few launches for the whole list.  The list arguments (g, p, buf, n) are HOST arrays of `count` device pointers /
+ * element counts; they are read during the call and travel in the kernel arguments, so the caller may reuse them at once.
+ * Each workgroup owns YV3_OPTIM_CHUNK consecutive elements of one tensor.  Pointers need 4-byte alignment only (16-byte
+ * aligned entries take 16-byte accesses); every access is bounded by the entry's n.  Entries must not overlap.  No allocation,
+ * no synchronisation, no device-to-host read, no atomics: identical calls give identical bits.  YV3_EINVAL (a null pointer, a
+ * count < 0, an n <= 0, unknown flags), YV3_EWORKSPACE, YV3_ELIMIT (a tensor of more than 2^30 chunks) -- all before any launch.
+ * ------------------------------------------------------------------------------------------ */
+#define YV3_OPTIM_CHUNK   16384
+#define YV3_SGD_FIRST     1   /* the first step of these parameters: buf = d (buf is not read)   */
+#define YV3_SGD_NESTEROV  2
+#define YV3_SGD_MAXIMIZE  4
+
+/* YV3_OPTIM_CHUNK, for callers that size the partials. */
+int yv3_optim_chunk(void);
+
+/* partials[k] = the fp64 sum of g^2 over chunk k, chunks numbered tensor by tensor (tensor i has ceil(n[i] / YV3_OPTIM_CHUNK)):
+ * per thread in element order, then a fixed tree over the workgroup's threads.  YV3_EWORKSPACE if partials_cap (in doubles)
+ * is smaller than the number of chunks. */
+int yv3_grad_sumsq(const float* const* g, const long long* n, int count, double* partials, long long partials_cap, void* stream);
+
+/* out[0] = total_norm = (float)sqrt(partials[0] + partials[1] + ..., in index order, fp64);
+ * out[1] = coef = min(max_norm / (total_norm + 1e-6f), 1.0f) in fp32, NaN if the quotient is NaN.  count = 0 gives 0 and 1. */
+int yv3_clip_coef(const double* partials, long long count, float max_norm, float* out, void* stream);
+
+/* g = g * (*coef) for every tensor of the list; coef on the device. */
+int yv3_grad_scale(float* const* g, const long long* n, int count, const float* coef, void* stream);
+
+/* One SGD step on every (p, g, buf) of the list with one set of hyper-parameters; per element, each line one fp32 rounding:
+ *   gs = coef ? g * (*coef) : g;  if MAXIMIZE: gs = -gs;         d = weight_decay != 0 ? gs + weight_decay * p : gs;
+ *   if momentum != 0:  buf = FIRST ? d : momentum * buf + one_minus_dampening * d;   d = NESTEROV ? d + momentum * buf : buf;
+ *   p = p + (-lr) * d.
+ * g is not written.  buf may be NULL when momentum == 0; coef (device) may be NULL. */
+int yv3_sgd_step(float* const* p, const float* const* g, float* const* buf, const long long* n, int count, const float* coef,
+                 float lr, float momentum, float one_minus_dampening, float weight_decay, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

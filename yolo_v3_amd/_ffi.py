@@ -195,6 +195,11 @@ _SIGNATURES = {
     "yv3_jpeg_parse": (c_int, [c_void_p, c_size_t, ctypes.POINTER(JpegInfo)]),
     "yv3_jpeg_workspace_bytes": (c_size_t, [c_void_p, c_int]),
     "yv3_jpeg_decode_batch": (c_int, [ctypes.POINTER(JpegBatchDesc), c_void_p, c_size_t, c_void_p]),
+    "yv3_optim_chunk": (c_int, []),
+    "yv3_grad_sumsq": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_longlong, c_void_p]),
+    "yv3_clip_coef": (c_int, [c_void_p, c_longlong, c_float, c_void_p, c_void_p]),
+    "yv3_grad_scale": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "yv3_sgd_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_float, c_float, c_float, c_float, c_int, c_void_p]),
 }
 # a _bf16 twin takes its base entry's arguments, with bf16 tensors where the base has fp32 ones (all void* here)
 _SIGNATURES.update({twin: _SIGNATURES[twin.replace("_bf16", "")] for twin in (
