@@ -478,6 +478,63 @@ int yv3_augment_images_from(const unsigned char* src, long long src_bytes, const
 int yv3_augment_labels(const double* labels, int B, int T, const int* hw, const double* params,
                        float* target, int max_rows, int out_h, int out_w, int* status, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The reference's ExtraAugmentations (transforms.py:292-329; csrc/extra_augment.hip) for B packed uint8 RGB images of any
+ * sizes: one program of at most YV3_EXTRA_MAX_STEPS steps per image, every step on the whole output of the step before,
+ * per channel, uint8 -> uint8.  The operations (tests/extra_aug_ref.py is their definition; v = the step's v[0..2]):
+ *   YV3_EXTRA_GAUSS     scipy.ndimage.gaussian_filter(sigma = v[0]) on uint8: radius r = int(4 sigma + 0.5) <= 12, the program's
+ *                       float64 gauss_w[0 .. 2r] (computed by the caller: exp(-0.5 / sigma^2 x^2), normalised), border reflect, rows
+ *                       then columns, each pass truncated to uint8; r == 0 leaves the image as it is
+ *   YV3_EXTRA_AVERAGE   cv2.blur, k in 2..7, anchor k / 2, border reflect-101, rint(float64(sum) * (1.0 / (k k)))
+ *   YV3_EXTRA_MEDIAN    odd k in 3..11, the middle of the k x k window, border replicated
+ *   YV3_EXTRA_SHARPEN   3x3 float32 kernel (1 - alpha) I + alpha [-1 .. 8 + lightness .. -1], alpha = v[0], lightness = v[1],
+ *                       border reflect-101, float32 sums in row-major tap order, rint, clip
+ *   YV3_EXTRA_NOISE     trunc(clip(p + v[0] * z)), z from Philox4x32-10 under `key` (counter = the pixel index y W + x, or that
+ *                       times 3 plus the channel when per_channel is 1) and Box-Muller in float64
+ *   YV3_EXTRA_ADD       clip(p + (int)v[c]), whole numbers in -255..255
+ *   YV3_EXTRA_MUL       trunc(clip(float32(p) * float32(v[c])))
+ *   YV3_EXTRA_CONTRAST  trunc(clip(float32(v[c]) * (float32(p) - 128) + 128))
+ * A program holds one weight table, used by each of its GAUSS steps with r > 0 (which therefore share one sigma; the kernels can
+ * only check r == gauss_radius).  The kernels check every
+ * image themselves and write status[b]: 0, or YV3_EINVAL (H or W <= 0, a range outside its buffer, n_steps outside 0..6, an
+ * unknown opcode, k out of range or even for the median, a non-finite value, a negative sigma or scale, r > 12, r != gauss_radius,
+ * weights that are not finite or not symmetric, per_channel not 0 / 1, a fractional ADD value); such an image is copied through
+ * unchanged (nothing is written for one whose ranges are out of bounds).  The return value covers the host arguments (YV3_EINVAL,
+ * YV3_EWORKSPACE), checked before any launch.  No allocation, no synchronisation, no atomics: identical calls give identical bits.
+ * ------------------------------------------------------------------------------------------ */
+#define YV3_EXTRA_MAX_STEPS 6
+#define YV3_EXTRA_MAX_RADIUS 12
+enum { YV3_EXTRA_GAUSS = 1, YV3_EXTRA_AVERAGE = 2, YV3_EXTRA_MEDIAN = 3, YV3_EXTRA_SHARPEN = 4, YV3_EXTRA_NOISE = 5,
+       YV3_EXTRA_ADD = 6, YV3_EXTRA_MUL = 7, YV3_EXTRA_CONTRAST = 8 };
+
+typedef struct yv3_extra_step {
+    int op;                      /* YV3_EXTRA_*                                                   */
+    int k;                       /* AVERAGE, MEDIAN: the window's side                            */
+    int per_channel;             /* NOISE: 0 = one draw per pixel, 1 = one per byte               */
+    int reserved;
+    double v[3];                 /* the operation's values (see above)                            */
+    unsigned long long key;      /* NOISE: the Philox key                                         */
+} yv3_extra_step;                /* 48 bytes */
+
+typedef struct yv3_extra_program {
+    int n_steps;                 /* 0 .. YV3_EXTRA_MAX_STEPS                                      */
+    int gauss_radius;            /* the radius gauss_w was computed for (0: no table)             */
+    yv3_extra_step steps[YV3_EXTRA_MAX_STEPS];
+    double gauss_w[2 * YV3_EXTRA_MAX_RADIUS + 1];
+} yv3_extra_program;             /* 496 bytes */
+
+/* Bytes of workspace yv3_extra_augment needs for a batch whose packed outputs take out_bytes (0 if out_bytes <= 0). */
+size_t yv3_extra_augment_workspace_bytes(long long out_bytes);
+
+/* Six launches (one per program slot).  Image b = hw[2b] x hw[2b+1] x 3 bytes, read at src + src_offsets[b] (inside src_bytes:
+ * src may be a packed batch or a larger allocation the images are gathered from; it is not written) and written at
+ * out + out_offsets[b] (inside out_bytes); its intermediate results live at workspace + out_offsets[b].  The out ranges of a
+ * batch must not overlap each other or the sources (the caller's duty).  All offsets are int64 bytes and need no alignment.
+ * programs: yv3_extra_program[B] in device memory.  workspace: >= yv3_extra_augment_workspace_bytes(out_bytes). */
+int yv3_extra_augment(const unsigned char* src, long long src_bytes, const long long* src_offsets, const int* hw,
+                      const void* programs, int B, unsigned char* out, long long out_bytes, const long long* out_offsets,
+                      void* workspace, size_t workspace_bytes, int* status, void* stream);
+
 /* Stand-alone UpsampleGroup tail (reference darknet.py:159-162: ``F.interpolate(out, scale_factor=2, mode='nearest')`` then
  * ``torch.cat((out, route_tail), 1)``), NCHW fp32:  out[b, c, y, x] = up[b, c, y/2, x/2] for c < c_up, tail[b, c - c_up, y, x] beyond.
  * up [B, c_up, h, w], tail [B, c_tail, 2h, 2w], out [B, c_up + c_tail, 2h, 2w].  Pure data movement (bit-exact).  Inside YoloNet

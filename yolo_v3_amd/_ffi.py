@@ -164,6 +164,9 @@ _SIGNATURES = {
     "yv3_augment_images_from": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_void_p,
                                         c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "yv3_augment_labels": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "yv3_extra_augment_workspace_bytes": (c_size_t, [c_longlong]),
+    "yv3_extra_augment": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_longlong, c_void_p,
+                                  c_void_p, c_size_t, c_void_p, c_void_p]),
     "yv3_upsample2x_concat": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "yv3_correct_boxes": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "yv3_gather_boxes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),

@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from . import _ffi
+from .extra_augment import sample_extra, check_programs, extra_augment_batch      # noqa: F401 (part of this module's interface)
 
 MAX_LABELS = 90
 N_PARAMS = 8                 # dhue, dsat, dexp, top, right, bottom, left, flip
@@ -379,13 +380,18 @@ class TrainBatches:
     the kernels write straight into the arena.  Files the GPU decoder does not take go through `read_image_rgb` as before.  The
     switch is not part of a ``state_dict``'s config: both settings give the same bits.
 
+    ``extra=True``: the reference's ``ExtraAugmentations`` in front of everything else, as ``Compose([ExtraAugmentations(),
+    IaaAugmentations([...]), ToTensor()])`` has them: every batch is ``augment_batch(extra_augment_batch(images,
+    sample_extra(seeds, shapes)), ...)`` (`yolo_v3_amd.extra_augment`) -- the extras run on the raw source (the arena keeps raw
+    sources), labels are untouched.  The switch is part of a ``state_dict``'s config when it is on.
+
     ``state_dict()`` / ``load_state_dict()`` resume between two batches with the same data order."""
 
     def __init__(self, list_file, batch_size, dim, seed, shuffle=True, max_labels=MAX_LABELS, multiscale=None, dim_interval=10,
-                 workers=0, prefetch=2, cache_bytes=0, decode="pil", **aug):
+                 workers=0, prefetch=2, cache_bytes=0, decode="pil", extra=False, **aug):
         if decode not in ("pil", "gpu"):
             raise ValueError("decode must be 'pil' or 'gpu'")
-        self.decode, self._side = decode, None
+        self.decode, self._side, self.extra = decode, None, bool(extra)
         with open(list_file, 'r') as f:
             self.img_list = [line.strip() for line in f.readlines() if line.strip()]
         self.label_list = [label_path(p) for p in self.img_list]
@@ -413,9 +419,12 @@ class TrainBatches:
 
     # ---- resume ---------------------------------------------------------------------------------------------------------------
     def _config(self):
-        return {"n": len(self.img_list), "batch_size": self.batch_size, "shuffle": bool(self.shuffle),
-                "multiscale": None if self.multiscale is None else list(self.multiscale), "dim_interval": self.dim_interval,
-                "aug": dict(self.aug)}
+        config = {"n": len(self.img_list), "batch_size": self.batch_size, "shuffle": bool(self.shuffle),
+                  "multiscale": None if self.multiscale is None else list(self.multiscale), "dim_interval": self.dim_interval,
+                  "aug": dict(self.aug)}
+        if self.extra:                                   # absent when off: a state written before the switch existed still loads
+            config["extra"] = True
+        return config
 
     def state_dict(self):
         """``{"seed", "epoch", "batch", "config"}``: ``epoch`` is the epoch of the iteration in progress and ``batch`` the number of
@@ -444,7 +453,7 @@ class TrainBatches:
         """One epoch's batches as ``(images, labels, params, dim)``, everything ``augment_batch`` takes, without touching a GPU.
         ``images[i]`` is None for a source that is resident in the arena (``params`` were drawn with its recorded shape); with
         ``decode="gpu"`` it is the undecoded `jpeg.Source` (``.shape`` from its header)."""
-        for _, images, labels, params, dim in self._host_batches():
+        for _, images, labels, params, dim, _ in self._host_batches():
             yield images, labels, params, dim
 
     def _host_batches(self):
@@ -485,8 +494,9 @@ class TrainBatches:
                         shapes.append(tuple(img.shape[:2]))
                     labels.append(rows)
                 params = sample_params(seeds[k * bs:k * bs + len(idx)], shapes=shapes, **self.aug)
+                programs = sample_extra(seeds[k * bs:k * bs + len(idx)], shapes) if self.extra else None
                 self._pos = (epoch, k + 1)
-                yield idx, images, labels, params, self.dim if dims is None else dims[k]
+                yield idx, images, labels, params, self.dim if dims is None else dims[k], programs
         finally:
             if pool is not None:
                 pool.shutdown(wait=True, cancel_futures=True)
@@ -518,7 +528,7 @@ class TrainBatches:
         """Enqueue the decode of a host batch's sources on the loader's stream: those the arena admits (in batch order, by the
         same rule and so at the same offsets as ``decode="pil"``) straight into it, the others into a buffer of the batch."""
         from . import jpeg
-        idx, images, labels, params, dim = batch
+        idx, images, labels, params, dim, _ = batch
         new = [i for i, im in enumerate(images) if im is not None]
         admitted, offsets = [], []
         if self.cache_bytes > 0 and new:
@@ -542,7 +552,7 @@ class TrainBatches:
 
     def _complete(self, launched):
         batch, admitted, jobs, pos = launched
-        idx, images, labels, params, dim = batch
+        idx, images, labels, params, dim, programs = batch
         out = list(images)
         for which, job in jobs:
             for i, view in zip(which, job.finish()):         # raises what read_image_rgb raises for a file nobody can decode
@@ -553,6 +563,8 @@ class TrainBatches:
             if out[i] is None:
                 out[i] = self._resident[j][0]
         self._pos = pos                                      # the host half runs one batch ahead: report the batch handed out
+        if programs is not None:
+            out = extra_augment_batch(out, programs)
         return augment_batch(out, labels, dim, params, self.max_labels)
 
     def _iter_gpu(self):
@@ -582,9 +594,11 @@ class TrainBatches:
     def _iter_pil(self):
         host = self._host_batches()
         try:
-            for idx, images, labels, params, dim in host:
+            for idx, images, labels, params, dim, programs in host:
                 if self.cache_bytes > 0:
                     images = self._admit(idx, images, labels)
+                if programs is not None:
+                    images = extra_augment_batch(images, programs)
                 yield augment_batch(images, labels, dim, params, self.max_labels)
         finally:
             host.close()                                 # joins the decode threads when the iterator is closed or dropped
