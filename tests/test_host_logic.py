@@ -30,6 +30,63 @@ def test_arch_accounting():
     assert abs(2 * arch.conv_macs_per_image(608) / 1e9 - 140.692) < 0.01    # GFLOP/img @608
 
 
+@pytest.mark.parametrize("num_class", [80, 100])
+def test_wiring_table_equals_the_restated_graph(num_class):
+    """arch.wiring, the package's one statement of the wiring, against tests/plan_ref.network_graph (written down from the reference's
+    wiring on its own), producer by producer, by name."""
+    from tests import plan_ref as pr
+    specs = arch.conv_specs(num_class)
+    wiring = arch.wiring(specs)
+    graph = pr.network_graph(num_class)
+    assert len(wiring) == len(graph) == 75
+
+    def name(j):
+        return None if j is None else specs[j].name
+    for i, (wr, node) in enumerate(zip(wiring, graph)):
+        assert specs[i].name == node.name
+        assert (pr.IMAGE if i == 0 else name(wr.x), name(wr.x2), name(wr.residual), wr.cin_up) == (node.x, node.x2, node.residual, node.cin_up), (i, wr, node)
+        assert all(j is None or j < i for j in (wr.x, wr.x2, wr.residual)), "a conv reads only earlier ones"
+    assert [(specs[i].name, wr.head) for i, wr in enumerate(wiring) if wr.head is not None] == [
+        ("pre_det1.mlist.6", 0), ("pre_det2.mlist.6", 1), ("pre_det3.mlist.6", 2)]
+    assert [i for i, wr in enumerate(wiring) if wr.residual is not None] == [i for i, sp in enumerate(specs) if sp.res2] and sum(sp.res2 for sp in specs) == 23
+    assert [(specs[i].name, wr.cin_up) for i, wr in enumerate(wiring) if wr.x2 is not None] == [("pre_det2.mlist.0", 256), ("pre_det3.mlist.0", 128)]
+
+
+# arch.conv_output_hw(size), written out: the 75 output sides (every picture is square), so that the values do not rest on the wiring table
+CONV_OUTPUT_SIDES = {
+    320: [320, 160, 160, 160, 80, 80, 80, 80, 80, 40, 40, 40, 40, 40, 40, 40, 40, 40, 40, 40, 40, 40, 40, 40, 40, 40, 20, 20, 20, 20, 20, 20, 20, 20, 20,
+          20, 20, 20, 20, 20, 20, 20, 20, 10, 10, 10, 10, 10, 10, 10, 10, 10, 10, 10, 10, 10, 10, 10, 10, 10, 20, 20, 20, 20, 20, 20, 20, 20, 40, 40,
+          40, 40, 40, 40, 40],
+    416: [416, 208, 208, 208, 104, 104, 104, 104, 104, 52, 52, 52, 52, 52, 52, 52, 52, 52, 52, 52, 52, 52, 52, 52, 52, 52, 26, 26, 26, 26, 26, 26, 26, 26,
+          26, 26, 26, 26, 26, 26, 26, 26, 26, 13, 13, 13, 13, 13, 13, 13, 13, 13, 13, 13, 13, 13, 13, 13, 13, 13, 26, 26, 26, 26, 26, 26, 26, 26, 52,
+          52, 52, 52, 52, 52, 52],
+    608: [608, 304, 304, 304, 152, 152, 152, 152, 152, 76, 76, 76, 76, 76, 76, 76, 76, 76, 76, 76, 76, 76, 76, 76, 76, 76, 38, 38, 38, 38, 38, 38, 38, 38,
+          38, 38, 38, 38, 38, 38, 38, 38, 38, 19, 19, 19, 19, 19, 19, 19, 19, 19, 19, 19, 19, 19, 19, 19, 19, 19, 38, 38, 38, 38, 38, 38, 38, 38, 76,
+          76, 76, 76, 76, 76, 76],
+}
+
+
+@pytest.mark.parametrize("size", [320, 416, 608])
+def test_conv_output_hw_keeps_its_values(size):
+    want = [(s, s) for s in CONV_OUTPUT_SIDES[size]]
+    assert len(want) == 75
+    assert arch.conv_output_hw(size) == want and arch.conv_output_hw(size, 100) == want
+    assert [g[2:] for g in arch.conv_hw(size, size)] == want
+
+
+def test_conv_hw_non_square():
+    """320 (H) x 480 (W): every conv's input and output picture.  Outputs: runs of equal size in stream order (backbone 1 + 3 + 5 + 17 + 17
+    + 9, pre_det1 and up1.conv 8, pre_det2 and up2.conv 8, pre_det3 7); a stride-2 conv reads twice its output, every other conv -- the two
+    joins, which read at their route's size, included -- a picture of its output's size."""
+    runs = ((320, 1), (160, 3), (80, 5), (40, 17), (20, 17), (10, 9 + 8), (20, 8), (40, 7))
+    out = [(h, h * 3 // 2) for h, n in runs for _ in range(n)]
+    geo = arch.conv_hw(320, 480)
+    assert len(out) == 75 and [g[2:] for g in geo] == out
+    assert [g[:2] for g in geo] == [(ho * sp.stride, wo * sp.stride) for sp, (ho, wo) in zip(arch.conv_specs(), out)]
+    assert geo[0] == (320, 480, 320, 480) and geo[1] == (320, 480, 160, 240) and geo[59] == (10, 15, 10, 15) and geo[60] == (20, 30, 20, 30)
+    assert arch.out_hw(13, 26, 3, 2) == (7, 13) and arch.out_hw(13, 26, 1, 1) == (13, 26)
+
+
 def test_state_dict_keys_match_reference(golden_dir):
     g = json.load(open(os.path.join(golden_dir, "weights_roundtrip.json")))
     net = YoloNet((416, 416))

@@ -50,7 +50,7 @@ def test_concat_folding_equals_scaling_each_half():
     q2, s2 = ir.quantize_weights(halves, np.ones(384, dtype=F32))
     assert np.array_equal(qw, q2) and np.array_equal(sw, s2)
     specs = arch.conv_specs(80)
-    g = engine.int8_graph(specs)
+    g = arch.wiring(specs)
     sc = {n: 0.01 * (k + 1) for k, n in enumerate(engine.int8_scale_names(specs))}
     for i, up, route in ((60, "up1.conv", "feature.mlist.23.conv2"), (68, "up2.conv", "feature.mlist.14.conv2")):
         s = engine.int8_input_scales(specs, g, sc, i)
@@ -234,7 +234,7 @@ def test_i8_selection_is_the_bf16_choice_for_the_layers_bytes():
     lib = _ffi.lib()
     specs = arch.conv_specs(80)
     hw = arch.conv_output_hw(416)
-    g = engine.int8_graph(specs)
+    g = arch.wiring(specs)
     n = 0
     for B in (1, 16, 64):
         for i in engine.int8_layers(specs):

@@ -1,10 +1,14 @@
 """Static description of the YOLOv3 / Darknet-53 convolution stack.
 
-One table drives everything that needs to agree on layer order and shapes:
-the darknet ``.weights`` stream order (reference ``darknet.py:292-303`` walks the
-module tree depth-first, which equals the darknet cfg order), the synthetic
-weight generator, the parameter containers in ``darknet.py`` and the HIP
-execution plan in ``engine.py``.
+Two tables drive everything that needs to agree on the network.  ``conv_specs``:
+layer order and shapes -- the darknet ``.weights`` stream order (reference
+``darknet.py:292-303`` walks the module tree depth-first, which equals the darknet
+cfg order), the synthetic weight generator, the parameter containers in
+``darknet.py``.  ``wiring``: which convolution reads, upsamples, concatenates and
+adds which output, and which three are heads -- the HIP execution plan and the I8
+scale folding in ``engine.py``, the training graph in ``backprop.py`` and the
+layer geometry (``conv_hw``) all read it; nothing else in the package walks the
+architecture.
 
 Reference architecture: ``darknet.py:72-81`` (backbone ``Darknet([1,2,8,8,4])``),
 ``darknet.py:107-120`` (``PreDetectionConvGroup``), ``darknet.py:153-162``
@@ -79,24 +83,64 @@ def conv_macs_per_image(size, num_class=80):
     return total
 
 
+# x        : index of the conv whose output this one reads (None: feature.mlist.0 reads the image)
+# x2       : only at the two joins (pre_det2.mlist.0, pre_det3.mlist.0), which read cat(nearest_up2x(x), x2): x is the up-conv, x2 the
+#            route (feature.mlist.23.conv2, feature.mlist.14.conv2); None everywhere else
+# cin_up   : at a join, the channels of the upsampled part (specs[x].cout); else 0
+# residual : index of the conv whose output the epilogue adds (the 23 res_layer conv2s); else None
+# head     : 0 / 1 / 2 on the three plain head convs; else None
+Wire = namedtuple("Wire", "x x2 cin_up residual head")
+_wiring = None
+
+
+def wiring(specs):
+    """One Wire per convolution of ``specs`` (``conv_specs`` order): the network's wiring (reference darknet.py:72-88 backbone with
+    x + conv2(conv1(x)), :107-120 detection branches, :179-194 upsample + concat).  No field depends on the class count, so the table
+    is built once."""
+    global _wiring
+    if _wiring is None:
+        wires = [Wire(None, None, 0, None, None)]
+
+        def add(x, x2=None, residual=None, head=None):
+            wires.append(Wire(x, x2, specs[x].cout if x2 is not None else 0, residual, head))
+            return len(wires) - 1
+
+        x, routes = 0, []
+        for nblk in BACKBONE_BLOCKS:
+            x = add(x)                                  # stride-2 3x3
+            for _ in range(nblk):
+                x = add(add(x), residual=x)             # x + conv2(conv1(x)), :53
+            routes.append(x)
+        for head, route in enumerate((None, routes[3], routes[2])):      # mlist[23] 26x26x512, mlist[14] 52x52x256 (:180-181)
+            if route is not None:
+                x = add(x)                              # upK.conv reads the fifth conv of the branch before (addCachedOut(-3), :185)
+            x = add(x, route)
+            for _ in range(4):
+                x = add(x)
+            add(add(x), head=head)
+        assert len(wires) == len(specs) == 75
+        _wiring = tuple(wires)
+    return _wiring
+
+
+def out_hw(h, w, k, stride):
+    pad = (k - 1) // 2
+    return (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+
+
+def conv_hw(H, W):
+    """(h, w, ho, wo) of every conv in ``conv_specs`` order for an H x W image: the picture it reads and the one it writes.  A join
+    reads at its route's size (the up-conv's output is upsampled to it)."""
+    specs = conv_specs()
+    geo = []
+    for sp, wr in zip(specs, wiring(specs)):
+        src = wr.x if wr.x2 is None else wr.x2
+        h, w = (H, W) if src is None else geo[src][2:]
+        geo.append((h, w) + out_hw(h, w, sp.k, sp.stride))
+    return geo
+
+
 def conv_output_hw(size, num_class=80):
     """Output (H, W) of every conv in ``conv_specs`` order for a square input."""
-    out = []
-    specs = conv_specs(num_class)
-    s = size
-    # backbone
-    i = 0
-    for sp in specs[:52]:
-        if sp.stride == 2:
-            s = (s + 2 * 1 - 3) // 2 + 1
-        out.append((s, s))
-        i += 1
-    g1 = s
-    out += [(g1, g1)] * 7          # pre_det1
-    out.append((g1, g1))           # up1.conv (before the x2 upsample)
-    g2 = g1 * 2
-    out += [(g2, g2)] * 7          # pre_det2
-    out.append((g2, g2))           # up2.conv
-    g3 = g2 * 2
-    out += [(g3, g3)] * 7          # pre_det3
-    return out
+    return [g[2:] for g in conv_hw(size, size)]
+

@@ -37,13 +37,14 @@ of the Function.
 52 of a frozen ``net.feature.eval()`` -- on the inference engine instead: a prefix engine (engine.Engine with n_conv) in the exact F32
 plan for F32 and in the BF16 plan for BF16 / BF16_ACT, whose outputs are copied into the run's buffers where a later op reads them
 (``_prefix``).  Everything from the first trainable or train-mode op on, the walk included, is as without the switch."""
+import functools
 import numbers
 from collections import namedtuple
 
 import torch
 import torch.nn as nn
 
-from . import _ffi
+from . import _ffi, arch
 from . import engine as _engine
 from . import yololayer as _yl
 
@@ -61,37 +62,38 @@ class _Op:
         self.bn = None if self.head else module.bn
 
 
+def _buffer(sp):
+    """The run's name for the output of the conv of spec sp: feature.mlist.<pos>[.conv2] -> f<pos> (.conv1: f<pos>a), upK.conv -> upK,
+    pre_detK.mlist.<i> -> pre_detK.<i> (the head conv: pre_detK.logits).  The input image is "x"."""
+    part = sp.name.split(".")
+    if part[0] == "feature":
+        return "f" + part[2] + ("a" if part[-1] == "conv1" else "")
+    if not sp.bn:
+        return part[0] + ".logits"
+    return part[0] if part[-1] == "conv" else "%s.%s" % (part[0], part[2])
+
+
+@functools.lru_cache(maxsize=1)
+def _ops():
+    """Per conv of arch.wiring: (the module's path from the net, _Op's arguments after the module); the same for every net."""
+    specs = arch.conv_specs()
+    out = []
+    for sp, wr in zip(specs, arch.wiring(specs)):
+        x, x2, res = (None if j is None else _buffer(specs[j]) for j in (wr.x, wr.x2, wr.residual))
+        x = x or "x"
+        src, src2 = (x, None) if x2 is None else (x2, x)      # _Op.src is the full-resolution input: at a join the route, Wire.x2
+        out.append((sp.name.split("."), (src, _buffer(sp), res, src2, wr.cin_up, wr.head)))
+    return out
+
+
 def graph(net):
-    """The net as a list of _Op in execution order (reference darknet.py:198-231)."""
-    from .darknet import res_layer
+    """The net as a list of _Op in execution order (arch.wiring; reference darknet.py:198-231)."""
     ops = []
-    feat = net.feature.mlist
-    ops.append(_Op(feat[0], "x", "f0"))
-    cur = "f0"
-    for pos in range(1, len(feat)):
-        m = feat[pos]
-        if isinstance(m, res_layer):
-            ops.append(_Op(m.conv1, cur, "f%da" % pos))
-            ops.append(_Op(m.conv2, "f%da" % pos, "f%d" % pos, res=cur))
-        else:
-            ops.append(_Op(m, cur, "f%d" % pos))
-        cur = "f%d" % pos
-    r61, r36 = "f%d" % net.feature.map2yolocfg[61], "f%d" % net.feature.map2yolocfg[36]
-
-    def predet(group, name, src, k, src2=None, cin_up=0):
-        prev = src
-        for i, m in enumerate(group.mlist[:-1]):
-            out = "%s.%d" % (name, i)
-            ops.append(_Op(m, prev, out, src2=src2 if i == 0 else None, cin_up=cin_up if i == 0 else 0))
-            prev = out
-        ops.append(_Op(group.mlist[-1], prev, "%s.logits" % name, head_idx=k))
-        return "%s.%d" % (name, group.getIdxFromYoloIdx(-3))
-
-    h1 = predet(net.pre_det1, "pre_det1", cur, 0)
-    ops.append(_Op(net.up1.conv, h1, "up1"))
-    h2 = predet(net.pre_det2, "pre_det2", r61, 1, src2="up1", cin_up=net.up1.conv.conv.out_channels)
-    ops.append(_Op(net.up2.conv, h2, "up2"))
-    predet(net.pre_det3, "pre_det3", r36, 2, src2="up2", cin_up=net.up2.conv.conv.out_channels)
+    for path, args in _ops():
+        m = net
+        for part in path:                # (straight from the modules' dicts: nn.Module.__getattr__ and get_submodule are slow)
+            m = m._modules[part]
+        ops.append(_Op(m, *args))
     return ops
 
 

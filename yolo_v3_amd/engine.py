@@ -22,6 +22,7 @@ import torch
 from . import _ffi, arch
 
 from ._ffi import ConvDesc, F32, BF16, F32X3, F32H2, F16, I8, ACT_LEAKY, ACT_LINEAR
+from .arch import out_hw
 
 _TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F32X3: torch.bfloat16, F32H2: torch.float16, F16: torch.float16, I8: torch.int8}   # element type of activation storage
 PLANES = {F32: 0, BF16: 1, F32X3: 3, F32H2: 2, F16: 1, I8: 1}   # 0: plain fp32 NHWC tensor; n > 0: n planes [n][B,H,W,C] (16-bit; I8: one plane of bytes)
@@ -115,7 +116,7 @@ WINO_MIN_CIN = int(measure_env("YV3_WINO_MIN_CIN", "256") or 256)     # Winograd
 _WINO_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
 
 
-SK_AUTO_CELLS = int(measure_env("YV3_SK_AUTO_CELLS", "1536") or 1536)     # stream-K by default up to this many 32x32 cells per batch (Plan.__init__)
+SK_AUTO_CELLS = int(measure_env("YV3_SK_AUTO_CELLS", "1536") or 1536)     # stream-K by default up to this many 32x32 cells per batch (Plan._scratch)
 
 
 WINO_MIN_CIN_F32 = 64  # exact-fp32 mode: fp32 MFMA runs at the vector rate, every 3x3 layer is matrix-bound -> from the 104x104 layers down
@@ -181,39 +182,6 @@ def pack_wino4(weight_f32, spec):
 I8_FIRST = 4          # convolutions 0-3 (the fused front and res64 launches) and the three head convs stay BF16 launches
 
 
-def int8_graph(specs):
-    """{conv index: (source conv, route conv or None, cin_up, residual conv or None)} of all 75 convolutions by the architecture
-    (the walk of Plan.__init__): whose output a convolution reads -- for the two upsample + concat layers the upsampled source and
-    the route whose channels follow its cin_up -- and which tensor its epilogue adds."""
-    g, i, cur, routes = {0: (None, None, 0, None)}, 1, 0, {}
-    for stage, nblk in enumerate(arch.BACKBONE_BLOCKS):
-        g[i] = (cur, None, 0, None); cur = i; i += 1
-        for _ in range(nblk):
-            g[i] = (cur, None, 0, None)
-            g[i + 1] = (i, None, 0, cur)
-            cur = i + 1; i += 2
-        routes[stage] = cur
-
-    def branch(x, x2=None):
-        nonlocal i
-        cu = specs[x].cout if x2 is not None else 0
-        route = None
-        for j in range(7):
-            g[i] = (x, x2, cu, None) if (j == 0 and x2 is not None) else (x, None, 0, None)
-            x = i; i += 1
-            if j == 4:
-                route = x
-        return route
-
-    h1 = branch(cur)
-    g[i] = (h1, None, 0, None); u1 = i; i += 1
-    h2 = branch(u1, routes[3])
-    g[i] = (h2, None, 0, None); u2 = i; i += 1
-    branch(u2, routes[2])
-    assert i == len(specs)
-    return g
-
-
 def int8_layers(specs):
     """Indices of the convolutions that run in int8: every conv_bn_relu from I8_FIRST on (68)."""
     return [i for i, sp in enumerate(specs) if i >= I8_FIRST and sp.bn]
@@ -239,13 +207,13 @@ def int8_scales_checked(net, specs):
     return out
 
 
-def int8_input_scales(specs, graph, scales, i):
+def int8_input_scales(specs, wiring, scales, i):
     """s_in(ci) of int8 layer i, fp32 [cin]: the source tensor's scale -- behind an upsample + concat the first cin_up channels carry the
-    upsampled tensor's and the rest the route's."""
-    src, src2, cu, _ = graph[i]
-    s_in = np.full(specs[i].cin, scales[specs[src].name], dtype=np.float32)
-    if src2 is not None:
-        s_in[cu:] = np.float32(scales[specs[src2].name])
+    upsampled tensor's and the rest the route's (wiring: arch.wiring)."""
+    wr = wiring[i]
+    s_in = np.full(specs[i].cin, scales[specs[wr.x].name], dtype=np.float32)
+    if wr.x2 is not None:
+        s_in[wr.cin_up:] = np.float32(scales[specs[wr.x2].name])
     return s_in
 
 
@@ -410,11 +378,6 @@ def make_desc(pc, x, y, B, H, W, residual=None, x2=None, cin_up=0, dtype=F32, ou
     return d
 
 
-def out_hw(h, w, k, stride):
-    pad = (k - 1) // 2
-    return (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
-
-
 class Plan:
     """Buffers + kernel descriptors for one (B, H, W).  A plan of a prefix engine (``engine.n_conv`` < 75) holds the buffers and
     launches of the first n_conv convolutions only, its head convs in the ``logits=True`` form: no detections, no decode."""
@@ -433,13 +396,25 @@ class Plan:
         if H % 32 or W % 32:
             raise _ffi.Yv3Error("input height/width must be multiples of 32 (got %dx%d)" % (H, W))
         self.B, self.H, self.W = B, H, W
-        dev, dt = engine.device, engine.dtype
-        packed, specs, n_conv = engine.packed, engine.all_specs, engine.n_conv
-        logits = bool(logits or n_conv < len(specs))
-        nc = engine.num_class
-        attrib = 5 + nc
-        keep = []            # every buffer the descriptors point to
-        descs = []
+        dt, i8 = engine.dtype, engine.dtype == I8
+        logits = bool(logits or engine.n_conv < len(engine.all_specs))
+        # the YOLO decode is fused into the three head convs' epilogue (plane kernels): their logits are then not
+        # materialised and the descriptors' dec_out is pointed at the caller's detections tensor before each launch
+        self.fused_decode = bool(engine.fuse_decode and dt != F32 and not logits)
+        # feature.mlist.0 + feature.mlist.1 run as ONE launch (csrc/conv_front.hip; exact fp32: csrc/conv_front_f32.hip); the first
+        # layer's [B,H,W,32] activation is then never written (conv0_out stays allocated for the un-fused / layer-by-layer paths)
+        self.fused_front = bool(i8 or (engine.fuse_front and dt in (F32H2, BF16, F32, F16)))      # (I8: the front is always the two fused BF16 launches)
+        # ... and the first residual block (feature.mlist.2: 1x1 64->32 + 3x3 32->64 + add) as one more (csrc/conv_res64.hip,
+        # csrc/conv_res64_f32.hip)
+        self.fused_res64 = bool(i8 or (self.fused_front and engine.fuse_res64))
+        self.first_desc = 3 if self.fused_res64 else (1 if self.fused_front else 0)
+        self._scratch(engine, flags, two_lanes)
+        self._launches(engine, two_lanes)
+        self._decode_params(engine)
+
+    def _scratch(self, engine, flags, two_lanes):
+        """The status word and the two scratch buffers the launches share."""
+        B, H, W, dev, dt = self.B, self.H, self.W, engine.device, engine.dtype
         # sticky status word written by the kernels (bit 0: an fp16-plane output was saturated) + its host mirror
         self.flags = flags if flags is not None else torch.zeros(1, device=dev, dtype=torch.int32)   # (lanes of one Detector share one)
         self.flags_host = torch.zeros(1, dtype=torch.int32).pin_memory()
@@ -452,7 +427,6 @@ class Plan:
         use_sk = engine.stream_k if engine.stream_k is not None else (cells <= SK_AUTO_CELLS and not two_lanes)
         self.workspace = (torch.zeros(_ffi.lib().yv3_conv_workspace_bytes(), device=dev, dtype=torch.uint8)
                           if (dt == F32H2 and use_sk) else None)
-        self.layer_out = {}  # conv name -> (buffer, (h, w, c)) for bring-up / per-layer parity tests
         # Winograd scratch (the transformed input of ONE layer at a time; launches of a plan are stream-ordered): sized for
         # the largest eligible layer of this plan
         self.wino_ws = None
@@ -465,120 +439,75 @@ class Plan:
                 need = max(need, max(_ffi.lib().yv3_wino4_workspace_bytes(B, H // f, W // f, c) for c, f in ((64, 4), (128, 8), (256, 16), (512, 32))))
             self.wino_ws = torch.zeros(need, device=dev, dtype=torch.uint8)       # (zero-filled: hand-over flags of the even schedule)
 
+    def _launches(self, engine, two_lanes):
+        """One output buffer and one descriptor (batch_split: two) per convolution 1 .. n_conv - 1, in arch.wiring's order."""
+        B, H, W, dev, dt = self.B, self.H, self.W, engine.device, engine.dtype
+        packed, specs, n_conv = engine.packed, engine.all_specs, engine.n_conv
+        wiring, hw = arch.wiring(specs), arch.conv_hw(H, W)
         # I8: a mixed plan -- convolutions 0-3 and the heads are BF16 launches on bf16 planes, the 68 between them int8 launches on int8
-        # tensors (ldt: a layer's launch dtype); the front's output is quantised once (front_q), each head reads the integers of the
-        # layer before it, written as bf16 by that layer's epilogue
+        # tensors (ld: a layer's launch dtype); the front's output is quantised once (front_q), each head reads the integers of the
+        # layer before it, written as one bf16 plane by that layer's epilogue
         i8 = dt == I8
         act_dt = BF16 if i8 else dt
-        i8_scales = engine.int8_scales if i8 else None
-        i8_graph = int8_graph(specs) if i8 else None
-
-        def ldt(i):
-            return I8 if (i8 and i >= I8_FIRST and specs[i].bn) else act_dt
-
-        def buf(h, w, c, dtype=act_dt):
-            t = alloc_act(B, h, w, c, dtype, dev)
-            keep.append(t)
-            return t
-
-        # the YOLO decode is fused into the three head convs' epilogue (plane kernels): their logits are then not
-        # materialised and the descriptors' dec_out is pointed at the caller's detections tensor before each launch
-        self.fused_decode = bool(engine.fuse_decode and dt != F32 and not logits)
-        self.head_descs = []     # (descriptor index, ho, wo)
-        self.desc_spec = []      # descriptor index -> index into arch.conv_specs (a layer may run as two launches: batch_split)
+        scales = engine.int8_scales if i8 else None
+        feeds_head = {wr.x for wr in wiring if wr.head is not None}
         ncu = torch.cuda.get_device_properties(dev).multi_processor_count
         ncu = ncu & ~7 if ncu >= 8 else 256
-        # feature.mlist.0 + feature.mlist.1 run as ONE launch (csrc/conv_front.hip; exact fp32: csrc/conv_front_f32.hip); the first
-        # layer's [B,H,W,32] activation is then never written (conv0_out stays allocated for the un-fused / layer-by-layer paths)
-        self.fused_front = bool(i8 or (engine.fuse_front and dt in (F32H2, BF16, F32, F16)))      # (I8: the front is always the two fused BF16 launches)
-        # ... and the first residual block (feature.mlist.2: 1x1 64->32 + 3x3 32->64 + add) as one more (csrc/conv_res64.hip,
-        # csrc/conv_res64_f32.hip)
-        self.fused_res64 = bool(i8 or (self.fused_front and engine.fuse_res64))
-        self.front_q = buf(H // 2, W // 2, specs[I8_FIRST - 1].cout, I8) if i8 else None
-        self.front_inv_s = float(np.float32(1.0) / np.float32(i8_scales[specs[I8_FIRST - 1].name])) if i8 else 0.0
-        self.first_desc = 3 if self.fused_res64 else (1 if self.fused_front else 0)
+        keep, descs = [], []     # every buffer the descriptors point to; the descriptors
 
-        def conv(i, x, h, w, residual=None, x2=None, cin_up=0, out_dtype=None):
-            ho, wo = out_hw(h, w, specs[i].k, specs[i].stride)
-            if i >= n_conv:           # past a prefix engine's last convolution: the geometry only
-                return None, ho, wo
-            pc = packed[i]
-            head = out_dtype == F32 and dt != F32
-            ld = ldt(i)
+        def buf(h, w, c, dtype):
+            keep.append(alloc_act(B, h, w, c, dtype, dev))
+            return keep[-1]
+
+        self.head_descs = []     # (descriptor index, ho, wo)
+        self.desc_spec = []      # descriptor index -> index into arch.conv_specs (a layer may run as two launches: batch_split)
+        self.front_q = buf(H // 2, W // 2, specs[I8_FIRST - 1].cout, I8) if i8 else None
+        self.front_inv_s = float(np.float32(1.0) / np.float32(scales[specs[I8_FIRST - 1].name])) if i8 else 0.0
+        self.conv0_out = buf(H, W, specs[0].cout, act_dt)
+        self.layer_out = {specs[0].name: self.conv0_out}     # conv name -> its output buffer, for bring-up / per-layer parity tests
+        out = [self.conv0_out] + [None] * (len(specs) - 1)   # ... by conv index; None: not written (fused-decode head, past a prefix's n_conv)
+        for i in range(1, n_conv):
+            wr, pc, (h, w, ho, wo) = wiring[i], packed[i], hw[i]
+            sp = pc.spec
+            ld = I8 if (i8 and i >= I8_FIRST and sp.bn) else act_dt
+            out_dtype = F32 if wr.head is not None else BF16 if (i8 and i in feeds_head) else None
+            head = wr.head is not None and dt != F32              # a plane-kernel head: where the decode can be fused
+            x = self.front_q if (i8 and i == I8_FIRST) else out[wr.x]
+            x2, residual = (out[j] if j is not None else None for j in (wr.x2, wr.residual))
             s_res = inv_s_out = 0.0
             if ld == I8:
-                if i == I8_FIRST:
-                    x = self.front_q
-                inv_s_out = float(np.float32(1.0) / np.float32(i8_scales[pc.spec.name]))
-                if residual is not None:
-                    s_res = i8_scales[specs[i8_graph[i][3]].name]
-            y = None if (head and self.fused_decode) else buf(ho, wo, pc.spec.cout, ld if out_dtype is None else out_dtype)
+                inv_s_out = float(np.float32(1.0) / np.float32(scales[sp.name]))
+                if wr.residual is not None:
+                    s_res = scales[specs[wr.residual].name]
+            y = None if (head and self.fused_decode) else buf(ho, wo, sp.cout, ld if out_dtype is None else out_dtype)
             if head:
                 self.head_descs.append((len(descs), ho, wo))
             split = None
-            if engine.batch_split and dt == F32H2 and pc.spec.k == 3 and not head and self.workspace is None:
+            if engine.batch_split and dt == F32H2 and sp.k == 3 and not head and self.workspace is None:
                 split = batch_split(B, ho, wo, pc.cout_pad, ncu)
             for part in ([None] if split is None else [(0, split[0]), (split[0], split[1])]):
-                descs.append(make_desc(pc, x, y, B, h, w, residual, x2, cin_up, ld, out_dtype, self.flags, self.workspace, batch=part,
+                descs.append(make_desc(pc, x, y, B, h, w, residual, x2, wr.cin_up, ld, out_dtype, self.flags, self.workspace, batch=part,
                                        wino_ws=self.wino_ws, two_lanes=two_lanes, wino_always=engine.wino_always,
                                        wino4_tiles=engine.stream_k is False, s_res=s_res, inv_s_out=inv_s_out))
                 self.desc_spec.append(i)
             if y is not None:
-                self.layer_out[pc.spec.name] = y
-            return y, ho, wo
-
-        # ---- backbone (reference darknet.py:72-88)
-        self.conv0_out = buf(H, W, 32)
-        self.layer_out["feature.mlist.0"] = self.conv0_out
-        cur, h, w = self.conv0_out, H, W
-        i = 1
-        routes = {}
-        for stage, nblk in enumerate(arch.BACKBONE_BLOCKS):
-            cur, h, w = conv(i, cur, h, w); i += 1
-            for _ in range(nblk):
-                mid, _, _ = conv(i, cur, h, w); i += 1
-                cur, _, _ = conv(i, mid, h, w, residual=cur); i += 1          # x + conv2(conv1(x)), :53
-            routes[stage] = (cur, h, w)
-        r36, r61 = routes[2], routes[3]        # mlist[14] 52x52x256, mlist[23] 26x26x512 (:180-181)
-
-        # ---- detection branches (darknet.py:204-223)
-        self.logits = []
-
-        def branch(x, h, w, x2=None, cin_up=0):
-            nonlocal i
-            route = None
-            for j in range(6):
-                if j == 0 and x2 is not None:
-                    x, _, _ = conv(i, x, h, w, x2=x2, cin_up=cin_up)
-                elif j == 5 and i8:
-                    x, _, _ = conv(i, x, h, w, out_dtype=BF16)                 # the head's input: the same integers as one bf16 plane
-                else:
-                    x, _, _ = conv(i, x, h, w)
-                i += 1
-                if j == 4:
-                    route = x                                                   # addCachedOut(-3), :185
-            lg, _, _ = conv(i, x, h, w, out_dtype=F32); i += 1
-            self.logits.append((lg, h, w))
-            return route
-
-        h1 = branch(cur, h, w)
-        u1, _, _ = conv(i, h1, h, w); i += 1                                      # up1.conv (13x13)
-        t61, h61, w61 = r61
-        h2 = branch(u1, h61, w61, x2=t61, cin_up=specs[i - 1].cout)         # nearest x2 + cat fused
-        u2, _, _ = conv(i, h2, h61, w61); i += 1                                  # up2.conv (26x26)
-        t36, h36, w36 = r36
-        branch(u2, h36, w36, x2=t36, cin_up=specs[i - 1].cout)
-        assert i == len(specs) == 75 and len(packed) == n_conv and self.desc_spec[:3] == [1, 2, 3]
-
+                self.layer_out[sp.name] = out[i] = y
+        # Engine.run_front takes the outputs of convolutions 1 and 3 from descriptors 0 and 2
+        assert len(packed) == n_conv and self.desc_spec[:3] == [1, 2, 3]
+        self.logits = [(out[i], hw[i][2], hw[i][3]) for i, wr in enumerate(wiring) if wr.head is not None]
         self._keep = keep
         self.n_desc = len(descs)
         self.descs = (ConvDesc * len(descs))(*descs)
+
+    def _decode_params(self, engine):
+        """Rows per head and in all; for a whole-network plan the three decodes' parameters, written into the head descriptors where
+        the decode is fused."""
         self.rows = [hh * ww * 3 for (_, hh, ww) in self.logits]
         self.N = sum(self.rows)
-        self.attrib = attrib
+        self.attrib = 5 + engine.num_class
         self._dets_ptr = None
         self.decode_args = []
-        if n_conv < len(specs):
+        if engine.n_conv < len(engine.all_specs):
             return
         # decode parameters (yololayer.py:36-38): stride = H_img / nH, anchors by mask
         anchors = engine.anchors
@@ -587,7 +516,7 @@ class Plan:
             flat = []
             for m in mask:
                 flat += [float(anchors[2 * m]), float(anchors[2 * m + 1])]
-            self.decode_args.append(((ctypes.c_float * 6)(*flat), float(H) / hh, row0, lg, hh, ww))
+            self.decode_args.append(((ctypes.c_float * 6)(*flat), float(self.H) / hh, row0, lg, hh, ww))
             row0 += hh * ww * 3
         if self.fused_decode:
             for (di, ho, wo), (anc, stride, r0, _, _, _) in zip(self.head_descs, self.decode_args):
@@ -595,7 +524,7 @@ class Plan:
                 d.dec_stride = stride
                 for k in range(6):
                     d.dec_anchors[k] = anc[k]
-                d.dec_out_batch_stride = self.N * attrib
+                d.dec_out_batch_stride = self.N * self.attrib
 
     def bind_detections(self, dets):
         """Point the fused head convs at `dets` ([B, N, 5+C] fp32, contiguous)."""
@@ -800,15 +729,15 @@ class Engine:
         with torch.cuda.device(self.device):
             if self.dtype == I8:
                 sc = self.int8_scales = int8_scales_checked(self.net, self.all_specs)
-                g = int8_graph(self.all_specs)
+                wiring = arch.wiring(self.all_specs)
 
                 def pack(i, sp):
                     mod = self.net.get_submodule(sp.name)
                     if i < I8_FIRST:
                         return pack_conv(mod, sp, BF16)
                     if not sp.bn:
-                        return pack_conv(mod, sp, BF16, head_scale=sc[self.all_specs[g[i][0]].name])
-                    return pack_conv(mod, sp, I8, s_in=int8_input_scales(self.all_specs, g, sc, i))
+                        return pack_conv(mod, sp, BF16, head_scale=sc[self.all_specs[wiring[i].x].name])
+                    return pack_conv(mod, sp, I8, s_in=int8_input_scales(self.all_specs, wiring, sc, i))
                 self.packed = [pack(i, sp) for i, sp in enumerate(self.specs)]
             else:
                 self.packed = [pack_conv(self.net.get_submodule(sp.name), sp, self.dtype, self.winograd, self.winograd4) for sp in self.specs]
