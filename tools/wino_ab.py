@@ -8,8 +8,8 @@ from yolo_v3_amd.darknet import conv_bn_relu
 LAYERS = {"c26": (256, 512, 26), "c13": (512, 1024, 13), "c38": (256, 512, 38), "c19": (512, 1024, 19), "c52": (128, 256, 52), "c76": (128, 256, 76)}
 B = int(os.environ.get("BB", "64"))
 iters = int(os.environ.get("ITERS", "20"))
-engine.WINO_MIN_CIN = 128
 dt = _ffi.F32H2
+engine.MODES[dt] = engine.MODES[dt]._replace(wino_min_cin=128)
 torch.cuda.set_device(0)
 lib = _ffi.lib(); st = _ffi.stream_ptr()
 for name in sys.argv[1:] or ["c26", "c13"]:

@@ -273,16 +273,8 @@ class YoloNet(nn.Module):
         self.yolo3 = YoloLayer(pairs, list(arch.ANCHOR_MASKS[2]), img_dim, numClass)
 
         self._engines = {}
-        # Convolution math mode (include/yv3.h).  All three fp32 modes meet the 1e-4 parity bar against the
-        # reference (tests/test_gpu_e2e.py):
-        #   F32H2 (default) fp16 hi+lo planes, 3 fp16 MFMAs per fp32 product   -- fastest; activations must stay
-        #                   within +-65504 (checked: a saturated value raises Yv3Error instead of passing silently)
-        #   F32X3           exact 3-way bf16 split, 6 bf16 MFMAs per product   -- fp32 exponent range, ~1.6x slower
-        #   F32             exact fp32 MFMA                                    -- ~2.7x slower
-        # _ffi.BF16 and _ffi.F16 are the reduced-precision throughput modes (not 1e-4 modes): one 16-bit plane, the same kernels and
-        # cost; F16 keeps 11 significant bits instead of 8 and needs activations within +-65504 (else it re-runs in BF16, once).
-        # _ffi.I8 is post-training quantisation: int8 activations (one scale per tensor, from calibrate_int8) and weights on the int8 matrix
-        # cores for the 68 conv_bn_relu layers behind the front; the front and the heads stay BF16 launches.  Inference only.
+        # Convolution math mode (include/yv3.h): one of the six codes of engine.MODES, which states what each mode is.  F32H2, F32X3 and
+        # F32 meet the 1e-4 parity bar against the reference (tests/test_gpu_e2e.py); BF16, F16 and I8 are reduced-precision modes.
         self.math_mode = DEFAULT_MATH_MODE
         # {conv name: activation scale} of math mode I8 (calibrate_int8, or a saved dict): a plain attribute -- pickled and deep-copied with
         # the net, not a state_dict key
@@ -302,7 +294,7 @@ class YoloNet(nn.Module):
         self._prefix_engines = {}
 
     def __setattr__(self, name, value):
-        if name == "math_mode" and value == _ffi.I8 and not isinstance(value, bool):
+        if name == "math_mode" and getattr(_engine.mode_of(value), "mixed", False):
             _engine.int8_scales_checked(self, arch.conv_specs(self.numClass))      # Yv3Error: calibrate first
         super().__setattr__(name, value)
 

@@ -27,7 +27,7 @@ from collections import OrderedDict
 import torch
 
 from . import _ffi
-from .engine import Plan
+from .engine import MODES, Plan
 from .utils import PostProcessor, boxes_to_list
 
 
@@ -273,8 +273,7 @@ TWO_LANES_MIN_PIXELS = 40 * 416 * 416
 # ... per math mode (images of 416 x 416; same measurement, profiles/r05ai_two_lanes_threshold_check.txt): the default fp16-plane mode and the
 # bf16x3 mode cross over at 40 (f32x3 bs=40 +5 %); exact fp32 at ~52 (bs=48 -0.9 %, bs=56 +2.4 %, bs=64 +6.2 %); BF16 only beyond ~112
 # (bs=64 ONE lane +6.8 %, bs=96 / 112 equal, bs=128 two lanes +3.5 %; 608x608 bs=32 one lane +6 %)
-# (F16: BF16's value -- the same kernels and bytes -- not a measurement of its own; I8: BF16's value too, two-lane tuning for int8 is not done)
-TWO_LANES_MIN_IMAGES_416 = {_ffi.F32H2: 40, _ffi.F32X3: 40, _ffi.F32: 52, _ffi.BF16: 120, _ffi.F16: 120, _ffi.I8: 120}
+TWO_LANES_MIN_IMAGES_416 = {c: m.two_lanes_416 for c, m in MODES.items()}
 
 
 def two_lanes_min_pixels(dtype):

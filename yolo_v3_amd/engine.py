@@ -14,7 +14,9 @@ tensors.  Here the whole network is a static plan:
   row order equals the reference's ``torch.cat((det1, det2, det3), 1)``.
 """
 import ctypes
+import numbers
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -24,8 +26,79 @@ from . import _ffi, arch
 from ._ffi import ConvDesc, F32, BF16, F32X3, F32H2, F16, I8, ACT_LEAKY, ACT_LINEAR
 from .arch import out_hw
 
-_TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F32X3: torch.bfloat16, F32H2: torch.float16, F16: torch.float16, I8: torch.int8}   # element type of activation storage
-PLANES = {F32: 0, BF16: 1, F32X3: 3, F32H2: 2, F16: 1, I8: 1}   # 0: plain fp32 NHWC tensor; n > 0: n planes [n][B,H,W,C] (16-bit; I8: one plane of bytes)
+
+def measure_env(name, default=None):
+    """Tuning / A-B overrides from the environment are honoured ONLY in measurement sessions (YV3_MEASURE=1, set by tools/gpu.sh): in
+    normal use a stray YV3_* variable changes nothing -- kernel selection is a function of the descriptor, the product knobs are
+    attributes of the net (net.math_mode, .stream_k, .winograd, .deterministic, .lanes, ...)."""
+    if os.environ.get("YV3_MEASURE") != "1":
+        return default
+    return os.environ.get(name, default)
+
+
+WINO_MIN_CIN = int(measure_env("YV3_WINO_MIN_CIN", "256") or 256)     # Winograd F(2x2,3x3) for 3x3 / stride-1 layers with at least this many input channels (26x26 and 13x13 at
+                       # 416x416): below, the transformed input (16 B per input element through HBM) costs more than the MFMAs saved
+WINO_MIN_CIN_F32 = 64  # exact-fp32 mode: fp32 MFMA runs at the vector rate, every 3x3 layer is matrix-bound -> from the 104x104 layers down
+
+# What one inference math mode (net.math_mode, include/yv3.h) fixes; the code below and detect.py read it.  storage, planes: an activation
+# buffer's element type and layout (0: plain fp32 NHWC, n: n planes [n][B,H,W,C]).  launch: the mode its front, head and activation
+# buffers run in; mixed: a plan of such launches around int8 ones, which needs net.int8_scales and covers the whole network only.  split,
+# merge: entry points fp32 NHWC -> planes and back (None beside planes > 0: there is no conversion).  Packing: row_scale, a power-of-two
+# scale per output channel; pad128, cout_pad above 128 is a multiple of 128 (the plane kernels' channel tile); wino_min_cin, Winograd
+# F(2x2,3x3) from this many input channels (None: never), wino_cout128: for a cout that is a multiple of 128 only, wino4: with F(4x4,3x3)
+# filter images beside it.  Plans: front, res64, the fused front's two entry points (None: no fused front), front_optional: net.fuse_front
+# and .fuse_res64 apply; head_decode: head convs can decode in their epilogue; stream_k, batch_split: the stream-K workspace and
+# net.batch_split apply.  Status: always_status, every forward has a status word to check (Engine.checks_status); overflow_msg,
+# RangeOverflow's text; fallback, the mode that takes over after one, fallback_text: what that is and how to ask for it, for the warning.
+# two_lanes_416: `Detector` runs two lanes from this many images of 416 x 416 (the measurements: detect.TWO_LANES_MIN_PIXELS).
+Mode = namedtuple("Mode", "name storage planes launch mixed split merge row_scale pad128 wino_min_cin wino_cout128 wino4 front res64 "
+                          "front_optional head_decode stream_k batch_split always_status overflow_msg fallback fallback_text two_lanes_416")
+MODES = {F32H2: Mode(
+    name="F32H2", storage=torch.float16, planes=2, launch=F32H2, mixed=False, split="yv3_split_planes", merge="yv3_merge_planes",
+    row_scale=True, pad128=True, wino_min_cin=WINO_MIN_CIN, wino_cout128=False, wino4=False, front="yv3_conv_front",
+    res64="yv3_res_block64", front_optional=True, head_decode=True, stream_k=True, batch_split=True, always_status=True,
+    overflow_msg=("an activation exceeded the fp16 range (|v| > 65504) and was saturated: math mode F32H2 cannot "
+                  "represent this network/input; set net.math_mode = yolo_v3_amd.F32X3 (or F32) and rerun "
+                  "(net.strict_range = False, the default, does that by itself)"),
+    fallback=F32X3, fallback_text=("F32X3 (three bf16 planes: fp32 range, 24 bits, ~1.9x the time)", "F32X3 / F32"), two_lanes_416=40)}
+MODES[F32X3] = MODES[F32H2]._replace(
+    name="F32X3", storage=torch.bfloat16, planes=3, launch=F32X3, row_scale=False, wino_min_cin=None, front=None, res64=None,
+    stream_k=False, batch_split=False, always_status=False, fallback=None, fallback_text=None)
+MODES[F32] = MODES[F32X3]._replace(
+    name="F32", storage=torch.float32, planes=0, launch=F32, split=None, merge=None, pad128=False, wino_min_cin=WINO_MIN_CIN_F32,
+    wino_cout128=True, wino4=True, front="yv3_conv_front_f32", res64="yv3_res_block64_f32", head_decode=False, two_lanes_416=52)
+MODES[BF16] = MODES[F32X3]._replace(
+    name="BF16", planes=1, launch=BF16, front="yv3_conv_front_bf16", res64="yv3_res_block64_bf16", always_status=True, two_lanes_416=120,
+    overflow_msg=("the first layer of math mode BF16 runs on the fp16 matrix cores and needs |input| <= 4094 and "
+                  "|weight| <= 255 (csrc/conv0.hip); this input / these weights exceed that and were saturated: "
+                  "use net.math_mode = yolo_v3_amd.F32X3 (or F32)"))
+MODES[F16] = MODES[BF16]._replace(             # (two_lanes_416: BF16's -- the same kernels and bytes -- not a measurement of its own)
+    name="F16", storage=torch.float16, launch=F16, split="yv3_split_plane_f16", merge="yv3_merge_plane_f16", row_scale=True,
+    front="yv3_conv_front_f16", res64="yv3_res_block64_f16",
+    overflow_msg=("an activation exceeded the fp16 range (|v| > 65504) and was saturated: math mode F16 cannot represent this "
+                  "network/input; set net.math_mode = yolo_v3_amd.BF16 (the same cost, fp32's exponent range, 8 bits) or F32X3 / F32 "
+                  "and rerun (net.strict_range = False, the default, re-runs in BF16 by itself)"),
+    fallback=BF16, fallback_text=("BF16 (one bf16 plane: fp32 range, 8 bits instead of 11, the same time)", "BF16"))
+MODES[I8] = MODES[BF16]._replace(              # (the front and the heads are BF16's; two_lanes_416: BF16's too, two-lane tuning for int8 is not done)
+    name="I8", storage=torch.int8, mixed=True, split=None, merge=None, front_optional=False)
+# an entry point that lacks an argument of its field's other entries, brought to their form: one fp16 plane has no plane count (argument 3
+# of a split or merge), the exact-fp32 front kernels no status word (argument 11)
+_ADAPT = {"yv3_split_plane_f16": 3, "yv3_merge_plane_f16": 3, "yv3_conv_front_f32": 11, "yv3_res_block64_f32": 11}
+
+_TORCH_DTYPE = {c: m.storage for c, m in MODES.items()}        # element type of activation storage
+PLANES = {c: m.planes for c, m in MODES.items()}
+RANGE_FALLBACK = {c: m.fallback for c, m in MODES.items() if m.fallback is not None}
+
+
+def mode_of(dtype):
+    """The Mode of a math-mode code, or None for anything else (a bool is not a mode)."""
+    return MODES.get(dtype) if isinstance(dtype, numbers.Integral) and not isinstance(dtype, bool) else None
+
+
+def entry(name):
+    """The library function behind an entry point of a Mode, taking the arguments of its field."""
+    f, i = getattr(_ffi.lib(), name), _ADAPT.get(name)
+    return f if i is None else lambda *a: f(*a[:i], *a[i + 1:])
 
 
 def alloc_act(B, h, w, c, dtype, device):
@@ -35,46 +108,36 @@ def alloc_act(B, h, w, c, dtype, device):
     return torch.empty(shape, device=device, dtype=_TORCH_DTYPE[dtype])
 
 
+def _plane_entry(dtype, field):
+    m = MODES[dtype]
+    if m.planes and getattr(m, field) is None:
+        raise _ffi.Yv3Error("an int8 tensor is integers and a scale: there is no layout conversion for %s" % m.name)
+    return m, getattr(m, field)
+
+
 def to_planes(x_nhwc_f32, dtype):
     """fp32 NHWC tensor -> the activation layout of `dtype` (exact for F32X3)."""
-    if dtype == I8:
-        raise _ffi.Yv3Error("an int8 tensor is integers and a scale: there is no layout conversion for I8")
-    np_ = PLANES[dtype]
-    if np_ == 0:
-        return x_nhwc_f32.float().contiguous()
+    m, split = _plane_entry(dtype, "split")
     x = x_nhwc_f32.float().contiguous()
-    out = torch.empty((np_,) + tuple(x.shape), device=x.device, dtype=_TORCH_DTYPE[dtype])
-    if dtype == F16:             # (yv3_split_planes' one plane is bf16)
-        _ffi.check(_ffi.lib().yv3_split_plane_f16(x.data_ptr(), out.data_ptr(), x.numel(), _ffi.stream_ptr()), "yv3_split_plane_f16")
-        return out
-    _ffi.check(_ffi.lib().yv3_split_planes(x.data_ptr(), out.data_ptr(), x.numel(), np_, _ffi.stream_ptr()), "yv3_split_planes")
+    if m.planes == 0:
+        return x
+    out = torch.empty((m.planes,) + tuple(x.shape), device=x.device, dtype=m.storage)
+    _ffi.check(entry(split)(x.data_ptr(), out.data_ptr(), x.numel(), m.planes, _ffi.stream_ptr()), split)
     return out
 
 
 def from_planes(t, dtype):
     """Activation buffer of `dtype` -> fp32 NHWC tensor."""
-    if dtype == I8:
-        raise _ffi.Yv3Error("an int8 tensor is integers and a scale: there is no layout conversion for I8")
-    np_ = PLANES[dtype]
-    if np_ == 0 or t.dtype == torch.float32:
+    m, merge = _plane_entry(dtype, "merge")
+    if m.planes == 0 or t.dtype == torch.float32:
         return t
     out = torch.empty(tuple(t.shape[1:]), device=t.device, dtype=torch.float32)
-    if dtype == F16:
-        _ffi.check(_ffi.lib().yv3_merge_plane_f16(t.data_ptr(), out.data_ptr(), out.numel(), _ffi.stream_ptr()), "yv3_merge_plane_f16")
-        return out
-    _ffi.check(_ffi.lib().yv3_merge_planes(t.data_ptr(), out.data_ptr(), out.numel(), np_, _ffi.stream_ptr()), "yv3_merge_planes")
+    _ffi.check(entry(merge)(t.data_ptr(), out.data_ptr(), out.numel(), m.planes, _ffi.stream_ptr()), merge)
     return out
 
 
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-RANGE_FALLBACK = {F32H2: F32X3, F16: BF16}      # Engine.range_fallback: the mode that takes over after a RangeOverflow
-FALLBACK_TEXT = {          # (mode, what it falls back to, how to ask for that directly) of the one warning
-    F32H2: ("F32H2", "F32X3 (three bf16 planes: fp32 range, 24 bits, ~1.9x the time)", "F32X3 / F32"),
-    F16: ("F16", "BF16 (one bf16 plane: fp32 range, 8 bits instead of 11, the same time)", "BF16"),
-}
 
 
 class StreamKTimeout(_ffi.Yv3Error):
@@ -102,32 +165,23 @@ def conv_params(module):
     return module.conv.weight, module.bn, None
 
 
-def measure_env(name, default=None):
-    """Tuning / A-B overrides from the environment are honoured ONLY in measurement sessions (YV3_MEASURE=1, set by tools/gpu.sh): in
-    normal use a stray YV3_* variable changes nothing -- kernel selection is a function of the descriptor, the product knobs are
-    attributes of the net (net.math_mode, .stream_k, .winograd, .deterministic, .lanes, ...)."""
-    if os.environ.get("YV3_MEASURE") != "1":
-        return default
-    return os.environ.get(name, default)
-
-
-WINO_MIN_CIN = int(measure_env("YV3_WINO_MIN_CIN", "256") or 256)     # Winograd F(2x2,3x3) for 3x3 / stride-1 layers with at least this many input channels (26x26 and 13x13 at
-                       # 416x416): below, the transformed input (16 B per input element through HBM) costs more than the MFMAs saved
 _WINO_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
 
 
 SK_AUTO_CELLS = int(measure_env("YV3_SK_AUTO_CELLS", "1536") or 1536)     # stream-K by default up to this many 32x32 cells per batch (Plan._scratch)
 
 
-WINO_MIN_CIN_F32 = 64  # exact-fp32 mode: fp32 MFMA runs at the vector rate, every 3x3 layer is matrix-bound -> from the 104x104 layers down
-
-
 def wino_eligible(spec, dtype):
-    if not (spec.k == 3 and spec.stride == 1 and spec.bn):
-        return False
-    if dtype == F32H2:
-        return spec.cin >= WINO_MIN_CIN
-    return dtype == F32 and spec.cin >= WINO_MIN_CIN_F32 and spec.cout % 128 == 0
+    m = MODES[dtype]
+    return bool(spec.k == 3 and spec.stride == 1 and spec.bn and m.wino_min_cin is not None and spec.cin >= m.wino_min_cin
+                and not (m.wino_cout128 and spec.cout % 128))
+
+
+def conv_cout_pad(cout, dtype):
+    """Output channels of a packed weight: a multiple of 32, and above 128 of 128 where the plane kernels tile the channels by 128 (any
+    class count, e.g. 3*(5+40) = 135 -> 256)."""
+    cout_pad = (cout + 31) // 32 * 32
+    return (cout_pad + 127) // 128 * 128 if (MODES[dtype].pad128 and cout_pad > 128) else cout_pad
 
 
 def pack_wino(weight_f32, alpha_bn, spec, cout_pad, dtype=F32H2):
@@ -259,7 +313,8 @@ def pack_conv(module, spec, dtype, winograd=False, winograd4=True, s_in=None, he
         _ffi.check(lib.yv3_pack_conv_weight(wq.data_ptr(), wp.data_ptr(), spec.cout, spec.cin, spec.k, spec.cout, I8, s), "yv3_pack_conv_weight")
         return PackedConv(spec, wp, torch.from_numpy(m).to(dev), beta, spec.cout)
     w_orig, alpha_bn = w32, alpha
-    if dtype in (F32H2, F16) and spec.cin != 3:
+    m = MODES[dtype]
+    if m.row_scale and spec.cin != 3:
         # (F16: the same scale -- one fp16 plane keeps its 11 bits for every weight of a row down to 2^-14 of the row's maximum)
         # fp16 planes keep a relative precision of 2^-22 only while the `lo` part is a normal fp16 number, i.e. for
         # |w| >= 2^-3 after scaling: bring EVERY OUTPUT CHANNEL's weights to max|w_row| in [1,2) with its own exact
@@ -273,16 +328,14 @@ def pack_conv(module, spec, dtype, winograd=False, winograd4=True, s_in=None, he
     if spec.cin == 3:
         # first layer: direct-conv kernel wants [cin][kh][kw][cout] fp32
         return PackedConv(spec, w32.permute(1, 2, 3, 0).contiguous(), alpha, beta, spec.cout)
-    cout_pad = (spec.cout + 31) // 32 * 32
-    if dtype != F32 and cout_pad > 128:
-        cout_pad = (cout_pad + 127) // 128 * 128     # plane kernels tile the channels by 128 (any class count, e.g. 3*(5+40) = 135 -> 256)
+    cout_pad = conv_cout_pad(spec.cout, dtype)
     nw = cout_pad * spec.k * spec.k * spec.cin
-    wp = torch.empty(max(1, PLANES[dtype]) * nw, device=dev, dtype=_TORCH_DTYPE[dtype])
+    wp = torch.empty(max(1, m.planes) * nw, device=dev, dtype=m.storage)
     _ffi.check(lib.yv3_pack_conv_weight(w32.data_ptr(), wp.data_ptr(), spec.cout, spec.cin, spec.k,
                                         cout_pad, dtype, s), "yv3_pack_conv_weight")
     if winograd and wino_eligible(spec, dtype):
         ww, aw = pack_wino(w_orig, alpha_bn, spec, cout_pad, dtype)
-        w4 = pack_wino4(w_orig, spec) if (dtype == F32 and winograd4 and spec.cout % 64 == 0 and (spec.cin == 64 or spec.cin % 128 == 0) and cout_pad == spec.cout) else None
+        w4 = pack_wino4(w_orig, spec) if (m.wino4 and winograd4 and spec.cout % 64 == 0 and (spec.cin == 64 or spec.cin % 128 == 0) and cout_pad == spec.cout) else None
         return PackedConv(spec, wp, alpha, beta, cout_pad, ww, aw, w4)
     return PackedConv(spec, wp, alpha, beta, cout_pad)
 
@@ -356,10 +409,11 @@ def make_desc(pc, x, y, B, H, W, residual=None, x2=None, cin_up=0, dtype=F32, ou
     d.flags = _ptr(flags)
     d.workspace = _ptr(workspace)
     d.workspace_bytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
-    if wino_ws is not None and pc.w_wino is not None and batch is None and dtype in (F32H2, F32) and (out_dtype is None or out_dtype == dtype):
+    m = MODES[dtype]
+    if wino_ws is not None and pc.w_wino is not None and batch is None and m.wino_min_cin is not None and (out_dtype is None or out_dtype == dtype):
         d.w_wino, d.alpha_wino = _ptr(pc.w_wino), _ptr(pc.alpha_wino)
         d.wino_ws, d.wino_ws_bytes = _ptr(wino_ws), wino_ws.numel() * wino_ws.element_size()
-        if dtype == F32 and pc.w_wino4 is not None:
+        if m.wino4 and pc.w_wino4 is not None:
             d.w_wino4 = _ptr(pc.w_wino4)
     if batch is not None:
         b0, nb = batch
@@ -396,25 +450,26 @@ class Plan:
         if H % 32 or W % 32:
             raise _ffi.Yv3Error("input height/width must be multiples of 32 (got %dx%d)" % (H, W))
         self.B, self.H, self.W = B, H, W
-        dt, i8 = engine.dtype, engine.dtype == I8
+        m = engine.mode
         logits = bool(logits or engine.n_conv < len(engine.all_specs))
         # the YOLO decode is fused into the three head convs' epilogue (plane kernels): their logits are then not
         # materialised and the descriptors' dec_out is pointed at the caller's detections tensor before each launch
-        self.fused_decode = bool(engine.fuse_decode and dt != F32 and not logits)
+        self.fused_decode = bool(engine.fuse_decode and m.head_decode and not logits)
         # feature.mlist.0 + feature.mlist.1 run as ONE launch (csrc/conv_front.hip; exact fp32: csrc/conv_front_f32.hip); the first
         # layer's [B,H,W,32] activation is then never written (conv0_out stays allocated for the un-fused / layer-by-layer paths)
-        self.fused_front = bool(i8 or (engine.fuse_front and dt in (F32H2, BF16, F32, F16)))      # (I8: the front is always the two fused BF16 launches)
+        self.fused_front = bool(m.front is not None and (engine.fuse_front or not m.front_optional))      # (I8: the front is always the two fused BF16 launches)
         # ... and the first residual block (feature.mlist.2: 1x1 64->32 + 3x3 32->64 + add) as one more (csrc/conv_res64.hip,
         # csrc/conv_res64_f32.hip)
-        self.fused_res64 = bool(i8 or (self.fused_front and engine.fuse_res64))
+        self.fused_res64 = bool(self.fused_front and (engine.fuse_res64 or not m.front_optional))
         self.first_desc = 3 if self.fused_res64 else (1 if self.fused_front else 0)
+        self.front, self.res64 = (entry(m.front), entry(m.res64)) if self.fused_front else (None, None)      # Engine.run_front's two calls
         self._scratch(engine, flags, two_lanes)
         self._launches(engine, two_lanes)
         self._decode_params(engine)
 
     def _scratch(self, engine, flags, two_lanes):
         """The status word and the two scratch buffers the launches share."""
-        B, H, W, dev, dt = self.B, self.H, self.W, engine.device, engine.dtype
+        B, H, W, dev, m = self.B, self.H, self.W, engine.device, engine.mode
         # sticky status word written by the kernels (bit 0: an fp16-plane output was saturated) + its host mirror
         self.flags = flags if flags is not None else torch.zeros(1, device=dev, dtype=torch.int32)   # (lanes of one Detector share one)
         self.flags_host = torch.zeros(1, dtype=torch.int32).pin_memory()
@@ -426,29 +481,27 @@ class Plan:
         cells = B * ((H + 31) // 32) * ((W + 31) // 32)
         use_sk = engine.stream_k if engine.stream_k is not None else (cells <= SK_AUTO_CELLS and not two_lanes)
         self.workspace = (torch.zeros(_ffi.lib().yv3_conv_workspace_bytes(), device=dev, dtype=torch.uint8)
-                          if (dt == F32H2 and use_sk) else None)
+                          if (m.stream_k and use_sk) else None)
         # Winograd scratch (the transformed input of ONE layer at a time; launches of a plan are stream-ordered): sized for
         # the largest eligible layer of this plan
         self.wino_ws = None
-        if engine.winograd and dt in (F32H2, F32) and not engine.batch_split:      # (batch_split slices the same layers: direct kernels only)
+        if engine.winograd and m.wino_min_cin is not None and not engine.batch_split:      # (batch_split slices the same layers: direct kernels only)
             wsb = _ffi.lib().yv3_wino_workspace_bytes
             # eligible layers read 64 channels at H/4 (F32 only), 128 at H/8, 256 at H/16, 512 at H/32: the shallowest one is the largest
-            lo = WINO_MIN_CIN_F32 if dt == F32 else WINO_MIN_CIN
-            need = max(wsb(B, H // f, W // f, c) for c, f in ((64, 4), (128, 8), (256, 16), (512, 32)) if c >= min(lo, 512))
-            if dt == F32:          # (the F(4x4) form's V is 36 positions x a sixteenth of the pixels: never the larger one, asked for the record)
+            need = max(wsb(B, H // f, W // f, c) for c, f in ((64, 4), (128, 8), (256, 16), (512, 32)) if c >= min(m.wino_min_cin, 512))
+            if m.wino4:            # (the F(4x4) form's V is 36 positions x a sixteenth of the pixels: never the larger one, asked for the record)
                 need = max(need, max(_ffi.lib().yv3_wino4_workspace_bytes(B, H // f, W // f, c) for c, f in ((64, 4), (128, 8), (256, 16), (512, 32))))
             self.wino_ws = torch.zeros(need, device=dev, dtype=torch.uint8)       # (zero-filled: hand-over flags of the even schedule)
 
     def _launches(self, engine, two_lanes):
         """One output buffer and one descriptor (batch_split: two) per convolution 1 .. n_conv - 1, in arch.wiring's order."""
-        B, H, W, dev, dt = self.B, self.H, self.W, engine.device, engine.dtype
+        B, H, W, dev, m = self.B, self.H, self.W, engine.device, engine.mode
         packed, specs, n_conv = engine.packed, engine.all_specs, engine.n_conv
         wiring, hw = arch.wiring(specs), arch.conv_hw(H, W)
         # I8: a mixed plan -- convolutions 0-3 and the heads are BF16 launches on bf16 planes, the 68 between them int8 launches on int8
         # tensors (ld: a layer's launch dtype); the front's output is quantised once (front_q), each head reads the integers of the
         # layer before it, written as one bf16 plane by that layer's epilogue
-        i8 = dt == I8
-        act_dt = BF16 if i8 else dt
+        i8, act_dt = m.mixed, m.launch
         scales = engine.int8_scales if i8 else None
         feeds_head = {wr.x for wr in wiring if wr.head is not None}
         ncu = torch.cuda.get_device_properties(dev).multi_processor_count
@@ -471,7 +524,7 @@ class Plan:
             sp = pc.spec
             ld = I8 if (i8 and i >= I8_FIRST and sp.bn) else act_dt
             out_dtype = F32 if wr.head is not None else BF16 if (i8 and i in feeds_head) else None
-            head = wr.head is not None and dt != F32              # a plane-kernel head: where the decode can be fused
+            head = wr.head is not None and m.head_decode              # a plane-kernel head: where the decode can be fused
             x = self.front_q if (i8 and i == I8_FIRST) else out[wr.x]
             x2, residual = (out[j] if j is not None else None for j in (wr.x2, wr.residual))
             s_res = inv_s_out = 0.0
@@ -483,7 +536,7 @@ class Plan:
             if head:
                 self.head_descs.append((len(descs), ho, wo))
             split = None
-            if engine.batch_split and dt == F32H2 and sp.k == 3 and not head and self.workspace is None:
+            if engine.batch_split and m.batch_split and sp.k == 3 and not head and self.workspace is None:
                 split = batch_split(B, ho, wo, pc.cout_pad, ncu)
             for part in ([None] if split is None else [(0, split[0]), (split[0], split[1])]):
                 descs.append(make_desc(pc, x, y, B, h, w, residual, x2, wr.cin_up, ld, out_dtype, self.flags, self.workspace, batch=part,
@@ -593,6 +646,11 @@ class Engine:
 
     def __init__(self, net, dtype=F32, n_conv=75):
         self.net = net
+        self.mode = mode_of(dtype)
+        if self.mode is None:
+            err = _ffi.Yv3Error("an engine's math mode must be one of yolo_v3_amd.%s, got %r" % (", ".join(m.name for m in MODES.values()), dtype))
+            err.code = _ffi.EINVAL
+            raise err
         self.dtype = dtype
         self.num_class = net.numClass
         self.anchors = [float(a) for a in net.anchors_flat]
@@ -600,7 +658,7 @@ class Engine:
         if not self.FRONT_CONVS <= n_conv <= len(self.all_specs):
             raise _ffi.Yv3Error("an engine covers the first %d to %d convolutions, got %r" % (self.FRONT_CONVS, len(self.all_specs), n_conv))
         self.n_conv = int(n_conv)
-        if dtype == I8 and self.n_conv != len(self.all_specs):
+        if self.mode.mixed and self.n_conv != len(self.all_specs):
             raise _ffi.Yv3Error("I8 is an inference mode of the whole network: there is no int8 prefix engine")
         self.int8_scales = None                          # I8: the checked copy of net.int8_scales the packed weights and plans were built from
         self.specs = self.all_specs[:self.n_conv]        # what this engine packs and runs
@@ -693,7 +751,7 @@ class Engine:
         the 248 MB of weights and one host sync per forward) to the signature."""
         ts = self._param_tensors()
         sig = tuple((t.data_ptr(), t._version) for t in ts)
-        if self.dtype == I8:                # the scales are folded into the packed weights and written into the plans' descriptors
+        if self.mode.mixed:                 # the scales are folded into the packed weights and written into the plans' descriptors
             sig += (tuple(sorted(int8_scales_checked(self.net, self.all_specs).items())),)
         if getattr(self.net, "weight_check", "version") == "checksum" and ts and ts[0].is_cuda:
             # position-sensitive integer hash of the parameters' BIT patterns: sum_i bits_i * (i mod 65521 + 1) in wrapping
@@ -727,16 +785,16 @@ class Engine:
         _ffi.require_cuda(first, "YoloNet parameters (call net.cuda() first)")
         self.device = first.device
         with torch.cuda.device(self.device):
-            if self.dtype == I8:
+            if self.mode.mixed:
                 sc = self.int8_scales = int8_scales_checked(self.net, self.all_specs)
                 wiring = arch.wiring(self.all_specs)
 
                 def pack(i, sp):
                     mod = self.net.get_submodule(sp.name)
                     if i < I8_FIRST:
-                        return pack_conv(mod, sp, BF16)
+                        return pack_conv(mod, sp, self.mode.launch)
                     if not sp.bn:
-                        return pack_conv(mod, sp, BF16, head_scale=sc[self.all_specs[wiring[i].x].name])
+                        return pack_conv(mod, sp, self.mode.launch, head_scale=sc[self.all_specs[wiring[i].x].name])
                     return pack_conv(mod, sp, I8, s_in=int8_input_scales(self.all_specs, wiring, sc, i))
                 self.packed = [pack(i, sp) for i, sp in enumerate(self.specs)]
             else:
@@ -765,7 +823,7 @@ class Engine:
         key = (B, H, W)
         p = self._plans.get(key)
         if logits and (p is None or p.fused_decode):
-            if p is None and not (self.fuse_decode and self.dtype != F32):
+            if p is None and not (self.fuse_decode and self.mode.head_decode):
                 return self.plan(B, H, W)
             key = (B, H, W, "logits")
             p = self._plans.get(key)
@@ -791,30 +849,16 @@ class Engine:
         if not plan.fused_front:
             return self.run_conv0(plan, x)
         p0, p1, d1 = self.packed[0], self.packed[1], plan.descs[0]
-        if self.dtype == F32:
-            _ffi.check(_ffi.lib().yv3_conv_front_f32(x.data_ptr(), p0.w.data_ptr(), p0.alpha.data_ptr(), p0.beta.data_ptr(),
-                                                     p1.w.data_ptr(), p1.alpha.data_ptr(), p1.beta.data_ptr(), d1.y,
-                                                     plan.B, plan.H, plan.W, _ffi.stream_ptr()), "yv3_conv_front_f32")
-            if plan.fused_res64:
-                p2, p3, d3 = self.packed[2], self.packed[3], plan.descs[2]
-                _ffi.check(_ffi.lib().yv3_res_block64_f32(d1.y, p2.w.data_ptr(), p2.alpha.data_ptr(), p2.beta.data_ptr(),
-                                                          p3.w.data_ptr(), p3.alpha.data_ptr(), p3.beta.data_ptr(), d3.y,
-                                                          plan.B, plan.H // 2, plan.W // 2, _ffi.stream_ptr()), "yv3_res_block64_f32")
-            return
-        lib = _ffi.lib()
-        front = {F32H2: lib.yv3_conv_front, BF16: lib.yv3_conv_front_bf16, F16: lib.yv3_conv_front_f16, I8: lib.yv3_conv_front_bf16}[self.dtype]
-        _ffi.check(front(x.data_ptr(), p0.w.data_ptr(), p0.alpha.data_ptr(), p0.beta.data_ptr(),
-                                             p1.w.data_ptr(), p1.alpha.data_ptr(), p1.beta.data_ptr(), d1.y,
-                                             plan.B, plan.H, plan.W, plan.flags.data_ptr(), _ffi.stream_ptr()), "yv3_conv_front")
+        flags, s = plan.flags.data_ptr(), _ffi.stream_ptr()
+        _ffi.check(plan.front(x.data_ptr(), p0.w.data_ptr(), p0.alpha.data_ptr(), p0.beta.data_ptr(),
+                              p1.w.data_ptr(), p1.alpha.data_ptr(), p1.beta.data_ptr(), d1.y, plan.B, plan.H, plan.W, flags, s), "yv3_conv_front")
         if plan.fused_res64:
             p2, p3, d3 = self.packed[2], self.packed[3], plan.descs[2]
-            res = {F32H2: lib.yv3_res_block64, BF16: lib.yv3_res_block64_bf16, F16: lib.yv3_res_block64_f16, I8: lib.yv3_res_block64_bf16}[self.dtype]
-            _ffi.check(res(d1.y, p2.w.data_ptr(), p2.alpha.data_ptr(), p2.beta.data_ptr(),
-                                                  p3.w.data_ptr(), p3.alpha.data_ptr(), p3.beta.data_ptr(), d3.y,
-                                                  plan.B, plan.H // 2, plan.W // 2, plan.flags.data_ptr(), _ffi.stream_ptr()),
+            _ffi.check(plan.res64(d1.y, p2.w.data_ptr(), p2.alpha.data_ptr(), p2.beta.data_ptr(),
+                                  p3.w.data_ptr(), p3.alpha.data_ptr(), p3.beta.data_ptr(), d3.y, plan.B, plan.H // 2, plan.W // 2, flags, s),
                        "yv3_res_block64")
-            if self.dtype == I8:              # the one boundary launch: the front's bf16 output -> the first int8 layer's input
-                _ffi.check(lib.yv3_quantize_bf16_i8(d3.y, plan.front_q.data_ptr(), plan.front_q.numel(), plan.front_inv_s, _ffi.stream_ptr()),
+            if plan.front_q is not None:      # (I8) the one boundary launch: the front's bf16 output -> the first int8 layer's input
+                _ffi.check(_ffi.lib().yv3_quantize_bf16_i8(d3.y, plan.front_q.data_ptr(), plan.front_q.numel(), plan.front_inv_s, s),
                            "yv3_quantize_bf16_i8")
 
     def run_conv_sequence(self, plan, dets=None):
@@ -852,15 +896,7 @@ class Engine:
             x = x.float().contiguous()
         return x
 
-    OVERFLOW_MSG = ("an activation exceeded the fp16 range (|v| > 65504) and was saturated: math mode F32H2 cannot "
-                    "represent this network/input; set net.math_mode = yolo_v3_amd.F32X3 (or F32) and rerun "
-                    "(net.strict_range = False, the default, does that by itself)")
-    OVERFLOW_MSG_F16 = ("an activation exceeded the fp16 range (|v| > 65504) and was saturated: math mode F16 cannot represent this "
-                        "network/input; set net.math_mode = yolo_v3_amd.BF16 (the same cost, fp32's exponent range, 8 bits) or F32X3 / F32 "
-                        "and rerun (net.strict_range = False, the default, re-runs in BF16 by itself)")
-    OVERFLOW_MSG_BF16 = ("the first layer of math mode BF16 runs on the fp16 matrix cores and needs |input| <= 4094 and "
-                         "|weight| <= 255 (csrc/conv0.hip); this input / these weights exceed that and were saturated: "
-                         "use net.math_mode = yolo_v3_amd.F32X3 (or F32)")
+    OVERFLOW_MSG = MODES[F32H2].overflow_msg
 
     def raise_if_overflowed(self, plan, flag_value):
         """Turn the kernels' sticky saturation flag into an error (and clear it)."""
@@ -872,7 +908,7 @@ class Engine:
                 raise StreamKTimeout("a stream-K accumulator hand-over timed out: the schedule needs all of its workgroups resident at once "
                                      "and something else (another stream / thread / process running small batches) held part of the GPU.  "
                                      "Callers that share the GPU set net.stream_k = False (or net.deterministic = True)")
-            raise RangeOverflow({BF16: self.OVERFLOW_MSG_BF16, I8: self.OVERFLOW_MSG_BF16, F16: self.OVERFLOW_MSG_F16}.get(self.dtype, self.OVERFLOW_MSG))
+            raise RangeOverflow(self.mode.overflow_msg)
 
     def range_fallback(self):
         """After a RangeOverflow: the engine that takes over (RANGE_FALLBACK) -- for the default mode F32X3, the same plane pipeline on
@@ -881,7 +917,7 @@ class Engine:
         caller wants the error; BF16: a reduced-precision mode the caller chose).  The choice is remembered on the network
         (``net._range_fallback``: {mode asked for: mode that runs}; ``YoloNet.engine`` hands out the fall-back engine wherever this
         engine's mode is asked for from now on) and announced once."""
-        to = RANGE_FALLBACK.get(self.dtype)
+        to = self.mode.fallback
         if to is None or getattr(self.net, "strict_range", False):
             return None
         import warnings
@@ -889,14 +925,14 @@ class Engine:
         if self.dtype not in chosen:
             warnings.warn("yolo_v3_amd: an activation left the fp16 range of math mode %s (|v| > 65504); this network now runs in %s -- "
                           "set net.math_mode = %s to avoid the first, discarded pass, or net.strict_range = True to get an error instead"
-                          % FALLBACK_TEXT[self.dtype], RuntimeWarning)
+                          % ((self.mode.name,) + self.mode.fallback_text), RuntimeWarning)
             chosen[self.dtype] = to
         return self.net.engine(to)
 
     def checks_status(self):
         """Does a forward of this engine have a kernel status word to look at?  F32H2 / F16 / BF16: fp16 saturation (+ stream-K hand-over);
         F32: only the F(4x4) stage's even schedule can set it (hand-over time-out on a shared GPU) -- not with ``net.stream_k = False``."""
-        return self.dtype in (F32H2, BF16, F16, I8) or (self.dtype == F32 and self.winograd and self.winograd4 and self.stream_k is not False)
+        return self.mode.always_status or (self.mode.wino4 and self.winograd and self.winograd4 and self.stream_k is not False)
 
     def disable_stream_k(self):
         """After a StreamKTimeout: this engine stops using the stream-K schedule (plans are rebuilt without its workspace; holders
