@@ -852,6 +852,28 @@ size_t yv3_jpeg_workspace_bytes(const yv3_jpeg_info* infos_host, int B);
  * identical calls give identical bits. */
 int yv3_jpeg_decode_batch(const yv3_jpeg_batch_desc* desc, void* ws, size_t ws_bytes, void* stream);
 
+/* The entropy stage of yv3_jpeg_decode_batch_ex (an enum, not status or reason codes).
+ * SERIAL: one lane per unit (a whole scan, or a restart segment), as yv3_jpeg_decode_batch.
+ * PARALLEL: the self-synchronising decoder (csrc/jpeg_sync.h).  A unit of 256 bytes or more is cut into subsequences of 64
+ * bytes, one lane each; a lane decodes speculatively from its first bit, exit states are handed down the chain until each
+ * subsequence's entry state is proven from the unit's first bit (windows of 256 subsequences, at most 16 proving passes each),
+ * and only proven lanes write.  Shorter units take one lane each as before; one image may hold both kinds. */
+enum { YV3_JPEG_ENTROPY_SERIAL = 0, YV3_JPEG_ENTROPY_PARALLEL = 1 };
+
+/* yv3_jpeg_workspace_bytes for the given entropy stage.  The parallel stage keeps its per-subsequence records in LDS, so both
+ * stages need the same bytes; 0 on a bad argument or an unknown `entropy`. */
+size_t yv3_jpeg_workspace_bytes_ex(const yv3_jpeg_info* infos_host, int B, int entropy);
+
+/* yv3_jpeg_decode_batch with the entropy stage chosen per call; SERIAL is yv3_jpeg_decode_batch itself, through the same code.
+ * The status contract of PARALLEL: status[b] and, at status 0, every destination byte are exactly SERIAL's for the same input,
+ * whatever the bytes are.  The parallel stage either establishes that the serial routine would return 0 for a unit and have
+ * written exactly these coefficients, or it zeroes the unit's coefficients again and runs the serial routine on one lane in the
+ * same launch (an FF that is no FF 00 pair, an error from a proven state, a wrong block count, a failed end check, a DC value
+ * outside 16 bits); that routine's status stands.  handed_over: device [B] or null; with PARALLEL, handed_over[b] = the units of
+ * image b that were handed to the serial routine -- 0 for every file an encoder can write (not written with SERIAL).  The same
+ * argument checks before any launch, and YV3_EINVAL for an unknown `entropy`; no allocation, no synchronisation. */
+int yv3_jpeg_decode_batch_ex(const yv3_jpeg_batch_desc* desc, int entropy, int* handed_over, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * The update step (csrc/optim.hip; yolo_v3_amd/optim.py): torch's clip_grad_norm_ and torch.optim.SGD over a list of fp32
  * tensors, a few launches for the whole list.  The list arguments (g, p, buf, n) are HOST arrays of `count` device pointers /

@@ -1,0 +1,217 @@
+"""The self-synchronising entropy stage on the GPU (``yv3_jpeg_decode_batch_ex`` with ``YV3_JPEG_ENTROPY_PARALLEL``): one mixed batch of
+every setting, scans longer than one window, damaged files whose status must be the serial stage's, and the Python surface."""
+import ctypes
+import io
+
+import numpy as np
+import pytest
+import torch
+
+from tests import jpeg_craft
+from tests.test_gpu_jpeg import damaged_files, files, pil_rgb  # noqa: F401  (files: the fixture of every PIL setting)
+from tests.test_jpeg_host import picture
+from tests.test_jpeg_sync_host import crafted_long_files, table_files
+from yolo_v3_amd import _ffi, evaluate, jpeg
+from yolo_v3_amd import augment as aug
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+GUARD = 512
+SERIAL, PARALLEL = jpeg.ENTROPY["serial"], jpeg.ENTROPY["parallel"]
+
+
+def run_batch(datas, entropy, infos=None):
+    """One yv3_jpeg_decode_batch_ex over ``datas`` (sources at odd offsets, destinations at any alignment between guard bytes, the
+    workspace between guard bytes).  Returns statuses, hand-over counts and the destination bytes of every image; asserts that
+    nothing outside the destinations, the statuses, the counts and the workspace was written."""
+    B = len(datas)
+    lib = _ffi.lib()
+    host = (_ffi.JpegInfo * B)()
+    src_off, pos = [], 1
+    for k, d in enumerate(datas):
+        host[k] = jpeg.parse(d)
+        assert host[k].reason == 0, k
+        src_off.append(pos)
+        pos = (pos + len(d) + 3) | 1
+    src = np.full(pos + 7, 0x5A, np.uint8)
+    for o, d in zip(src_off, datas):
+        src[o:o + len(d)] = np.frombuffer(d, np.uint8)
+    sizes = [host[k].width * host[k].height * 3 for k in range(B)]
+    dst_off, dpos = [], GUARD + 1
+    for k in range(B):
+        dst_off.append(dpos)
+        dpos += sizes[k] + GUARD + (k % 3)
+    dst = torch.full((dpos,), 0xA5, dtype=torch.uint8, device=DEV)
+    need = lib.yv3_jpeg_workspace_bytes_ex(ctypes.addressof(host), B, entropy)
+    assert need == lib.yv3_jpeg_workspace_bytes(ctypes.addressof(host), B)
+    ws = torch.full((need + 2 * GUARD,), 0x3C, dtype=torch.uint8, device=DEV)
+    d_src = torch.from_numpy(src).to(DEV)
+    d_soff = torch.tensor(src_off, dtype=torch.int64, device=DEV)
+    d_doff = torch.tensor(dst_off, dtype=torch.int64, device=DEV)
+    d_info = torch.from_numpy(np.frombuffer(infos if infos is not None else host, np.uint8).copy()).to(DEV)
+    status = torch.full((B + 2,), 777, dtype=torch.int32, device=DEV)
+    handed = torch.full((B + 2,), 555, dtype=torch.int32, device=DEV)
+    desc = _ffi.JpegBatchDesc(src=d_src.data_ptr(), src_bytes=d_src.numel(), src_offsets=d_soff.data_ptr(), infos=d_info.data_ptr(),
+                              infos_host=ctypes.addressof(host), dst=dst.data_ptr(), dst_bytes=dst.numel(), dst_offsets=d_doff.data_ptr(),
+                              status=status.data_ptr() + 4, B=B)
+    _ffi.check(lib.yv3_jpeg_decode_batch_ex(ctypes.byref(desc), entropy, handed.data_ptr() + 4, ws.data_ptr() + GUARD, need,
+                                            _ffi.stream_ptr()), "yv3_jpeg_decode_batch_ex")
+    torch.cuda.synchronize()
+    st, ho = status.cpu().numpy(), handed.cpu().numpy()
+    assert st[0] == 777 and st[-1] == 777 and ho[0] == 555 and ho[-1] == 555
+    if entropy == SERIAL:
+        assert (ho == 555).all()                                         # not written by the serial stage
+    got = dst.cpu().numpy()
+    mask = np.ones(got.size, bool)
+    out = []
+    for k in range(B):
+        mask[dst_off[k]:dst_off[k] + sizes[k]] = False
+        out.append(got[dst_off[k]:dst_off[k] + sizes[k]].reshape(host[k].height, host[k].width, 3))
+    assert (got[mask] == 0xA5).all()                                     # the canary around every destination
+    wsn = ws.cpu().numpy()
+    assert (wsn[:GUARD] == 0x3C).all() and (wsn[GUARD + need:] == 0x3C).all()       # and around the workspace
+    assert (d_src.cpu().numpy() == src).all()
+    return st[1:-1], ho[1:-1], out
+
+
+def test_every_setting_in_one_mixed_batch(files):
+    cases, refs = files
+    extra = table_files() + crafted_long_files()
+    names = [n for n, _ in cases] + [n for n, _ in extra] + ["photograph again", "noise q100 4:4:4 again"]
+    datas = [d for _, d in cases] + [d for _, d in extra] + [extra[0][1], extra[4][1]]       # windows: the same long files twice
+    refs = list(refs) + [pil_rgb(d) for d in datas[len(cases):]]
+    st1, ho1, px1 = run_batch(datas, PARALLEL)
+    bad = [(names[k], int(st1[k]), int(ho1[k])) for k in range(len(datas)) if st1[k] or ho1[k]]
+    assert not bad, bad[:10]                                             # status 0 and no unit handed over, for every file
+    wrong = [names[k] for k in range(len(datas)) if not np.array_equal(px1[k], refs[k])]
+    assert not wrong, (len(wrong), wrong[:10])                           # PIL's pixels, bit for bit
+    st0, _, px0 = run_batch(datas, SERIAL)
+    assert np.array_equal(st0, st1) and all(np.array_equal(a, b) for a, b in zip(px0, px1))
+    st2, ho2, px2 = run_batch(datas, PARALLEL)                           # identical calls, identical bits
+    assert np.array_equal(st2, st1) and np.array_equal(ho2, ho1) and all(np.array_equal(a, b) for a, b in zip(px2, px1))
+    # both kinds of unit were met: scans of more than one window, units of one lane, and one image with both
+    long_bytes = [len(d) for d in datas[len(cases):]]
+    assert max(long_bytes) > 2 * 256 * 64 and min(len(d) for d in datas) < 700
+
+
+def test_damaged_files_get_the_serial_status():
+    good, truncated, corrupted = damaged_files()
+    other = jpeg_craft.pil_bytes(np.asarray(picture(33, 19, seed=12)), quality=75, subsampling=1, restart_marker_blocks=2)
+    lost_marker = other.replace(b"\xff\xd1", b"\x12\x34", 1)
+    sources = jpeg_craft.corruption_sources()
+    datas = [good, truncated, other, corrupted, lost_marker, good[:-2]]
+    for (name, src), seed in list(zip(sources, jpeg_craft.CORRUPTION_SEEDS))[:2]:
+        datas += jpeg_craft.corruptions(src, 300, seed)
+    long_src = table_files()[1][1]                                       # damage inside a scan of several windows' worth of passes
+    datas += jpeg_craft.corruptions(long_src, 40, 3)
+    datas = [d for d in datas if jpeg.parse(d).reason == 0]
+    assert len(datas) > 600
+    st0, _, px0 = run_batch(datas, SERIAL)
+    st1, ho1, px1 = run_batch(datas, PARALLEL)
+    assert np.array_equal(st0, st1), [(k, int(a), int(b)) for k, (a, b) in enumerate(zip(st0, st1)) if a != b][:10]
+    assert (st1 == 0).sum() > 30 and (st1 != 0).sum() > 100 and ho1.sum() > 0 and (ho1[st1 != 0] >= 0).all()
+    for k, d in enumerate(datas):
+        if st1[k] == 0:
+            assert np.array_equal(px1[k], px0[k]), k
+            try:
+                ref = pil_rgb(d)
+            except Exception:                                            # (a file without EOI: PIL refuses it, jpeg.py routes it)
+                continue
+            assert np.array_equal(px1[k], ref), k
+
+
+def test_lying_records_stay_inside_their_buffers():
+    """test_gpu_jpeg's lying-record case through the parallel stage: the same statuses as the serial one."""
+    good, _, _ = damaged_files()
+    lib = _ffi.lib()
+    B = 4
+    infos = (_ffi.JpegInfo * B)()
+    for k in range(B):
+        infos[k] = jpeg.parse(good)
+    host = (_ffi.JpegInfo * B)()
+    ctypes.memmove(host, infos, ctypes.sizeof(infos))
+    infos[1].scan_length = 1 << 40
+    infos[2].width = 20000
+    n = 64 * 48 * 3
+    d_src = torch.from_numpy(np.frombuffer(good, np.uint8).copy()).to(DEV)
+    d_soff = torch.zeros(B, dtype=torch.int64, device=DEV)
+    d_doff = torch.tensor([0, n, 2 * n, 3 * n - 1], dtype=torch.int64, device=DEV)
+    d_info = torch.from_numpy(np.frombuffer(infos, np.uint8).copy()).to(DEV)
+    need = lib.yv3_jpeg_workspace_bytes_ex(ctypes.addressof(host), B, PARALLEL)
+    results = []
+    for entropy in (SERIAL, PARALLEL):
+        dst = torch.full((3 * n + GUARD,), 0xA5, dtype=torch.uint8, device=DEV)
+        ws = torch.empty(need, dtype=torch.uint8, device=DEV)
+        status = torch.full((B,), 777, dtype=torch.int32, device=DEV)
+        handed = torch.full((B,), 555, dtype=torch.int32, device=DEV)
+        desc = _ffi.JpegBatchDesc(src=d_src.data_ptr(), src_bytes=d_src.numel(), src_offsets=d_soff.data_ptr(), infos=d_info.data_ptr(),
+                                  infos_host=ctypes.addressof(host), dst=dst.data_ptr(), dst_bytes=3 * n, dst_offsets=d_doff.data_ptr(),
+                                  status=status.data_ptr(), B=B)
+        _ffi.check(lib.yv3_jpeg_decode_batch_ex(ctypes.byref(desc), entropy, handed.data_ptr(), ws.data_ptr(), need, _ffi.stream_ptr()),
+                   "yv3_jpeg_decode_batch_ex")
+        torch.cuda.synchronize()
+        results.append((status.tolist(), dst.cpu().numpy()))
+        if entropy == PARALLEL:
+            assert handed.tolist() == [0, 0, 0, 0]
+    assert results[0][0] == results[1][0] == [0, _ffi.JPEG_S_BOUNDS, _ffi.JPEG_S_INFO, _ffi.JPEG_S_BOUNDS]
+    assert np.array_equal(results[0][1], results[1][1])
+    assert np.array_equal(results[1][1][:n].reshape(48, 64, 3), pil_rgb(good)) and (results[1][1][n:] == 0xA5).all()
+
+
+def test_decode_batch_parallel_one_upload_one_status_read(files):
+    cases, refs = files
+    pick = list(range(0, len(cases), 37))
+    photo = table_files()[0][1]
+    before = dict(jpeg.counters)
+    out = jpeg.decode_batch([cases[j][1] for j in pick] + [photo], device=DEV, entropy="parallel")
+    assert {k: jpeg.counters[k] - before[k] for k in ("calls", "uploads", "status_reads", "fallbacks")} == \
+        {"calls": 1, "uploads": 1, "status_reads": 1, "fallbacks": 0}
+    assert out.fallback == [False] * (len(pick) + 1) and out.handed_over == [0] * (len(pick) + 1)
+    for t, j in zip(out, pick):
+        assert np.array_equal(t.cpu().numpy(), refs[j]), cases[j][0]
+    assert np.array_equal(out[-1].cpu().numpy(), pil_rgb(photo))
+    again = jpeg.decode_batch([cases[j][1] for j in pick] + [photo], device=DEV, entropy="parallel")
+    assert all(torch.equal(a, b) for a, b in zip(out, again))
+    assert jpeg.decode_batch([photo], device=DEV).handed_over == [0]     # the serial stage: zeros
+
+
+def test_damaged_files_come_back_through_pil_with_parallel():
+    good, truncated, corrupted = damaged_files()
+    progressive = jpeg_craft.pil_bytes(np.asarray(picture(17, 13, seed=13)), progressive=True)
+    batch = [good, truncated, corrupted, progressive, good]
+    out = jpeg.decode_batch(batch, device=DEV, errors="keep", entropy="parallel")
+    ser = jpeg.decode_batch(batch, device=DEV, errors="keep")
+    assert out.fallback == ser.fallback == [False, True, True, True, False] and out.reasons == ser.reasons
+    assert out.reasons[2] == ("device", _ffi.JPEG_S_CODE) and out.reasons[3] == ("parser", _ffi.JPEG_PROGRESSIVE)
+    assert out.handed_over[0] == 0 and out.handed_over[1] >= 1 and out.handed_over[2] >= 1 and out.handed_over[3] == 0
+    for i, data in enumerate(batch):
+        try:
+            ref = evaluate.read_image_rgb(io.BytesIO(data))
+        except Exception as e:
+            assert type(out[i]) is type(e) and str(out[i]) == str(e) and i == 1
+            continue
+        assert np.array_equal(out[i].cpu().numpy(), ref), i
+
+
+def test_train_batches_with_the_parallel_stage(tmp_path):
+    (tmp_path / "images").mkdir()
+    (tmp_path / "labels").mkdir()
+    paths = []
+    for i, ((w, h), kw) in enumerate([((120, 90), dict(subsampling=2)), ((70, 90), dict(subsampling=1, restart_marker_blocks=3)),
+                                      ((64, 64), dict(subsampling=0)), ((57, 31), dict())]):
+        p = str(tmp_path / "images" / ("img%d.jpg" % i))
+        picture(w, h, "L" if i == 3 else "RGB", "gradient" if i % 2 else "noise", seed=60 + i).save(p, "JPEG", quality=85, **kw)
+        np.savetxt(str(tmp_path / "labels" / ("img%d.txt" % i)), np.array([[1, 0.5, 0.5, 0.3, 0.4]]))
+        paths.append(p)
+    lst = tmp_path / "train.txt"
+    lst.write_text("\n".join(paths) + "\n")
+
+    def epoch(**kw):
+        return [(x.cpu().numpy(), t.cpu().numpy()) for x, t in aug.TrainBatches(str(lst), 2, (128, 96), seed=4, jitter=0.2, **kw)]
+    base = epoch()
+    got = epoch(decode="gpu", entropy="parallel")
+    assert len(base) == len(got) == 2
+    for (x, t), (x0, t0) in zip(got, base):
+        assert np.array_equal(x.view(np.int32), x0.view(np.int32)) and np.array_equal(t.view(np.int32), t0.view(np.int32))
+    with pytest.raises(ValueError):
+        aug.TrainBatches(str(lst), 2, (128, 96), seed=4, decode="gpu", entropy="fast")

@@ -5,14 +5,16 @@ their label files in a temporary directory, bs 16, dim 416, whole epochs ending 
   workers    workers=8: the next batches' files are decoded on threads
   resident   cache_bytes holding the whole list, measured from the second epoch on: no file is read, no pixel uploaded
   defaults_gpu / workers_gpu   the first two with decode="gpu": the JPEGs are decoded on the GPU (yolo_v3_amd/jpeg.py), one batch ahead
-  *+step     the four above with a stand-in training step after every batch: fp32 matrix products on the current stream, sized at
+  *_par      (--entropy parallel | both) the two decode="gpu" settings with entropy="parallel", the self-synchronising entropy stage;
+             --entropy parallel replaces the serial ones by them, --entropy both times both in the same rounds
+  *+step     the four above (and the *_par ones) with a stand-in training step after every batch: fp32 matrix products on the current stream, sized at
              start-up to --step-ms of device time and only enqueued (as a training loop enqueues its step), so that the setting's
              ms per batch minus --step-ms is what the loader adds to a step it can overlap with
 Rounds are interleaved (one epoch of every setting per round); per setting the median, minimum and maximum of the per-epoch
 ms per batch, the batches per second of the median, the host's share (time inside ``next()``, before the synchronise) and the
 bytes uploaded per batch as the code counts them (``augment.counters``).  One JSON line per setting.
 
-    python tools/loader_bench.py [--rounds 9] [--warmup 2] [--workers 8]
+    python tools/loader_bench.py [--rounds 9] [--warmup 2] [--workers 8] [--entropy serial|parallel|both]
 """
 import argparse
 import json
@@ -107,16 +109,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workers", type=int, default=8)
     ap.add_argument("--step-ms", type=float, default=80.0)
+    ap.add_argument("--entropy", choices=("serial", "parallel", "both"), default="serial")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as root:
         lst = write_files(root)
         make = lambda **kw: aug.TrainBatches(lst, BS, (DIM, DIM), seed=1, **kw)
-        loaders = {"defaults": make(), "workers": make(workers=a.workers), "resident": make(cache_bytes=make().decoded_bytes()),
-                   "defaults_gpu": make(decode="gpu"), "workers_gpu": make(workers=a.workers, decode="gpu")}
+        loaders = {"defaults": make(), "workers": make(workers=a.workers), "resident": make(cache_bytes=make().decoded_bytes())}
+        if a.entropy != "parallel":
+            loaders.update({"defaults_gpu": make(decode="gpu"), "workers_gpu": make(workers=a.workers, decode="gpu")})
+        if a.entropy != "serial":
+            loaders.update({"defaults_gpu_par": make(decode="gpu", entropy="parallel"),
+                            "workers_gpu_par": make(workers=a.workers, decode="gpu", entropy="parallel")})
         step, step_ms = make_step(a.step_ms)
         steps = {}
-        for k in ("defaults", "workers", "defaults_gpu", "workers_gpu"):
-            loaders[k + "+step"] = make(workers=loaders[k].workers, decode=loaders[k].decode)
+        for k in [k for k in loaders if k != "resident"]:
+            loaders[k + "+step"] = make(workers=loaders[k].workers, decode=loaders[k].decode, entropy=loaders[k].entropy)
             steps[k + "+step"] = step
         epoch(loaders["resident"])                         # the first epoch fills the arena
         assert loaders["resident"].resident_images() == N_IMAGES
@@ -131,6 +138,7 @@ def main():
             med = float(np.median(wall))
             print(json.dumps({"setting": k, "bs": BS, "dim": DIM, "src": "%dx%d jpeg q90" % (W, H), "images": N_IMAGES,
                               "workers": loaders[k].workers, "cache_bytes": loaders[k].cache_bytes, "decode": loaders[k].decode,
+                              "entropy": loaders[k].entropy if loaders[k].decode == "gpu" else None,
                               "ms_per_batch": round(med, 3), "min_ms": round(wall[0], 3), "max_ms": round(wall[-1], 3),
                               "batches_per_s": round(1e3 / med, 1), "host_ms_per_batch": round(float(np.median([s[1] for s in v])), 3),
                               "upload_bytes_per_batch": int(np.median([s[2] for s in v])), "rounds": a.rounds,

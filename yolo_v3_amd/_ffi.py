@@ -198,6 +198,8 @@ _SIGNATURES = {
     "yv3_jpeg_parse": (c_int, [c_void_p, c_size_t, ctypes.POINTER(JpegInfo)]),
     "yv3_jpeg_workspace_bytes": (c_size_t, [c_void_p, c_int]),
     "yv3_jpeg_decode_batch": (c_int, [ctypes.POINTER(JpegBatchDesc), c_void_p, c_size_t, c_void_p]),
+    "yv3_jpeg_workspace_bytes_ex": (c_size_t, [c_void_p, c_int, c_int]),
+    "yv3_jpeg_decode_batch_ex": (c_int, [ctypes.POINTER(JpegBatchDesc), c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "yv3_optim_chunk": (c_int, []),
     "yv3_grad_sumsq": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_longlong, c_void_p]),
     "yv3_clip_coef": (c_int, [c_void_p, c_longlong, c_float, c_void_p, c_void_p]),

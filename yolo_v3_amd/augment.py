@@ -378,7 +378,8 @@ class TrainBatches:
     enqueued on a stream the loader owns before batch k is handed out, and batch k's consumer waits for batch k's own event
     (measured against a step that fills every CU the decode did not overlap with it: DESIGN.md section 8f); with ``cache_bytes``
     the kernels write straight into the arena.  Files the GPU decoder does not take go through `read_image_rgb` as before.  The
-    switch is not part of a ``state_dict``'s config: both settings give the same bits.
+    switch is not part of a ``state_dict``'s config: both settings give the same bits.  ``entropy`` (``"serial"`` by default, or
+    ``"parallel"``) is passed on to `jpeg.submit`: the decoder's entropy stage, which changes no bit either.
 
     ``extra=True``: the reference's ``ExtraAugmentations`` in front of everything else, as ``Compose([ExtraAugmentations(),
     IaaAugmentations([...]), ToTensor()])`` has them: every batch is ``augment_batch(extra_augment_batch(images,
@@ -388,10 +389,12 @@ class TrainBatches:
     ``state_dict()`` / ``load_state_dict()`` resume between two batches with the same data order."""
 
     def __init__(self, list_file, batch_size, dim, seed, shuffle=True, max_labels=MAX_LABELS, multiscale=None, dim_interval=10,
-                 workers=0, prefetch=2, cache_bytes=0, decode="pil", extra=False, **aug):
+                 workers=0, prefetch=2, cache_bytes=0, decode="pil", extra=False, entropy="serial", **aug):
         if decode not in ("pil", "gpu"):
             raise ValueError("decode must be 'pil' or 'gpu'")
-        self.decode, self._side, self.extra = decode, None, bool(extra)
+        if entropy not in ("serial", "parallel"):
+            raise ValueError("entropy must be 'serial' or 'parallel'")
+        self.decode, self._side, self.extra, self.entropy = decode, None, bool(extra), entropy
         with open(list_file, 'r') as f:
             self.img_list = [line.strip() for line in f.readlines() if line.strip()]
         self.label_list = [label_path(p) for p in self.img_list]
@@ -545,9 +548,10 @@ class TrainBatches:
         rest = [i for i in new if i not in admitted]
         jobs = []
         if admitted:
-            jobs.append((admitted, jpeg.submit([images[i] for i in admitted], stream=self._side, dst=(self._arena, offsets))))
+            jobs.append((admitted, jpeg.submit([images[i] for i in admitted], stream=self._side, dst=(self._arena, offsets),
+                                                   entropy=self.entropy)))
         if rest:
-            jobs.append((rest, jpeg.submit([images[i] for i in rest], stream=self._side)))
+            jobs.append((rest, jpeg.submit([images[i] for i in rest], stream=self._side, entropy=self.entropy)))
         return batch, admitted, jobs, self._pos
 
     def _complete(self, launched):

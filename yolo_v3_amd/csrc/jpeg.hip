@@ -7,6 +7,11 @@
 //                    footprint that would keep other images' workgroups off the CU), all lanes zero the image's coefficients and
 //                    find its restart markers, then one lane decodes each restart segment (jpeg_entropy.h; a file without DRI
 //                    is one segment, one lane): the parallelism is the many images in flight
+//   entropy_kernel<1> the same kernel with the self-synchronising stage (jpeg_sync.h; yv3_jpeg_decode_batch_ex, entropy =
+//                    YV3_JPEG_ENTROPY_PARALLEL): a unit of YV3_JPEG_SYNC_MIN_BYTES or more is cut into subsequences of
+//                    YV3_JPEG_SYNC_S bytes and decoded by the whole workgroup, a window of 256 subsequences at a time (sync_unit
+//                    below); shorter units still take one lane each.  A unit the parallel path cannot establish as error-free is
+//                    re-zeroed and handed to yv3_jpeg_decode_unit on one lane in the same launch, whose status stands
 //   idct_kernel      one lane per 8x8 block: dequantise, jidctint's two passes, +128, clamp -> the component's uint8 plane; a block
 //                    outside the range in which every libjpeg build computes the same bytes (jpeg_pixel.h) raises the image's
 //                    status to YV3_JPEG_S_RANGE
@@ -17,6 +22,7 @@
 #include "yv3_common.h"
 #include "jpeg_parse.h"
 #include "jpeg_pixel.h"
+#include "jpeg_sync.h"
 
 namespace {
 
@@ -62,9 +68,142 @@ __global__ __launch_bounds__(256) void layout_kernel(const yv3_jpeg_info* __rest
     }
 }
 
+// One unit of YV3_JPEG_SYNC_MIN_BYTES or more, by the whole workgroup (every lane calls it with the same arguments).  0: coef
+// holds exactly what yv3_jpeg_decode_unit would have written and that routine would return 0.  1: the caller hands the unit to
+// it (an FF that is no stuffing pair, an error from a proven state, a wrong block count, a failed end check, a DC value out of
+// range).  Windows of 256 subsequences, the first one's entry state proven: a speculative pass, at most YV3_JPEG_SYNC_P proving
+// passes (each hands every lane its predecessor's exit state, or its own first bit again while that state is invalid; a lane whose
+// entry state changed decodes again), then the proven
+// prefix -- lane 0 and every lane whose entry state is its predecessor's exit state, up to the first break of that chain -- is
+// committed by the write pass and the next window opens behind it.  Pass p proves lane p at the latest, so a window commits
+// min(P + 1, its lanes) subsequences or more and the loop ends after at most nsub windows.  No lane waits on another's flag:
+// every dependency goes through a barrier.
+__device__ int sync_unit(const unsigned char* scan, long long begin, long long end, const yv3_jpeg_geom* g, const yv3_jpeg_hufftab* tabs,
+                         const unsigned char* sel, const unsigned char* natural, short* coef, int m0, int m1) {
+    constexpr int L = YV3_JPEG_SYNC_LANES, S = YV3_JPEG_SYNC_S;
+    __shared__ yv3_jpeg_sync_state s_en[L], s_ex[L], s_entry;
+    __shared__ int s_cnt[L], s_off[L];
+    __shared__ long long s_dc[L][3];
+    __shared__ int s_flag, s_np, s_base, s_err, s_fin;
+    const int t = threadIdx.x;
+    const int bpm = yv3_jpeg_sync_bpm(g), unit_blocks = (m1 - m0) * bpm, nblocks = g->nblocks;    // <= 6 * 2048 * 2048
+    const long long nsub = (end - begin + S - 1) / S;
+    __syncthreads();                                       // the previous unit's last reads of the flags
+    if (t == 0) { s_flag = 0; s_err = 0; s_fin = 0; s_base = 0; s_entry.bit = begin * 8; s_entry.blk = 0; s_entry.zz = 0; }
+    __syncthreads();
+    for (long long i = begin + t; i < end; i += L)
+        if (yv3_jpeg_sync_marker(scan, i, end)) s_flag = 1;
+    __syncthreads();
+    if (s_flag) return 1;
+    long long w0 = 0;
+    while (w0 < nsub) {                                    // every window commits at least its lane 0
+        const int nl = nsub - w0 < L ? (int)(nsub - w0) : L;
+        yv3_jpeg_sync_state en, ex;
+        en.bit = -1; en.blk = 0; en.zz = 0; ex = en;
+        int cnt = 0;
+        long long cut = end;
+        if (t < nl) {                                      // the speculative pass
+            cut = yv3_jpeg_sync_cut(scan, begin, end, w0 + t + 1, S);
+            if (t == 0) en = s_entry;
+            else en.bit = yv3_jpeg_sync_cut(scan, begin, end, w0 + t, S) * 8;
+            yv3_jpeg_sync_lane(scan, end, cut, &en, g, tabs, sel, sel + 4, natural, 0, nblocks, m0, 0, 0, &ex, &cnt);
+            s_en[t] = en; s_ex[t] = ex; s_cnt[t] = cnt;
+        }
+        for (int p = 0; p < YV3_JPEG_SYNC_P; ++p) {        // the proving passes
+            if (t == 0) s_flag = 0;
+            __syncthreads();
+            bool changed = false;
+            yv3_jpeg_sync_state ne = en;
+            if (t > 0 && t < nl) {
+                ne = s_ex[t - 1];
+                if (ne.bit < 0) { ne.bit = yv3_jpeg_sync_cut(scan, begin, end, w0 + t, S) * 8; ne.blk = 0; ne.zz = 0; }     // stay speculative
+                changed = !yv3_jpeg_sync_same(ne, en);
+                if (changed) s_flag = 1;
+            }
+            __syncthreads();
+            const int any = s_flag;
+            __syncthreads();                               // every lane has read the flag before lane 0 clears it for the next pass
+            if (!any) break;                               // every chain link holds: the whole window is proven
+            if (changed) {
+                en = ne;
+                yv3_jpeg_sync_lane(scan, end, cut, &en, g, tabs, sel, sel + 4, natural, 0, nblocks, m0, 0, 0, &ex, &cnt);
+                s_en[t] = en; s_ex[t] = ex; s_cnt[t] = cnt;     // (s_ex[t] is read by lane t + 1 alone, before the barrier above)
+            }
+        }
+        __syncthreads();
+        if (t == 0) s_np = nl;
+        __syncthreads();
+        if (t > 0 && t < nl) {
+            const yv3_jpeg_sync_state prev = s_ex[t - 1];
+            if (prev.bit < 0 || !yv3_jpeg_sync_same(prev, en)) atomicMin(&s_np, t);
+        }
+        __syncthreads();
+        const int np = s_np;                               // 1 <= np <= nl
+        if (t == 0) {                                      // exclusive prefix sum of the proven block counts
+            int run = s_base;
+            for (int j = 0; j < np; ++j) {
+                s_off[j] = run;
+                run = s_cnt[j] < unit_blocks - run ? run + s_cnt[j] : unit_blocks;
+            }
+            s_base = run;
+        }
+        __syncthreads();
+        if (t < np && s_off[t] < unit_blocks) {            // the write pass (a lane behind the unit's last block has nothing to write:
+                                                           // the lane that completed that block makes the end checks)
+            const int r = yv3_jpeg_sync_lane(scan, end, cut, &en, g, tabs, sel, sel + 4, natural, coef, nblocks, m0, s_off[t], unit_blocks,
+                                             &ex, &cnt);
+            if (r == YV3_JPEG_SYNC_ERROR) s_err = 1;
+            if (r == YV3_JPEG_SYNC_FINISHED) s_fin = 1;
+        }
+        __syncthreads();
+        if (s_err) return 1;
+        if (s_fin) break;
+        if (t == 0) s_entry = s_ex[np - 1];
+        w0 += np;
+        __syncthreads();
+    }
+    if (!s_fin) return 1;                                  // the bytes ran out before the unit's last block
+    // the DC pass: each lane sums the differences of its run of MCUs, lane 0 scans the 256 sums, each lane applies its prefix
+    const int M = m1 - m0, chunk = (M + L - 1) / L;
+    const int lo = m0 + (t * chunk < M ? t * chunk : M), hi = m0 + ((t + 1) * chunk < M ? (t + 1) * chunk : M);
+    long long sums[3] = {0, 0, 0};
+    yv3_jpeg_sync_dc_sum(coef, g, nblocks, lo, hi, sums);
+    for (int c = 0; c < 3; ++c) s_dc[t][c] = sums[c];
+    __syncthreads();
+    if (t == 0) {
+        long long run[3] = {0, 0, 0};
+        for (int j = 0; j < L; ++j)
+            for (int c = 0; c < 3; ++c) { const long long v = s_dc[j][c]; s_dc[j][c] = run[c]; run[c] += v; }
+    }
+    __syncthreads();
+    for (int c = 0; c < 3; ++c) sums[c] = s_dc[t][c];
+    if (!yv3_jpeg_sync_dc_apply(coef, g, nblocks, lo, hi, sums)) s_err = 1;
+    __syncthreads();
+    return s_err;
+}
+
+// The byte range [*begin, *end) of unit u between the restart markers found at marks[], and its MCUs [*m0, *m1).  0, or
+// YV3_JPEG_S_MARKER for markers out of order or out of range.
+__device__ int unit_range(const unsigned char* scan, int len, const int* marks, const yv3_jpeg_geom& g, int u, long long* begin,
+                          long long* end, int* m0, int* m1) {
+    int code = 0;
+    *begin = 0; *end = len;
+    if (u > 0) *begin = (long long)marks[u - 1] + 2;
+    if (u < g.nunits - 1) {
+        *end = marks[u];
+        if (*end < 0 || *end + 1 >= len || scan[*end + 1] != 0xD0 + (u & 7)) code = YV3_JPEG_S_MARKER;
+    }
+    if (*begin < 0 || *begin > len || *end < *begin) code = YV3_JPEG_S_MARKER;
+    *m0 = u * g.mcus_per_unit;
+    *m1 = g.nmcu - *m0 < g.mcus_per_unit ? g.nmcu : *m0 + g.mcus_per_unit;
+    return code;
+}
+
+// SYNC 0: one lane per unit.  SYNC 1: long units go to sync_unit; `handed` [B] counts the units handed back to one lane.
+template <int SYNC>
 __global__ __launch_bounds__(256) void entropy_kernel(const unsigned char* __restrict__ src, const long long* __restrict__ src_offsets,
                                                       const yv3_jpeg_info* __restrict__ infos, yv3_jpeg_slot* __restrict__ slots,
-                                                      unsigned char* __restrict__ ws, int* __restrict__ status) {
+                                                      unsigned char* __restrict__ ws, int* __restrict__ status, int* __restrict__ handed) {
     __shared__ yv3_jpeg_hufftab tabs[8];
     __shared__ yv3_jpeg_geom g;
     __shared__ int counts[256];
@@ -73,6 +212,7 @@ __global__ __launch_bounds__(256) void entropy_kernel(const unsigned char* __res
     __shared__ unsigned char natural[64];
     const int b = blockIdx.x, t = threadIdx.x;
     const yv3_jpeg_slot slot = slots[b];
+    if (SYNC && handed && t == 0) handed[b] = 0;           // whichever way the image leaves this kernel
     if (slot.status) return;                               // the whole workgroup: layout_kernel refused the image
     const yv3_jpeg_info* f = infos + b;
     if (t == 0) { s_geom = yv3_jpeg_geometry(f, &g); s_status = 0; s_total = 0; }
@@ -122,21 +262,55 @@ __global__ __launch_bounds__(256) void entropy_kernel(const unsigned char* __res
     __syncthreads();                                       // raise it below, so the branch is the same for the whole workgroup
     if (before == 0) {
         short* coef = (short*)(ws + slot.coef_off);
-        for (int u = t; u < nunits; u += 256) {
-            int code = 0;
-            long long begin = 0, end = len;
-            if (u > 0) begin = (long long)marks[u - 1] + 2;
-            if (u < nunits - 1) {
-                end = marks[u];
-                if (end < 0 || end + 1 >= len || scan[end + 1] != 0xD0 + (u & 7)) code = YV3_JPEG_S_MARKER;
+        if constexpr (SYNC == 0) {
+            for (int u = t; u < nunits; u += 256) {
+                long long begin, end;
+                int m0, m1;
+                int code = unit_range(scan, len, marks, g, u, &begin, &end, &m0, &m1);
+                if (!code) code = yv3_jpeg_decode_unit(scan, begin, end, &g, tabs, sel, sel + 4, natural, m0, m1, coef, g.nblocks);
+                if (code) atomicMax(&s_status, code);
             }
-            if (begin < 0 || begin > len || end < begin) code = YV3_JPEG_S_MARKER;
-            if (!code) {
-                const int m0 = u * g.mcus_per_unit;
-                const int m1 = g.nmcu - m0 < g.mcus_per_unit ? g.nmcu : m0 + g.mcus_per_unit;
-                code = yv3_jpeg_decode_unit(scan, begin, end, &g, tabs, sel, sel + 4, natural, m0, m1, coef, g.nblocks);
+        } else {
+            __shared__ int s_long[256], s_nlong, s_handed;
+            if (t == 0) s_handed = 0;
+            for (int u0 = 0; u0 < nunits; u0 += 256) {     // 256 units a round: the short ones decoded, the long ones listed
+                if (t == 0) s_nlong = 0;
+                __syncthreads();
+                const int u = u0 + t;
+                if (u < nunits) {
+                    long long begin, end;
+                    int m0, m1;
+                    int code = unit_range(scan, len, marks, g, u, &begin, &end, &m0, &m1);
+                    if (!code) {
+                        if (end - begin >= YV3_JPEG_SYNC_MIN_BYTES) s_long[atomicAdd(&s_nlong, 1)] = u;      // at most 256 a round
+                        else code = yv3_jpeg_decode_unit(scan, begin, end, &g, tabs, sel, sel + 4, natural, m0, m1, coef, g.nblocks);
+                    }
+                    if (code) atomicMax(&s_status, code);
+                }
+                __syncthreads();
+                const int nlong = s_nlong;
+                for (int q = 0; q < nlong; ++q) {          // the whole workgroup, one long unit after the other
+                    long long begin, end;
+                    int m0, m1;
+                    if (unit_range(scan, len, marks, g, s_long[q], &begin, &end, &m0, &m1)) continue;       // (it passed above)
+                    if (sync_unit(scan, begin, end, &g, tabs, sel, natural, coef, m0, m1)) {
+                        const int bpm = yv3_jpeg_sync_bpm(&g);
+                        const long long n16u = (long long)(m1 - m0) * bpm * 8;
+                        for (long long i = t; i < n16u; i += 256) {             // the unit's blocks, zero again
+                            const long long blk = yv3_jpeg_sync_block(&g, m0 + (int)(i / 8 / bpm), (int)(i / 8 % bpm), g.nblocks);
+                            if (blk >= 0) ((int4*)(coef + blk * 64))[i & 7] = make_int4(0, 0, 0, 0);
+                        }
+                        __syncthreads();
+                        if (t == 0) {
+                            const int code = yv3_jpeg_decode_unit(scan, begin, end, &g, tabs, sel, sel + 4, natural, m0, m1, coef, g.nblocks);
+                            if (code) atomicMax(&s_status, code);
+                            ++s_handed;
+                        }
+                    }
+                }
+                __syncthreads();
             }
-            if (code) atomicMax(&s_status, code);
+            if (t == 0 && handed && s_handed) handed[b] = s_handed;
         }
     }
     __syncthreads();
@@ -225,7 +399,9 @@ __global__ __launch_bounds__(256) void colour_kernel(const yv3_jpeg_info* __rest
 
 }  // namespace
 
-extern "C" int yv3_jpeg_decode_batch(const yv3_jpeg_batch_desc* desc, void* ws, size_t ws_bytes, void* stream) {
+extern "C" int yv3_jpeg_decode_batch_ex(const yv3_jpeg_batch_desc* desc, int entropy, int* handed_over, void* ws, size_t ws_bytes,
+                                        void* stream) {
+    if (entropy != YV3_JPEG_ENTROPY_SERIAL && entropy != YV3_JPEG_ENTROPY_PARALLEL) return YV3_EINVAL;
     if (!desc || !ws || ((uintptr_t)ws & 255) != 0) return YV3_EINVAL;
     if (!desc->src || !desc->src_offsets || !desc->infos || !desc->infos_host || !desc->dst || !desc->dst_offsets || !desc->status)
         return YV3_EINVAL;
@@ -248,7 +424,12 @@ extern "C" int yv3_jpeg_decode_batch(const yv3_jpeg_batch_desc* desc, void* ws, 
     hipLaunchKernelGGL(layout_kernel, dim3(1), dim3(256), 0, s, desc->infos, desc->src_offsets, desc->src_bytes, desc->dst_offsets,
                        desc->dst_bytes, B, slots, (long long)ws_bytes, desc->status);
     YV3_CHECK_LAUNCH();
-    hipLaunchKernelGGL(entropy_kernel, dim3(B), dim3(256), 0, s, desc->src, desc->src_offsets, desc->infos, slots, wsb, desc->status);
+    if (entropy == YV3_JPEG_ENTROPY_PARALLEL)
+        hipLaunchKernelGGL(entropy_kernel<1>, dim3(B), dim3(256), 0, s, desc->src, desc->src_offsets, desc->infos, slots, wsb, desc->status,
+                           handed_over);
+    else
+        hipLaunchKernelGGL(entropy_kernel<0>, dim3(B), dim3(256), 0, s, desc->src, desc->src_offsets, desc->infos, slots, wsb, desc->status,
+                           (int*)0);
     YV3_CHECK_LAUNCH();
     const int gx_idct = (int)(max_blocks / 256 + 1 < 4096 ? max_blocks / 256 + 1 : 4096);
     hipLaunchKernelGGL(idct_kernel, dim3(gx_idct, B), dim3(256), 0, s, desc->infos, slots, wsb, desc->status);
@@ -258,4 +439,8 @@ extern "C" int yv3_jpeg_decode_batch(const yv3_jpeg_batch_desc* desc, void* ws, 
                        desc->dst_offsets);
     YV3_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int yv3_jpeg_decode_batch(const yv3_jpeg_batch_desc* desc, void* ws, size_t ws_bytes, void* stream) {
+    return yv3_jpeg_decode_batch_ex(desc, YV3_JPEG_ENTROPY_SERIAL, 0, ws, ws_bytes, stream);
 }

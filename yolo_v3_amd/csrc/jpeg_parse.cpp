@@ -163,3 +163,8 @@ size_t yv3_jpeg_batch_workspace(const yv3_jpeg_info* infos, int B, bool strict) 
 extern "C" size_t yv3_jpeg_workspace_bytes(const yv3_jpeg_info* infos_host, int B) {
     return yv3_jpeg_batch_workspace(infos_host, B, false);
 }
+
+extern "C" size_t yv3_jpeg_workspace_bytes_ex(const yv3_jpeg_info* infos_host, int B, int entropy) {
+    if (entropy != YV3_JPEG_ENTROPY_SERIAL && entropy != YV3_JPEG_ENTROPY_PARALLEL) return 0;
+    return yv3_jpeg_batch_workspace(infos_host, B, false);      // the parallel stage's records live in LDS
+}

@@ -242,7 +242,7 @@ def read_image_rgb(path):
         return np.asarray(im.convert("RGB"), dtype=np.uint8).copy()
 
 
-def generate_results_file(net, target_txt, classes_names, out, bs, dim, is_letterbox=False, decode="pil"):
+def generate_results_file(net, target_txt, classes_names, out, bs, dim, is_letterbox=False, decode="pil", entropy="serial"):
     """reference evaluate.py:208-219: the COCO-results file of a list of images -- ``target_txt`` is the reference's text file with one
     image path per line (a list of paths, or of ``(path, uint8 RGB [H,W,3] array)`` pairs, is accepted too).  Per batch of ``bs``
     images: the evaluation pipeline's input preparation on the GPU (``IaaLetterbox(dim)`` when ``is_letterbox`` else
@@ -250,10 +250,13 @@ def generate_results_file(net, target_txt, classes_names, out, bs, dim, is_lette
     0.45) and the writer.  ``dim`` = (w, h).  Returns the number of result entries written.
 
     ``decode="gpu"``: each batch's files are decoded by `jpeg.decode_batch` instead of `read_image_rgb` in this thread -- the same
-    pixels (files the GPU decoder does not take still go through `read_image_rgb`), so the same file."""
+    pixels (files the GPU decoder does not take still go through `read_image_rgb`), so the same file.  ``entropy`` is passed on to
+    it (``"serial"`` or ``"parallel"``; it changes no pixel)."""
     from .utils import letterbox_batch
     if decode not in ("pil", "gpu"):
         raise ValueError("decode must be 'pil' or 'gpu'")
+    if entropy not in ("serial", "parallel"):
+        raise ValueError("entropy must be 'serial' or 'parallel'")
     if isinstance(target_txt, str):
         with open(target_txt, 'r') as f:
             items = [line.strip() for line in f.readlines() if line.strip()]
@@ -267,7 +270,7 @@ def generate_results_file(net, target_txt, classes_names, out, bs, dim, is_lette
             paths = [c if isinstance(c, str) else c[0] for c in chunk]
             if decode == "gpu":
                 from . import jpeg
-                files = iter(jpeg.decode_batch([c for c in chunk if isinstance(c, str)]))
+                files = iter(jpeg.decode_batch([c for c in chunk if isinstance(c, str)], entropy=entropy))
                 imgs = [next(files) if isinstance(c, str) else c[1] for c in chunk]
             else:
                 imgs = [read_image_rgb(c) if isinstance(c, str) else c[1] for c in chunk]

@@ -20,6 +20,8 @@ from . import _ffi
 _ALIGN = 256
 _INFO_BYTES = ctypes.sizeof(_ffi.JpegInfo)
 
+ENTROPY = {"serial": 0, "parallel": 1}                    # enum YV3_JPEG_ENTROPY_* of include/yv3.h (no JPEG_* code of _ffi)
+
 counters = {"calls": 0, "uploads": 0, "upload_bytes": 0, "status_reads": 0, "fallbacks": 0}     # for measurements and tests
 
 
@@ -94,17 +96,22 @@ class Source:
 
 class Decoded(list):
     """`decode_batch`'s result: a list of uint8 ``[H,W,3]`` GPU tensors.  ``fallback[i]``: image i took the PIL path;
-    ``reasons[i]``: ``("parser", reason)``, ``("exif", None)``, ``("device", status)``, ``("truncated", None)`` or None."""
+    ``reasons[i]``: ``("parser", reason)``, ``("exif", None)``, ``("device", status)``, ``("truncated", None)`` or None;
+    ``handed_over[i]``: the units of image i that ``entropy="parallel"`` handed to the serial routine on the device (0 for a file
+    an encoder can write, and always with ``entropy="serial"`` or for an image that never reached the device)."""
     fallback = ()
     reasons = ()
+    handed_over = ()
 
 
 class Job:
     """A decode in flight on ``stream``, with an event recorded right after its own work.  `finish` waits for that event on the
-    host, reads the statuses once, routes damaged files through PIL and makes the current stream wait for the event too."""
+    host, reads the statuses once, routes damaged files through PIL and makes the current stream wait for the event too.
+    ``handed_over`` (one int per image, zeros until `finish`): see `Decoded`."""
 
-    def __init__(self, items, views, reasons, status_host, event, stream, keep):
+    def __init__(self, items, views, reasons, status_host, event, stream, keep, parallel=False):
         self.items, self.views, self.reasons = items, views, reasons
+        self.handed_over, self._parallel = [0] * len(items), parallel
         self._status_host, self._event, self._stream, self._keep = status_host, event, stream, keep
         self._finished = False
 
@@ -115,12 +122,15 @@ class Job:
             redo = False
             if self._status_host is not None:
                 counters["status_reads"] += 1
-                status = self._status_host.numpy()
+                status = self._status_host.numpy()           # [B] statuses, then (parallel) [B] hand-over counts: one read
+                B = len(status) // 2 if self._parallel else len(status)
                 k = 0
                 for i, it in enumerate(self.items):
                     if not it.on_gpu:
                         continue
                     st = int(status[k])
+                    if self._parallel:
+                        self.handed_over[i] = int(status[B + k])
                     k += 1
                     if st == 0 and not it.unterminated:
                         continue
@@ -150,6 +160,7 @@ class Job:
                 out.append(self.views[i])
         out.fallback = [r is not None for r in self.reasons]
         out.reasons = list(self.reasons)
+        out.handed_over = list(self.handed_over)
         cur = torch.cuda.current_stream(self._keep[0].device)
         if cur != self._stream:
             cur.wait_event(self._event)                      # the consumer waits for this job alone: a later job's decode on the
@@ -158,12 +169,17 @@ class Job:
         return out
 
 
-def submit(sources, device=None, stream=None, dst=None):
+def submit(sources, device=None, stream=None, dst=None, entropy="serial"):
     """Enqueue the decode of ``sources`` (paths, ``bytes`` or prepared `Source` objects) on ``stream`` (default: the current one)
     and return the `Job`.  One device allocation holds, in this order, the upload -- records, offsets, the files' bytes and the
     pixels of the images PIL already decoded -- and the images the kernels write, each at a 256-aligned offset; it is filled by
     ONE host-to-device copy.  ``dst = (tensor, offsets)``: image i is decoded into the uint8 1-D ``tensor`` (`TrainBatches`'
-    arena) at ``offsets[i]`` instead, for every i (None entries are not allowed: split the batch)."""
+    arena) at ``offsets[i]`` instead, for every i (None entries are not allowed: split the batch).  ``entropy="parallel"``: the
+    self-synchronising entropy stage (``yv3_jpeg_decode_batch_ex``) -- the same statuses and pixels; its hand-over counts lie
+    behind the statuses and come back in the same read."""
+    if entropy not in ENTROPY:
+        raise ValueError("entropy must be 'serial' or 'parallel'")
+    parallel = entropy == "parallel"
     if not torch.cuda.is_available():
         raise _ffi.Yv3Error("no GPU available: this package has no CPU path")
     dev = torch.device(device if device is not None else "cuda")
@@ -186,7 +202,7 @@ def submit(sources, device=None, stream=None, dst=None):
     o_soff = _round_up(o_info + B * _INFO_BYTES)
     o_doff = _round_up(o_soff + B * 8)
     o_stat = _round_up(o_doff + B * 8)
-    o_src = _round_up(o_stat + B * 4)
+    o_src = _round_up(o_stat + B * (8 if parallel else 4))   # parallel: [B] hand-over counts behind the statuses
     src_off, pos = [], o_src
     for i in gpu:
         src_off.append(pos - o_src)
@@ -248,26 +264,28 @@ def submit(sources, device=None, stream=None, dst=None):
         keep = [buf]
         status_host = None
         if B:
-            ws_bytes = lib.yv3_jpeg_workspace_bytes(ctypes.addressof(infos), B)
+            ws_bytes = lib.yv3_jpeg_workspace_bytes_ex(ctypes.addressof(infos), B, ENTROPY[entropy])
             ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
             base = buf.data_ptr()
             desc = _ffi.JpegBatchDesc(src=base + o_src, src_bytes=src_bytes, src_offsets=base + o_soff, infos=base + o_info,
                                       infos_host=ctypes.addressof(infos), dst=dst_t.data_ptr(), dst_bytes=dst_t.numel(),
                                       dst_offsets=base + o_doff, status=base + o_stat, B=B)
-            _ffi.check(lib.yv3_jpeg_decode_batch(ctypes.byref(desc), ws.data_ptr(), ws.numel(), stream.cuda_stream),
-                       "yv3_jpeg_decode_batch")
-            status_host = torch.empty(B, dtype=torch.int32, pin_memory=True)
-            status_host.copy_(buf[o_stat:o_stat + B * 4].view(torch.int32), non_blocking=True)
+            _ffi.check(lib.yv3_jpeg_decode_batch_ex(ctypes.byref(desc), ENTROPY[entropy], base + o_stat + B * 4 if parallel else None,
+                                                    ws.data_ptr(), ws.numel(), stream.cuda_stream), "yv3_jpeg_decode_batch_ex")
+            n_read = 2 * B if parallel else B
+            status_host = torch.empty(n_read, dtype=torch.int32, pin_memory=True)
+            status_host.copy_(buf[o_stat:o_stat + n_read * 4].view(torch.int32), non_blocking=True)
         event = torch.cuda.Event()                          # after this job's upload, kernels and status copy, and nothing else
         event.record(stream)
-    return Job(items, views, reasons, status_host, event, stream, keep)
+    return Job(items, views, reasons, status_host, event, stream, keep, parallel)
 
 
-def decode_batch(sources, device=None, errors="raise"):
+def decode_batch(sources, device=None, errors="raise", entropy="serial"):
     """uint8 RGB ``[H,W,3]`` GPU tensors of ``sources`` (paths or ``bytes``), each what `evaluate.read_image_rgb` returns for it,
     as views into one allocation at 256-aligned offsets: a `Decoded` list whose ``fallback`` says which images took the PIL path.
     One upload (records + file bytes) and one status read per call.  ``errors="raise"`` (default): an image PIL cannot read
-    raises what `read_image_rgb` raises; ``"keep"``: the exception takes the image's place in the list."""
+    raises what `read_image_rgb` raises; ``"keep"``: the exception takes the image's place in the list.  ``entropy``: ``"serial"``
+    (default; one lane per restart segment or scan) or ``"parallel"`` (the self-synchronising stage): the same result either way."""
     if errors not in ("raise", "keep"):
         raise ValueError("errors must be 'raise' or 'keep'")
-    return submit(sources, device=device).finish(errors)
+    return submit(sources, device=device, entropy=entropy).finish(errors)
