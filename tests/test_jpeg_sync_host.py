@@ -205,13 +205,18 @@ def crafted_long_files():
                  jpeg_craft.Component(jpeg_craft._ordinary(rng, mh, mw), 1, 1, tq=3, td=1, ta=0),
                  jpeg_craft.Component(jpeg_craft._ordinary(rng, mh, mw), 1, 1, tq=0, td=3, ta=2)]
         out.append(("selectors 2 and 3 %dx%d" % (h, v), jpeg_craft.write(101, 77, comps, quant, huff, ids=(7, 200, 0), sof=1)))
-    # 300 restart segments of four blocks: flat ones of a few bytes, and two of noise at q = 1 (hundreds of bytes each)
+    out.append(segments_300(rng, (5, 250)))
+    return out
+
+
+def segments_300(rng, long_units):
+    """300 restart segments of four blocks: flat ones of a few bytes, and those of ``long_units`` of noise at q = 1 (hundreds of
+    bytes each)."""
     c = np.zeros((1200, 1, 64), np.int64)
     c[:, 0, 0] = rng.randint(-40, 41, 1200)
-    for unit in (5, 250):
+    for unit in long_units:
         c[4 * unit:4 * unit + 4] = jpeg_craft.encodable(rng.randint(0, 256, (32, 8)), 1)
-    out.append(jpeg_craft._grey("300 segments, two long", 8, 9600, c, q=[1] * 64, restart=4))
-    return out
+    return jpeg_craft._grey("300 segments, two long", 8, 9600, c, q=[1] * 64, restart=4)
 
 
 def test_crafted_files(checker, tmp_path):
@@ -221,6 +226,43 @@ def test_crafted_files(checker, tmp_path):
             assert (f["units"], f["long_units"]) == (300, 2)
     for name, data in jpeg_craft.family_a():                     # the family as it is (most of its units are short ones)
         check_valid(checker, tmp_path, data, name)
+
+
+@pytest.mark.parametrize("group", ["rounds", "window_edges", "cuts", "dc_shapes"])
+def test_gpu_case_files_are_what_their_names_say(checker, tmp_path, group):
+    """The files of tests/jpeg_sync_cases.py, which test_gpu_jpeg_sync gives to the kernel: each decodes (PIL's pixels, through
+    `check_valid`) and still has the property it is in the batch for."""
+    from tests import jpeg_sync_cases as cases
+    files = getattr(cases, group)()
+    assert len(files) == len({n for n, _ in files}) >= 4
+    for name, data in files:
+        want = cases.EXPECT[name]
+        f = check_valid(checker, tmp_path, data, name, parallel=want["long_units"] > 0)
+        for key in ("units", "long_units", "nsub", "scan_bytes"):
+            if key in want:
+                assert f[key] == want[key], "%s: %s is %d, meant to be %d" % (name, key, f[key], want[key])
+        assert len(want["long_at"]) == want["long_units"], "%s: %d long units counted in the file" % (name, len(want["long_at"]))
+        for key in ("per_round", "long_at"):
+            if key + "_meant" in want:
+                assert want[key] == want[key + "_meant"], "%s: %s is %s, meant to be %s" % (name, key, want[key], want[key + "_meant"])
+        if "mcus" in want:
+            w, h = Image.open(io.BytesIO(data)).size
+            assert (f["units"], -(-w // 8) * -(-h // 8)) == (1, want["mcus"]), "%s: not one unit of %d MCUs" % (name, want["mcus"])
+        ceil = -(-f["nsub"] // LANES)
+        rule = {None: True, "1": f["windows"] == 1, ">=2": f["windows"] >= 2, ">ceil": f["windows"] > ceil}[want.get("windows")]
+        assert rule, "%s: %d windows for %d subsequences, meant to be %s" % (name, f["windows"], f["nsub"], want["windows"])
+
+
+def test_gpu_case_file_damaged_in_round_two_hands_a_unit_over(checker, tmp_path):
+    """The bit flipped in unit 270 is an error the lanes meet from a proven state (no marker that the first look at the unit
+    finds): one unit handed over, and the serial routine's status."""
+    from tests import jpeg_sync_cases as cases
+    name, data = cases.damaged_round_two()
+    assert jpeg.parse(data).reason == 0 and len(cases.unit_lengths(data)) == 300
+    (tmp_path / "in.jpg").write_bytes(data)
+    w = run_checker(checker, "decode", tmp_path / "in.jpg", tmp_path / "out.rgb", S).splitlines()[0].split()
+    f = dict(zip(w[0::2], (int(v) for v in w[1::2])))
+    assert f["status"] == f["serial"] != 0 and f["handed"] == 1 and (f["units"], f["long_units"]) == (300, 300), (name, f)
 
 
 @pytest.mark.parametrize("kw", [dict(subsampling=2, restart_marker_blocks=2), dict(subsampling=1, optimize=True), dict(subsampling=0)])
