@@ -874,6 +874,94 @@ size_t yv3_jpeg_workspace_bytes_ex(const yv3_jpeg_info* infos_host, int B, int e
  * argument checks before any launch, and YV3_EINVAL for an unknown `entropy`; no allocation, no synchronisation. */
 int yv3_jpeg_decode_batch_ex(const yv3_jpeg_batch_desc* desc, int entropy, int* handed_over, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Progressive files (SOF2; csrc/jpeg_prog.h), opt-in at every layer ----------------------------
+ * yv3_jpeg_parse_ex with YV3_JPEGP_ACCEPT describes an accepted progressive file in a yv3_jpeg_prog record; its yv3_jpeg_info
+ * keeps reason = YV3_JPEG_PROGRESSIVE, so every entry above still refuses the file.  yv3_jpeg_decode_batch_prog takes a batch
+ * that mixes baseline and progressive images.  (These names carry the prefix YV3_JPEGP_: the YV3_JPEG_ codes above are a
+ * closed list.) */
+#define YV3_JPEGP_ACCEPT       1   /* the `accept` flag of yv3_jpeg_parse_ex: progressive files                  */
+#define YV3_JPEGP_MAX_SCANS    64  /* a grey file with one scan per coefficient fits                             */
+#define YV3_JPEGP_MAX_TABLES   66  /* every scan's tables fit: 63 AC scans, one table each, and three DC tables  */
+
+/* further yv3_jpeg_info.reason codes, given by yv3_jpeg_parse_ex with YV3_JPEGP_ACCEPT alone */
+#define YV3_JPEGP_SCAN         12  /* a scan header outside the accepted forms: Ss = 0 with Se != 0, an interleaved AC scan,
+                                      Se < Ss or Se > 63, Al > 13, Ah neither 0 nor Al + 1, components repeated or out of order */
+#define YV3_JPEGP_SCRIPT       13  /* the scans are no complete progression: a repeated first scan, a refinement whose Ah is not
+                                      the Al before it, AC before DC, a band missing or not coded down to Al = 0 at EOI, or a
+                                      segment between scans that is none of DHT, DRI, COM, APPn                               */
+#define YV3_JPEGP_CAPACITY     14  /* more than YV3_JPEGP_MAX_SCANS scans                                         */
+#define YV3_JPEGP_DQT          15  /* a quantisation table after the first SOS                                   */
+
+/* further status[b] codes of yv3_jpeg_decode_batch_prog */
+#define YV3_JPEGP_S_REFINE     11  /* a refinement scan's symbol whose size is neither 0 nor 1                    */
+#define YV3_JPEGP_S_VALUE      12  /* an AC coefficient outside 16 bits after the shift or a correction           */
+
+typedef struct yv3_jpegp_scan {
+    long long offset, length;         /* the scan's entropy-coded bytes, from the start of the file                            */
+    int restart_interval;             /* the DRI in force at this SOS: MCUs (interleaved) or the component's own blocks         */
+    int pad0;
+    unsigned char ns;                 /* components in the scan, 1..3                                                          */
+    unsigned char ss, se, ah, al;
+    unsigned char level;              /* 1..nlevels: yv3_jpegp_levels' (csrc/jpeg_prog.h), recomputed on the device            */
+    unsigned char comp[3];            /* component indices, ascending                                                          */
+    unsigned char tab[3];             /* per component: index into tables[] -- the DC table of a first DC scan, the AC table
+                                         of an AC scan (tab[0]); unused entries are 255                                        */
+    unsigned char pad1[4];
+} yv3_jpegp_scan;
+
+typedef struct yv3_jpegp_table { unsigned char counts[16], values[256]; } yv3_jpegp_table;
+
+/* One image's progressive record, FIXED SIZE (a batch's records are an array; about 20 KB each, and only progressive images
+ * carry one).  tables[] holds each Huffman specification some scan uses, as it was in force at that scan's SOS: a table that
+ * is redefined between two scans takes two entries. */
+typedef struct yv3_jpeg_prog {
+    int accepted;                     /* 1: a progressive file the decoder takes; 0: none (every other field is then 0)        */
+    int nscans, ntables, nlevels;
+    yv3_jpegp_scan scans[YV3_JPEGP_MAX_SCANS];
+    yv3_jpegp_table tables[YV3_JPEGP_MAX_TABLES];
+} yv3_jpeg_prog;
+
+/* yv3_jpeg_parse with an `accept` flag word and a progressive record (prog may be null when accept is 0).  accept = 0: *out is
+ * yv3_jpeg_parse's, byte for byte, and *prog is zeroed.  With YV3_JPEGP_ACCEPT a SOF2 file is walked to its EOI: accepted
+ * (prog->accepted = 1, out->reason stays YV3_JPEG_PROGRESSIVE) when the frame obeys the baseline frame rules and the scans are a
+ * complete progression libjpeg decodes without a warning -- every scan of the forms in YV3_JPEGP_SCAN's comment with its tables
+ * defined at its SOS, every coefficient of every component coded first with Ah = 0 and then down to Al = 0, no DQT after the
+ * first SOS, nothing but EOI (or the end of a truncated file) after the last scan; otherwise out->reason says why.  out's
+ * frame fields (size, components, sampling, quantisers, has_exif) are valid for an accepted file; its scan and Huffman fields
+ * are not meaningful.  No byte outside data[0, n) is read.  For such a record yv3_jpeg_workspace_bytes and _ex answer as for
+ * any refused record -- the image adds nothing, so the result is the slot table of the batch (256 for B = 1), not 0 -- and the
+ * older decode entries answer YV3_ESHAPE. */
+int yv3_jpeg_parse_ex(const unsigned char* data, size_t n, int accept, yv3_jpeg_info* out, yv3_jpeg_prog* prog);
+
+/* yv3_jpeg_batch_desc plus the progressive records.  prog_of[b] = index of image b's record in progs, or -1 for a baseline
+ * image (whose info record has reason 0). */
+typedef struct yv3_jpeg_batch_desc_prog {
+    yv3_jpeg_batch_desc base;
+    const yv3_jpeg_prog* progs;       /* device [P]                                                                            */
+    const yv3_jpeg_prog* progs_host;  /* host [P]: the same records                                                            */
+    const int* prog_of;               /* device [B]                                                                            */
+    const int* prog_of_host;          /* host [B]                                                                              */
+    int P;                            /* 0: no progressive image; progs* may then be null                                      */
+} yv3_jpeg_batch_desc_prog;
+
+/* Host only: workspace bytes of yv3_jpeg_decode_batch_prog.  Without a progressive image it is yv3_jpeg_workspace_bytes_ex's;
+ * with one, a device copy of every info record and the restart offsets of every scan are added.  0 on a bad argument. */
+size_t yv3_jpeg_workspace_bytes_prog(const yv3_jpeg_info* infos_host, const int* prog_of_host, const yv3_jpeg_prog* progs_host, int P,
+                                     int B, int entropy);
+
+/* yv3_jpeg_decode_batch_ex for a batch that may hold progressive images.  Baseline images take the entropy stage `entropy`
+ * names, exactly as there; progressive images take entropy_prog_kernel (one workgroup per image; scans that code different
+ * coefficients run side by side, level by level), which is not launched when P is 0 -- the call is then
+ * yv3_jpeg_decode_batch_ex itself.  The device records are re-checked before any kernel trusts them; the status contract is
+ * the same: status 0 means libjpeg's bytes.  YV3_ESHAPE also for a prog_of_host entry outside [-1, P), a baseline record with
+ * reason != 0 and a progressive record yv3_jpeg_parse_ex cannot have produced. */
+int yv3_jpeg_decode_batch_prog(const yv3_jpeg_batch_desc_prog* desc, int entropy, int* handed_over, void* ws, size_t ws_bytes,
+                               void* stream);
+
+/* The kernels yv3_jpeg_decode_batch, _ex and _prog have launched in this process so far, counted where they are launched (for
+ * tests and measurements: a batch without a progressive image adds four, one with a progressive image five). */
+long long yv3_jpeg_launch_count(void);
+
 /* ------------------------------------------------------------------------------------------
  * The update step (csrc/optim.hip; yolo_v3_amd/optim.py): torch's clip_grad_norm_ and torch.optim.SGD over a list of fp32
  * tensors, a few launches for the whole list.  The list arguments (g, p, buf, n) are HOST arrays of `count` device pointers /

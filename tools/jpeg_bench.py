@@ -14,6 +14,14 @@ stage's kernel is the instance entropy_kernel<1>).  One JSON line; with --entrop
 "serial" and "parallel".
 
     python tools/jpeg_bench.py --bs 64 --src synth [--entropy serial|parallel|both] [--rounds 9] [--warmup 2]
+
+--progressive: both sources' pixels are encoded again by PIL at quality 90, 4:2:0, once with ``progressive=True`` and once as the
+baseline twin, and for each source at bs = 16 / 64 / 256, all in this one run and interleaved round by round: decode_batch with
+``progressive=True`` on the progressive bytes (wall and device time), PIL on one and on eight threads on the same progressive
+bytes, and the serial baseline stage on the twins; then, from one profiled call each, the device time of entropy_prog_kernel
+and of the twins' entropy_kernel<0>.  One JSON line per (source, batch size).
+
+    python tools/jpeg_bench.py --progressive [--rounds 5] [--warmup 1]
 """
 import argparse
 import io
@@ -33,7 +41,7 @@ sys.path.insert(0, REPO)
 from yolo_v3_amd import evaluate, jpeg        # noqa: E402
 from tools import loader_bench                # noqa: E402
 
-KERNELS = ("layout_kernel", "entropy_kernel<0>", "entropy_kernel<1>", "entropy_kernel", "idct_kernel", "colour_kernel")
+KERNELS = ("layout_prog_kernel", "entropy_prog_kernel", "layout_kernel", "entropy_kernel<0>", "entropy_kernel<1>", "entropy_kernel", "idct_kernel", "colour_kernel")
 
 
 def sources(kind, bs):
@@ -45,12 +53,12 @@ def sources(kind, bs):
     return [files[i % len(files)] for i in range(bs)]
 
 
-def gpu_pass(datas, entropy="serial"):
+def gpu_pass(datas, entropy="serial", progressive=False):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     e0.record()
-    out = jpeg.decode_batch(datas, entropy=entropy)
+    out = jpeg.decode_batch(datas, entropy=entropy, progressive=progressive)
     e1.record()
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
@@ -66,12 +74,12 @@ def pil_pass(datas, pool):
     return (time.perf_counter() - t0) * 1e3
 
 
-def kernel_split(datas, entropy="serial"):
+def kernel_split(datas, entropy="serial", progressive=False):
     """Device microseconds per kernel of one call, or None where the profiler gives no device times."""
     try:
         from torch.profiler import profile, ProfilerActivity
         with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            jpeg.decode_batch(datas, entropy=entropy)
+            jpeg.decode_batch(datas, entropy=entropy, progressive=progressive)
             torch.cuda.synchronize()
         split = {}
         for ev in prof.key_averages():
@@ -87,6 +95,50 @@ def kernel_split(datas, entropy="serial"):
         return {"error": repr(e)[:200]}
 
 
+def encode_again(data, progressive):
+    from PIL import Image
+    b = io.BytesIO()
+    Image.fromarray(evaluate.read_image_rgb(io.BytesIO(data))).save(b, "JPEG", quality=90, subsampling=2, progressive=progressive)
+    return b.getvalue()
+
+
+def progressive_main(a):
+    rate = lambda n, ms: round(n * 1e3 / ms, 1)
+    for src in ("synth", "photo"):
+        base = [(encode_again(d, True), encode_again(d, False)) for d in sources(src, 1 if src == "photo" else 64)]
+        for bs in (16, 64, 256):
+            prog = [base[i % len(base)][0] for i in range(bs)]
+            twin = [base[i % len(base)][1] for i in range(bs)]
+            ref = evaluate.read_image_rgb(io.BytesIO(prog[0]))
+            assert np.array_equal(jpeg.decode_batch(prog[:1], progressive=True)[0].cpu().numpy(), ref)
+            assert np.array_equal(jpeg.decode_batch(twin[:1])[0].cpu().numpy(), ref)
+            samples = {k: [] for k in ("prog_wall", "prog_device", "twin_wall", "twin_device", "pil_1", "pil_8")}
+            with ThreadPoolExecutor(max_workers=8) as pool:
+                for r in range(a.warmup + a.rounds):
+                    got = {}
+                    got["prog_wall"], got["prog_device"] = gpu_pass(prog, progressive=True)
+                    got["twin_wall"], got["twin_device"] = gpu_pass(twin)
+                    got["pil_1"] = pil_pass(prog, None)
+                    got["pil_8"] = pil_pass(prog, pool)
+                    if r >= a.warmup:
+                        for k, v in got.items():
+                            samples[k].append(v)
+            med = {k: float(np.median(v)) for k, v in samples.items()}
+            info, rec = jpeg.parse_ex(prog[0])
+            coded = int(np.mean([sum(r.scans[i].length for i in range(r.nscans)) for r in (jpeg.parse_ex(d)[1] for d in prog)]))
+            out = {"src": src, "shape": list(ref.shape[:2]), "bs": bs, "progressive_file_bytes": int(np.mean([len(d) for d in prog])),
+                   "twin_file_bytes": int(np.mean([len(d) for d in twin])), "coded_bytes": coded, "scans": rec.nscans,
+                   "levels": rec.nlevels, "rounds": a.rounds}
+            for k in samples:
+                out[k + "_ms"] = round(med[k], 3)
+                out["min_max_" + k + "_ms"] = [round(min(samples[k]), 3), round(max(samples[k]), 3)]
+            for k in ("prog_wall", "twin_wall", "pil_1", "pil_8"):
+                out[k + "_images_per_s"] = rate(bs, med[k])
+            out["prog_kernel_us"] = kernel_split(prog, progressive=True)
+            out["twin_kernel_us"] = kernel_split(twin)
+            print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bs", type=int, default=64)
@@ -94,7 +146,10 @@ def main():
     ap.add_argument("--entropy", choices=("serial", "parallel", "both"), default="serial")
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--progressive", action="store_true")
     a = ap.parse_args()
+    if a.progressive:
+        return progressive_main(a)
     modes = ("serial", "parallel") if a.entropy == "both" else (a.entropy,)
     datas = sources(a.src, a.bs)
     ref = evaluate.read_image_rgb(io.BytesIO(datas[0]))

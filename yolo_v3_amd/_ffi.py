@@ -97,6 +97,10 @@ JPEG_OK, JPEG_NOT_JPEG, JPEG_MALFORMED, JPEG_PROGRESSIVE, JPEG_SOF, JPEG_PRECISI
 JPEG_COLORSPACE, JPEG_SAMPLING, JPEG_MULTISCAN, JPEG_TABLES, JPEG_SIZE = range(7, 12)
 (JPEG_S_INFO, JPEG_S_BOUNDS, JPEG_S_HUFFTABLE, JPEG_S_CODE, JPEG_S_OVERRUN, JPEG_S_COEF, JPEG_S_MARKER, JPEG_S_EXTRA,
  JPEG_S_DC, JPEG_S_RANGE) = range(1, 11)
+# progressive files (the YV3_JPEGP_ names of include/yv3.h): the accept flag, the record's capacities, further reasons and statuses
+JPEGP_ACCEPT, JPEGP_MAX_SCANS, JPEGP_MAX_TABLES = 1, 64, 66
+JPEGP_SCAN, JPEGP_SCRIPT, JPEGP_CAPACITY, JPEGP_DQT = range(12, 16)
+JPEGP_S_REFINE, JPEGP_S_VALUE = 11, 12
 
 
 class JpegInfo(ctypes.Structure):
@@ -117,6 +121,30 @@ class JpegBatchDesc(ctypes.Structure):
                 ("infos", c_void_p), ("infos_host", c_void_p),
                 ("dst", c_void_p), ("dst_bytes", c_longlong), ("dst_offsets", c_void_p),
                 ("status", c_void_p), ("B", c_int)]
+
+
+class JpegpScan(ctypes.Structure):
+    """struct yv3_jpegp_scan (include/yv3.h)."""
+    _fields_ = [("offset", c_longlong), ("length", c_longlong), ("restart_interval", c_int), ("pad0", c_int),
+                ("ns", ctypes.c_ubyte), ("ss", ctypes.c_ubyte), ("se", ctypes.c_ubyte), ("ah", ctypes.c_ubyte), ("al", ctypes.c_ubyte),
+                ("level", ctypes.c_ubyte), ("comp", ctypes.c_ubyte * 3), ("tab", ctypes.c_ubyte * 3), ("pad1", ctypes.c_ubyte * 4)]
+
+
+class JpegpTable(ctypes.Structure):
+    """struct yv3_jpegp_table (include/yv3.h)."""
+    _fields_ = [("counts", ctypes.c_ubyte * 16), ("values", ctypes.c_ubyte * 256)]
+
+
+class JpegProg(ctypes.Structure):
+    """struct yv3_jpeg_prog (include/yv3.h)."""
+    _fields_ = [("accepted", c_int), ("nscans", c_int), ("ntables", c_int), ("nlevels", c_int),
+                ("scans", JpegpScan * JPEGP_MAX_SCANS), ("tables", JpegpTable * JPEGP_MAX_TABLES)]
+
+
+class JpegBatchDescProg(ctypes.Structure):
+    """struct yv3_jpeg_batch_desc_prog (include/yv3.h)."""
+    _fields_ = [("base", JpegBatchDesc), ("progs", c_void_p), ("progs_host", c_void_p), ("prog_of", c_void_p),
+                ("prog_of_host", c_void_p), ("P", c_int)]
 
 
 _SIGNATURES = {
@@ -200,6 +228,10 @@ _SIGNATURES = {
     "yv3_jpeg_decode_batch": (c_int, [ctypes.POINTER(JpegBatchDesc), c_void_p, c_size_t, c_void_p]),
     "yv3_jpeg_workspace_bytes_ex": (c_size_t, [c_void_p, c_int, c_int]),
     "yv3_jpeg_decode_batch_ex": (c_int, [ctypes.POINTER(JpegBatchDesc), c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "yv3_jpeg_parse_ex": (c_int, [c_void_p, c_size_t, c_int, ctypes.POINTER(JpegInfo), ctypes.POINTER(JpegProg)]),
+    "yv3_jpeg_workspace_bytes_prog": (c_size_t, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int]),
+    "yv3_jpeg_decode_batch_prog": (c_int, [ctypes.POINTER(JpegBatchDescProg), c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "yv3_jpeg_launch_count": (c_longlong, []),
     "yv3_optim_chunk": (c_int, []),
     "yv3_grad_sumsq": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_longlong, c_void_p]),
     "yv3_clip_coef": (c_int, [c_void_p, c_longlong, c_float, c_void_p, c_void_p]),

@@ -345,11 +345,11 @@ def _load_source(img_path, lab_path):
     return evaluate.read_image_rgb(img_path), read_labels(lab_path)
 
 
-def _load_bytes(img_path, lab_path):
+def _load_bytes(img_path, lab_path, progressive=False):
     """``decode="gpu"``: a worker only reads the file and parses its header (a file the GPU decoder does not take is decoded
     here by `read_image_rgb`, as in ``decode="pil"``; its exception, if any, is raised at its batch)."""
     from . import jpeg
-    src = jpeg.Source(img_path)
+    src = jpeg.Source(img_path, progressive=progressive)
     if src.error is not None:
         raise src.error
     return src, read_labels(lab_path)
@@ -379,7 +379,9 @@ class TrainBatches:
     (measured against a step that fills every CU the decode did not overlap with it: DESIGN.md section 8f); with ``cache_bytes``
     the kernels write straight into the arena.  Files the GPU decoder does not take go through `read_image_rgb` as before.  The
     switch is not part of a ``state_dict``'s config: both settings give the same bits.  ``entropy`` (``"serial"`` by default, or
-    ``"parallel"``) is passed on to `jpeg.submit`: the decoder's entropy stage, which changes no bit either.
+    ``"parallel"``) is passed on to `jpeg.submit`: the decoder's entropy stage, which changes no bit either.  ``progressive=True``
+    (with ``decode="gpu"``) is passed on too: progressive files the parser accepts are decoded on the GPU instead of by
+    `read_image_rgb` -- the same bits again, so it is no part of a ``state_dict``'s config either.
 
     ``extra=True``: the reference's ``ExtraAugmentations`` in front of everything else, as ``Compose([ExtraAugmentations(),
     IaaAugmentations([...]), ToTensor()])`` has them: every batch is ``augment_batch(extra_augment_batch(images,
@@ -389,12 +391,14 @@ class TrainBatches:
     ``state_dict()`` / ``load_state_dict()`` resume between two batches with the same data order."""
 
     def __init__(self, list_file, batch_size, dim, seed, shuffle=True, max_labels=MAX_LABELS, multiscale=None, dim_interval=10,
-                 workers=0, prefetch=2, cache_bytes=0, decode="pil", extra=False, entropy="serial", **aug):
+                 workers=0, prefetch=2, cache_bytes=0, decode="pil", extra=False, entropy="serial", progressive=False,
+                 **aug):
         if decode not in ("pil", "gpu"):
             raise ValueError("decode must be 'pil' or 'gpu'")
         if entropy not in ("serial", "parallel"):
             raise ValueError("entropy must be 'serial' or 'parallel'")
         self.decode, self._side, self.extra, self.entropy = decode, None, bool(extra), entropy
+        self.progressive = bool(progressive)
         with open(list_file, 'r') as f:
             self.img_list = [line.strip() for line in f.readlines() if line.strip()]
         self.label_list = [label_path(p) for p in self.img_list]
@@ -470,7 +474,12 @@ class TrainBatches:
         order, seeds, dims = epoch_schedule(self.seed, epoch, n, bs, self.shuffle, self.multiscale, self.dim_interval)
         n_batches = len(self)
         pool, pending = None, {}                         # pending: batch -> one future (or None: resident) per image
-        load = _load_bytes if self.decode == "gpu" else _load_source
+        load = _load_source
+        if self.decode == "gpu":
+            progressive = self.progressive
+
+            def load(img_path, lab_path):
+                return _load_bytes(img_path, lab_path, progressive)
         if self.workers > 0:
             from concurrent.futures import ThreadPoolExecutor
             pool = ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix="yv3-decode")
@@ -549,9 +558,10 @@ class TrainBatches:
         jobs = []
         if admitted:
             jobs.append((admitted, jpeg.submit([images[i] for i in admitted], stream=self._side, dst=(self._arena, offsets),
-                                                   entropy=self.entropy)))
+                                                   entropy=self.entropy, progressive=self.progressive)))
         if rest:
-            jobs.append((rest, jpeg.submit([images[i] for i in rest], stream=self._side, entropy=self.entropy)))
+            jobs.append((rest, jpeg.submit([images[i] for i in rest], stream=self._side, entropy=self.entropy,
+                                           progressive=self.progressive)))
         return batch, admitted, jobs, self._pos
 
     def _complete(self, launched):

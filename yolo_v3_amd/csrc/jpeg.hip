@@ -17,14 +17,30 @@
 //                    status to YV3_JPEG_S_RANGE
 //   colour_kernel    one lane per 4 output pixels: fancy upsampling of the chroma planes (h2v1 / h2v2), YCbCr -> RGB, 12 bytes
 //                    as three dword stores where the destination allows it
+//   layout_prog_kernel, entropy_prog_kernel   yv3_jpeg_decode_batch_prog with progressive images in the batch (jpeg_prog.h, DESIGN.md
+//                    section 8f.2): the layout kernel's sibling re-checks the progressive device records and hands the later
+//                    kernels frame records of its own making; one workgroup per progressive image decodes its scans level by
+//                    level, independent scans side by side.  Baseline images of such a batch take entropy_kernel as always
 // An image whose status is not 0 after any stage is skipped by the later ones: its destination bytes are not written.
 // (compiled with -ffp-contract=off like the other non-MFMA files; there is no floating point here)
 #include "yv3_common.h"
 #include "jpeg_parse.h"
 #include "jpeg_pixel.h"
 #include "jpeg_sync.h"
+#include "jpeg_prog.h"
+#include <atomic>
 
 namespace {
+
+// every kernel launch of this file is counted (yv3_jpeg_launch_count: what tests and measurements read)
+std::atomic<long long> g_launches{0};
+#define YV3_JPEG_LAUNCH(...)                                   \
+    do {                                                       \
+        hipLaunchKernelGGL(__VA_ARGS__);                       \
+        g_launches.fetch_add(1, std::memory_order_relaxed);    \
+    } while (0)
+
+static_assert(sizeof(yv3_jpeg_info) % 8 == 0, "layout_prog_kernel copies the records in 8-byte words");
 
 __global__ __launch_bounds__(256) void layout_kernel(const yv3_jpeg_info* __restrict__ infos, const long long* __restrict__ src_offsets,
                                                      long long src_bytes, const long long* __restrict__ dst_offsets, long long dst_bytes,
@@ -44,7 +60,7 @@ __global__ __launch_bounds__(256) void layout_kernel(const yv3_jpeg_info* __rest
         s.coef_off = code ? 0 : g.coef_bytes;              // sizes for now; thread 0 turns them into offsets below
         s.plane_off = code ? 0 : g.plane_bytes;
         s.unit_off = code ? 0 : g.unit_bytes;
-        s.status = code; s.pad = 0;
+        s.status = code; s.prog = 0;
         slots[b] = s;
     }
     __syncthreads();
@@ -213,7 +229,8 @@ __global__ __launch_bounds__(256) void entropy_kernel(const unsigned char* __res
     const int b = blockIdx.x, t = threadIdx.x;
     const yv3_jpeg_slot slot = slots[b];
     if (SYNC && handed && t == 0) handed[b] = 0;           // whichever way the image leaves this kernel
-    if (slot.status) return;                               // the whole workgroup: layout_kernel refused the image
+    if (slot.status || slot.prog) return;                  // the whole workgroup: layout_kernel refused the image, or it is
+                                                           // entropy_prog_kernel's
     const yv3_jpeg_info* f = infos + b;
     if (t == 0) { s_geom = yv3_jpeg_geometry(f, &g); s_status = 0; s_total = 0; }
     if (t < 8) sel[t] = t < 4 ? f->td[t] : f->ta[t - 4];
@@ -311,6 +328,223 @@ __global__ __launch_bounds__(256) void entropy_kernel(const unsigned char* __res
                 __syncthreads();
             }
             if (t == 0 && handed && s_handed) handed[b] = s_handed;
+        }
+    }
+    __syncthreads();
+    if (t == 0) { slots[b].status = s_status; status[b] = s_status; }
+}
+
+// layout_kernel for yv3_jpeg_decode_batch_prog with progressive images in the batch.  The info records are copied into the
+// workspace (`frames`), where a progressive image's becomes a frame record (yv3_jpegp_as_frame): the later kernels read the
+// copy.  A progressive image's DEVICE record is re-checked here -- its index, every scan's Ss / Se / Ah / Al, components and
+// table indices (yv3_jpegp_check), every scan's byte range against the source buffer in 64 bits -- and its share of restart
+// offsets is sized from the unit counts this kernel derives itself.
+__global__ __launch_bounds__(256) void layout_prog_kernel(const yv3_jpeg_info* __restrict__ infos, const yv3_jpeg_prog* __restrict__ progs,
+                                                          const int* __restrict__ prog_of, int P, const long long* __restrict__ src_offsets,
+                                                          long long src_bytes, const long long* __restrict__ dst_offsets, long long dst_bytes,
+                                                          int B, yv3_jpeg_slot* __restrict__ slots, yv3_jpeg_info* __restrict__ frames,
+                                                          long long ws_bytes, int* __restrict__ status) {
+    const long long nwords = (long long)B * (long long)(sizeof(yv3_jpeg_info) / 8);       // the record is a multiple of 8 bytes
+    for (long long i = threadIdx.x; i < nwords; i += blockDim.x) ((long long*)frames)[i] = ((const long long*)infos)[i];
+    __syncthreads();
+    for (int b = threadIdx.x; b < B; b += blockDim.x) {
+        yv3_jpeg_geom g;
+        yv3_jpeg_info* f = frames + b;
+        const int pi = prog_of[b];
+        int code;
+        if (pi < 0) {
+            code = pi == -1 ? yv3_jpeg_geometry(f, &g) : YV3_JPEG_S_INFO;
+        } else if (pi >= P || f->reason != YV3_JPEG_PROGRESSIVE) {
+            code = YV3_JPEG_S_INFO;
+        } else {
+            yv3_jpegp_as_frame(f);
+            code = yv3_jpegp_geometry(f, progs + pi, &g);
+        }
+        if (!code) {
+            const long long so = src_offsets[b], dof = dst_offsets[b], n3 = (long long)f->width * f->height * 3;
+            bool src_ok = so >= 0 && so <= src_bytes;
+            if (src_ok && pi < 0) {
+                src_ok = f->scan_offset <= src_bytes - so && f->scan_length <= src_bytes - so - f->scan_offset && f->scan_length <= 0x7fffffffLL;
+            } else if (src_ok) {
+                const yv3_jpeg_prog* p = progs + pi;
+                for (int i = 0; i < p->nscans; ++i) {        // offset, length >= 0 and length < 2^31: yv3_jpegp_check
+                    const long long o = p->scans[i].offset, l = p->scans[i].length;
+                    src_ok = src_ok && o <= src_bytes - so && l <= src_bytes - so - o;
+                }
+            }
+            const bool dst_ok = dof >= 0 && dof <= dst_bytes && n3 <= dst_bytes - dof;
+            if (!src_ok || !dst_ok) code = YV3_JPEG_S_BOUNDS;
+        }
+        yv3_jpeg_slot s;
+        s.coef_off = code ? 0 : g.coef_bytes;
+        s.plane_off = code ? 0 : g.plane_bytes;
+        s.unit_off = code ? 0 : g.unit_bytes;
+        s.status = code; s.prog = pi >= 0;
+        slots[b] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long pos = yv3_jpeg_round256((long long)B * (long long)sizeof(yv3_jpeg_slot)) +
+                        yv3_jpeg_round256((long long)B * (long long)sizeof(yv3_jpeg_info));
+        for (int b = 0; b < B; ++b) {
+            yv3_jpeg_slot s = slots[b];
+            if (!s.status) {
+                const long long total = s.coef_off + s.plane_off + s.unit_off;
+                if (pos > ws_bytes || total > ws_bytes - pos) {
+                    s.status = YV3_JPEG_S_BOUNDS;
+                } else {
+                    const long long c = pos, p = pos + s.coef_off, u = p + s.plane_off;
+                    s.coef_off = c; s.plane_off = p; s.unit_off = u;
+                    pos += total;
+                }
+                slots[b] = s;
+            }
+            status[b] = s.status;
+        }
+    }
+}
+
+// The entropy stage of a progressive image: one workgroup per image.  Lane 0 derives the geometry, every scan's unit count and
+// the level of every scan (yv3_jpegp_levels) from the device record layout_prog_kernel checked; all lanes zero the coefficients
+// and find every scan's restart markers.  Then level by level: lane 0 lists the level's scans and table slots, up to eight
+// lanes build the level's Huffman tables in LDS, and the level's units -- all independent: they code different coefficients
+// or different blocks -- are dealt to lanes across the four waves first (longest first, in a snake: unit i of a round of 256
+// goes to wave i mod 4, or 3 - i mod 4 on odd rows of four, lane i / 4), so that a few long scans do not share one wave; a
+// level with more units than lanes takes several rounds.  Levels
+// are separated by barriers; every loop bound around a barrier is read from LDS after a barrier, the same for all lanes.
+// `frames`: layout_prog_kernel's copies.
+__global__ __launch_bounds__(256) void entropy_prog_kernel(const unsigned char* __restrict__ src, const long long* __restrict__ src_offsets,
+                                                           const yv3_jpeg_info* __restrict__ frames, const yv3_jpeg_prog* __restrict__ progs,
+                                                           const int* __restrict__ prog_of, yv3_jpeg_slot* __restrict__ slots,
+                                                           unsigned char* __restrict__ ws, int* __restrict__ status) {
+    __shared__ yv3_jpeg_hufftab tabs[YV3_JPEGP_LEVEL_TABLES];
+    __shared__ yv3_jpeg_geom g;
+    __shared__ int counts[256];
+    __shared__ int s_units[YV3_JPEGP_MAX_SCANS], s_first[YV3_JPEGP_MAX_SCANS], s_cum[YV3_JPEGP_MAX_SCANS + 1];
+    __shared__ unsigned char s_level[YV3_JPEGP_MAX_SCANS], s_list[YV3_JPEGP_MAX_SCANS], s_slot[YV3_JPEGP_MAX_SCANS];
+    __shared__ unsigned char s_tabsrc[YV3_JPEGP_LEVEL_TABLES], s_tabdc[YV3_JPEGP_LEVEL_TABLES];
+    __shared__ int s_geom, s_status, s_total, s_nscans, s_nlevels, s_nlist, s_ntabs;
+    __shared__ unsigned char natural[64];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const yv3_jpeg_slot slot = slots[b];
+    if (!slot.prog || slot.status) return;                 // the whole workgroup: a baseline image, or one layout_prog_kernel refused
+    const yv3_jpeg_info* f = frames + b;
+    const yv3_jpeg_prog* p = progs + prog_of[b];           // 0 <= prog_of[b] < P: layout_prog_kernel
+    if (t == 0) {
+        s_geom = yv3_jpegp_geometry(f, p, &g);
+        s_status = 0; s_total = 0; s_nscans = 0; s_nlevels = 0;
+        if (!s_geom) {
+            s_nscans = p->nscans;
+            int first = 0;
+            for (int i = 0; i < p->nscans; ++i) {
+                const yv3_jpegp_scan* sc = p->scans + i;
+                s_units[i] = yv3_jpegp_scan_units(yv3_jpegp_scan_items(&g, sc->ns, sc->comp[0]), sc->restart_interval);
+                s_first[i] = first;
+                first += s_units[i];                           // <= the units the share was sized for: the same sum
+            }
+            s_nlevels = yv3_jpegp_levels(p, s_level);
+            for (int i = 0; i < p->nscans; ++i)
+                if (s_level[i] != p->scans[i].level) s_geom = YV3_JPEG_S_INFO;      // the parser's schedule is this one
+        }
+    }
+    if (t < 64) natural[t] = (unsigned char)yv3_jpeg_natural(t);
+    __syncthreads();
+    if (s_geom) {
+        if (t == 0) { slots[b].status = s_geom; status[b] = s_geom; }
+        return;
+    }
+    int4* cz = (int4*)(ws + slot.coef_off);
+    const long long n16 = (long long)g.nblocks * 8;
+    for (long long i = t; i < n16; i += 256) cz[i] = make_int4(0, 0, 0, 0);
+    const unsigned char* file = src + src_offsets[b];
+    int* marks = (int*)(ws + slot.unit_off);               // scan i: [s_first[i], s_first[i] + s_units[i] - 1) used
+    const int nscans = s_nscans, nlevels = s_nlevels;
+    for (int i = 0; i < nscans; ++i) {                     // the restart markers of every scan that has some
+        const int nunits = s_units[i];
+        if (nunits < 2) continue;                          // (the same for every lane: read from LDS after a barrier)
+        const unsigned char* scan = file + p->scans[i].offset;
+        const int len = (int)p->scans[i].length;
+        const int chunk = (len + 255) / 256;
+        const long long lo = (long long)t * chunk;
+        const long long hi = lo + chunk < len ? lo + chunk : len;
+        int cnt = 0;
+        for (long long k = lo; k < hi && k + 1 < len; ++k)
+            if (scan[k] == 0xFF && (scan[k + 1] & 0xF8) == 0xD0) ++cnt;
+        counts[t] = cnt;
+        __syncthreads();
+        if (t == 0) {
+            int run = 0;
+            for (int k = 0; k < 256; ++k) { const int c = counts[k]; counts[k] = run; run += c; }
+            s_total = run;
+        }
+        __syncthreads();
+        if (s_total != nunits - 1) {
+            if (t == 0) atomicMax(&s_status, YV3_JPEG_S_MARKER);
+        } else {
+            int k = counts[t];
+            int* m = marks + s_first[i];
+            for (long long q = lo; q < hi && q + 1 < len; ++q)
+                if (scan[q] == 0xFF && (scan[q + 1] & 0xF8) == 0xD0) { if (k < nunits - 1) m[k] = (int)q; ++k; }
+        }
+        __syncthreads();                                   // counts[] and s_total are free for the next scan
+    }
+    short* coef = (short*)(ws + slot.coef_off);
+    for (int lev = 1; lev <= nlevels; ++lev) {
+        __syncthreads();                                   // the level before: its coefficients, and its reads of the lists
+        if (t == 0) {
+            int n = 0, nt = 0, cum = 0;
+            for (int i = 0; i < nscans; ++i) {             // the level's scans, the most bytes per unit first
+                if (s_level[i] != lev) continue;
+                const yv3_jpegp_scan* sc = p->scans + i;
+                const long long key = sc->length / s_units[i];
+                int j = n++;
+                while (j > 0 && p->scans[s_list[j - 1]].length / s_units[s_list[j - 1]] < key) { s_list[j] = s_list[j - 1]; --j; }
+                s_list[j] = (unsigned char)i;
+                s_slot[i] = (unsigned char)nt;
+                const int need = yv3_jpegp_scan_tables(sc);
+                for (int q = 0; q < need && nt < YV3_JPEGP_LEVEL_TABLES; ++q) {          // (never more: yv3_jpegp_levels)
+                    s_tabsrc[nt] = sc->tab[q]; s_tabdc[nt] = sc->ss == 0; ++nt;
+                }
+            }
+            for (int j = 0; j < n; ++j) { s_cum[j] = cum; cum += s_units[s_list[j]]; }
+            s_cum[n] = cum; s_nlist = n; s_ntabs = nt;
+        }
+        __syncthreads();
+        if (t < s_ntabs) {
+            const yv3_jpegp_table* spec = p->tables + (s_tabsrc[t] < YV3_JPEGP_MAX_TABLES ? s_tabsrc[t] : 0);
+            const int code = yv3_jpeg_build_hufftab(spec->counts, spec->values, s_tabdc[t] ? 15 : 255, &tabs[t]);
+            if (code) atomicMax(&s_status, code);
+        }
+        __syncthreads();
+        const int before = s_status;                       // every lane reads it before any lane's decode can raise it
+        const int nlist = s_nlist, total = s_cum[nlist];
+        __syncthreads();
+        if (before) continue;                              // the image is lost; the remaining levels do nothing
+        // lane q of wave w takes unit 4q + w of a round, on odd q unit 4q + 3 - w: a snake, so that the fifth longest unit shares
+        // a wave with the fourth and not with the longest
+        for (int u = (t & 63) << 2 | ((t & 1) ? 3 - (t >> 6) : t >> 6); u < total; u += 256) {
+            int j = 0;
+            while (j + 1 < nlist && u >= s_cum[j + 1]) ++j;
+            const int i = s_list[j], k = u - s_cum[j], nunits = s_units[i];
+            const yv3_jpegp_scan sc = p->scans[i];
+            const int len = (int)sc.length;
+            const unsigned char* scan = file + sc.offset;
+            const int* m = marks + s_first[i];
+            long long begin = 0, end = len;
+            int code = 0;
+            if (k > 0) begin = (long long)m[k - 1] + 2;
+            if (k < nunits - 1) {
+                end = m[k];
+                if (end < 0 || end + 1 >= len || scan[end + 1] != 0xD0 + (k & 7)) code = YV3_JPEG_S_MARKER;
+            }
+            if (begin < 0 || begin > len || end < begin) code = YV3_JPEG_S_MARKER;
+            const int items = yv3_jpegp_scan_items(&g, sc.ns, sc.comp[0]);
+            const int per = sc.restart_interval ? sc.restart_interval : items;
+            const int i0 = k * per, i1 = items - i0 < per ? items : i0 + per;
+            const yv3_jpeg_hufftab* tp[3];
+            for (int q = 0; q < 3; ++q) tp[q] = tabs + ((s_slot[i] + q) & (YV3_JPEGP_LEVEL_TABLES - 1));
+            if (!code) code = yv3_jpegp_decode_unit(scan, begin, end, &g, &sc, tp, natural, i0, i1, coef, g.nblocks);
+            if (code) atomicMax(&s_status, code);
         }
     }
     __syncthreads();
@@ -421,21 +655,21 @@ extern "C" int yv3_jpeg_decode_batch_ex(const yv3_jpeg_batch_desc* desc, int ent
     hipStream_t s = (hipStream_t)stream;
     yv3_jpeg_slot* slots = (yv3_jpeg_slot*)ws;
     unsigned char* wsb = (unsigned char*)ws;
-    hipLaunchKernelGGL(layout_kernel, dim3(1), dim3(256), 0, s, desc->infos, desc->src_offsets, desc->src_bytes, desc->dst_offsets,
+    YV3_JPEG_LAUNCH(layout_kernel, dim3(1), dim3(256), 0, s, desc->infos, desc->src_offsets, desc->src_bytes, desc->dst_offsets,
                        desc->dst_bytes, B, slots, (long long)ws_bytes, desc->status);
     YV3_CHECK_LAUNCH();
     if (entropy == YV3_JPEG_ENTROPY_PARALLEL)
-        hipLaunchKernelGGL(entropy_kernel<1>, dim3(B), dim3(256), 0, s, desc->src, desc->src_offsets, desc->infos, slots, wsb, desc->status,
+        YV3_JPEG_LAUNCH(entropy_kernel<1>, dim3(B), dim3(256), 0, s, desc->src, desc->src_offsets, desc->infos, slots, wsb, desc->status,
                            handed_over);
     else
-        hipLaunchKernelGGL(entropy_kernel<0>, dim3(B), dim3(256), 0, s, desc->src, desc->src_offsets, desc->infos, slots, wsb, desc->status,
+        YV3_JPEG_LAUNCH(entropy_kernel<0>, dim3(B), dim3(256), 0, s, desc->src, desc->src_offsets, desc->infos, slots, wsb, desc->status,
                            (int*)0);
     YV3_CHECK_LAUNCH();
     const int gx_idct = (int)(max_blocks / 256 + 1 < 4096 ? max_blocks / 256 + 1 : 4096);
-    hipLaunchKernelGGL(idct_kernel, dim3(gx_idct, B), dim3(256), 0, s, desc->infos, slots, wsb, desc->status);
+    YV3_JPEG_LAUNCH(idct_kernel, dim3(gx_idct, B), dim3(256), 0, s, desc->infos, slots, wsb, desc->status);
     YV3_CHECK_LAUNCH();
     const int gx_col = (int)(max_groups / 256 + 1 < 4096 ? max_groups / 256 + 1 : 4096);
-    hipLaunchKernelGGL(colour_kernel, dim3(gx_col, B), dim3(256), 0, s, desc->infos, slots, (const unsigned char*)wsb, desc->dst,
+    YV3_JPEG_LAUNCH(colour_kernel, dim3(gx_col, B), dim3(256), 0, s, desc->infos, slots, (const unsigned char*)wsb, desc->dst,
                        desc->dst_offsets);
     YV3_CHECK_LAUNCH();
     return 0;
@@ -444,3 +678,48 @@ extern "C" int yv3_jpeg_decode_batch_ex(const yv3_jpeg_batch_desc* desc, int ent
 extern "C" int yv3_jpeg_decode_batch(const yv3_jpeg_batch_desc* desc, void* ws, size_t ws_bytes, void* stream) {
     return yv3_jpeg_decode_batch_ex(desc, YV3_JPEG_ENTROPY_SERIAL, 0, ws, ws_bytes, stream);
 }
+
+extern "C" int yv3_jpeg_decode_batch_prog(const yv3_jpeg_batch_desc_prog* desc, int entropy, int* handed_over, void* ws, size_t ws_bytes,
+                                          void* stream) {
+    if (!desc) return YV3_EINVAL;
+    if (desc->P == 0) return yv3_jpeg_decode_batch_ex(&desc->base, entropy, handed_over, ws, ws_bytes, stream);
+    if (entropy != YV3_JPEG_ENTROPY_SERIAL && entropy != YV3_JPEG_ENTROPY_PARALLEL) return YV3_EINVAL;
+    const yv3_jpeg_batch_desc* d = &desc->base;
+    if (!ws || ((uintptr_t)ws & 255) != 0) return YV3_EINVAL;
+    if (!d->src || !d->src_offsets || !d->infos || !d->infos_host || !d->dst || !d->dst_offsets || !d->status) return YV3_EINVAL;
+    if (!desc->progs || !desc->progs_host || !desc->prog_of || !desc->prog_of_host) return YV3_EINVAL;
+    const int B = d->B, P = desc->P;
+    if (B <= 0 || B > 65535 || P < 0 || P > 65535 || d->src_bytes <= 0 || d->dst_bytes <= 0) return YV3_EINVAL;
+    long long max_blocks = 1, max_groups = 1;
+    const size_t need = yv3_jpeg_batch_workspace_prog(d->infos_host, desc->prog_of_host, desc->progs_host, P, B, &max_blocks, &max_groups);
+    if (need == 0) return YV3_ESHAPE;
+    if (ws_bytes < need) return YV3_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    yv3_jpeg_slot* slots = (yv3_jpeg_slot*)ws;
+    unsigned char* wsb = (unsigned char*)ws;
+    yv3_jpeg_info* frames = (yv3_jpeg_info*)(wsb + yv3_jpeg_round256((long long)B * (long long)sizeof(yv3_jpeg_slot)));
+    YV3_JPEG_LAUNCH(layout_prog_kernel, dim3(1), dim3(256), 0, s, d->infos, desc->progs, desc->prog_of, P, d->src_offsets, d->src_bytes,
+                       d->dst_offsets, d->dst_bytes, B, slots, frames, (long long)ws_bytes, d->status);
+    YV3_CHECK_LAUNCH();
+    // (a batch of progressive images alone still takes this launch: its workgroups leave at once, after zeroing handed_over)
+    if (entropy == YV3_JPEG_ENTROPY_PARALLEL)
+        YV3_JPEG_LAUNCH(entropy_kernel<1>, dim3(B), dim3(256), 0, s, d->src, d->src_offsets, (const yv3_jpeg_info*)frames, slots, wsb,
+                           d->status, handed_over);
+    else
+        YV3_JPEG_LAUNCH(entropy_kernel<0>, dim3(B), dim3(256), 0, s, d->src, d->src_offsets, (const yv3_jpeg_info*)frames, slots, wsb,
+                           d->status, (int*)0);
+    YV3_CHECK_LAUNCH();
+    YV3_JPEG_LAUNCH(entropy_prog_kernel, dim3(B), dim3(256), 0, s, d->src, d->src_offsets, (const yv3_jpeg_info*)frames, desc->progs,
+                       desc->prog_of, slots, wsb, d->status);
+    YV3_CHECK_LAUNCH();
+    const int gx_idct = (int)(max_blocks / 256 + 1 < 4096 ? max_blocks / 256 + 1 : 4096);
+    YV3_JPEG_LAUNCH(idct_kernel, dim3(gx_idct, B), dim3(256), 0, s, (const yv3_jpeg_info*)frames, slots, wsb, d->status);
+    YV3_CHECK_LAUNCH();
+    const int gx_col = (int)(max_groups / 256 + 1 < 4096 ? max_groups / 256 + 1 : 4096);
+    YV3_JPEG_LAUNCH(colour_kernel, dim3(gx_col, B), dim3(256), 0, s, (const yv3_jpeg_info*)frames, slots, (const unsigned char*)wsb, d->dst,
+                       d->dst_offsets);
+    YV3_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" long long yv3_jpeg_launch_count(void) { return g_launches.load(std::memory_order_relaxed); }

@@ -242,7 +242,8 @@ def read_image_rgb(path):
         return np.asarray(im.convert("RGB"), dtype=np.uint8).copy()
 
 
-def generate_results_file(net, target_txt, classes_names, out, bs, dim, is_letterbox=False, decode="pil", entropy="serial"):
+def generate_results_file(net, target_txt, classes_names, out, bs, dim, is_letterbox=False, decode="pil", entropy="serial",
+                          progressive=False):
     """reference evaluate.py:208-219: the COCO-results file of a list of images -- ``target_txt`` is the reference's text file with one
     image path per line (a list of paths, or of ``(path, uint8 RGB [H,W,3] array)`` pairs, is accepted too).  Per batch of ``bs``
     images: the evaluation pipeline's input preparation on the GPU (``IaaLetterbox(dim)`` when ``is_letterbox`` else
@@ -251,7 +252,8 @@ def generate_results_file(net, target_txt, classes_names, out, bs, dim, is_lette
 
     ``decode="gpu"``: each batch's files are decoded by `jpeg.decode_batch` instead of `read_image_rgb` in this thread -- the same
     pixels (files the GPU decoder does not take still go through `read_image_rgb`), so the same file.  ``entropy`` is passed on to
-    it (``"serial"`` or ``"parallel"``; it changes no pixel)."""
+    it (``"serial"`` or ``"parallel"``; it changes no pixel), and so is ``progressive`` (True: accepted progressive files are
+    decoded on the GPU too)."""
     from .utils import letterbox_batch
     if decode not in ("pil", "gpu"):
         raise ValueError("decode must be 'pil' or 'gpu'")
@@ -270,7 +272,7 @@ def generate_results_file(net, target_txt, classes_names, out, bs, dim, is_lette
             paths = [c if isinstance(c, str) else c[0] for c in chunk]
             if decode == "gpu":
                 from . import jpeg
-                files = iter(jpeg.decode_batch([c for c in chunk if isinstance(c, str)], entropy=entropy))
+                files = iter(jpeg.decode_batch([c for c in chunk if isinstance(c, str)], entropy=entropy, progressive=progressive))
                 imgs = [next(files) if isinstance(c, str) else c[1] for c in chunk]
             else:
                 imgs = [read_image_rgb(c) if isinstance(c, str) else c[1] for c in chunk]

@@ -1,8 +1,9 @@
-"""Baseline JPEG decode on the GPU, bit for bit with PIL (libjpeg-turbo's defaults): ``csrc/jpeg_parse.cpp`` reads the headers on
-the host, ``csrc/jpeg.hip`` decodes a batch of files in four launches.
+"""JPEG decode on the GPU, bit for bit with PIL (libjpeg-turbo's defaults): ``csrc/jpeg_parse.cpp`` reads the headers on
+the host, ``csrc/jpeg.hip`` decodes a batch of files in four launches, five when ``progressive=True``
+and the batch holds a progressive file (section 8f.2).
 
 ``decode_batch(sources)`` returns what ``evaluate.read_image_rgb`` returns for every source, as GPU tensors.  A file the parser
-does not positively recognise (progressive, arithmetic, CMYK, 4:4:0 / 4:1:1, 12-bit, multi-scan, ... or no JPEG at all), a file
+does not positively recognise (progressive unless ``progressive=True``, arithmetic, CMYK, 4:4:0 / 4:1:1, 12-bit, multi-scan, ... or no JPEG at all), a file
 whose EXIF orientation is not 1, a file whose entropy-coded data the device reports as damaged or as holding coefficients outside
 the range in which every libjpeg computes the same bytes (``JPEG_S_RANGE``) and a file that ends without its EOI marker are
 decoded by ``read_image_rgb`` itself -- same pixels, same exceptions.  Nothing here is a default anywhere:
@@ -19,10 +20,13 @@ from . import _ffi
 
 _ALIGN = 256
 _INFO_BYTES = ctypes.sizeof(_ffi.JpegInfo)
+_PROG_BYTES = ctypes.sizeof(_ffi.JpegProg)
 
 ENTROPY = {"serial": 0, "parallel": 1}                    # enum YV3_JPEG_ENTROPY_* of include/yv3.h (no JPEG_* code of _ffi)
 
-counters = {"calls": 0, "uploads": 0, "upload_bytes": 0, "status_reads": 0, "fallbacks": 0}     # for measurements and tests
+# for measurements and tests; "launches": the kernels the calls launched, as the library counts them where it launches them
+# (yv3_jpeg_launch_count before and after the call); "prog_images": progressive images sent to the device
+counters = {"calls": 0, "uploads": 0, "upload_bytes": 0, "status_reads": 0, "fallbacks": 0, "launches": 0, "prog_images": 0}
 
 
 def _round_up(n, a=_ALIGN):
@@ -42,6 +46,15 @@ def parse(data):
     info = _ffi.JpegInfo()
     _ffi.check(_ffi.lib().yv3_jpeg_parse(data, len(data), ctypes.byref(info)), "yv3_jpeg_parse")
     return info
+
+
+def parse_ex(data, progressive=True):
+    """``yv3_jpeg_parse_ex`` of ``data``: ``(info, prog)``.  ``prog`` is the ``_ffi.JpegProg`` record of an accepted progressive
+    file (``info.reason`` then stays ``JPEG_PROGRESSIVE``) and None for every other file."""
+    info, prog = _ffi.JpegInfo(), _ffi.JpegProg()
+    _ffi.check(_ffi.lib().yv3_jpeg_parse_ex(data, len(data), _ffi.JPEGP_ACCEPT if progressive else 0, ctypes.byref(info),
+                                            ctypes.byref(prog)), "yv3_jpeg_parse_ex")
+    return info, (prog if prog.accepted else None)
 
 
 def _pil(source, data):
@@ -65,17 +78,26 @@ def _orientation(data):
 
 class Source:
     """One source ahead of the GPU: its bytes, its parsed record and, when it cannot go to the GPU decoder, either its pixels
-    from `read_image_rgb` (``pixels``) or the exception that raised (``error``).  Built on any thread (`TrainBatches`' workers)."""
-    __slots__ = ("source", "data", "info", "pixels", "error", "shape", "unterminated")
+    from `read_image_rgb` (``pixels``) or the exception that raised (``error``).  Built on any thread (`TrainBatches`' workers).
+    ``progressive=True``: the file is parsed with the progressive flag, and ``prog`` is the record of an accepted progressive
+    file (None for every other file)."""
+    __slots__ = ("source", "data", "info", "prog", "pixels", "error", "shape", "unterminated")
 
-    def __init__(self, source):
-        self.source, self.pixels, self.error = source, None, None
+    def __init__(self, source, progressive=False):
+        self.source, self.pixels, self.error, self.prog = source, None, None, None
         self.data = read_bytes(source)
-        self.info = parse(self.data)
+        if progressive:
+            self.info, self.prog = parse_ex(self.data)
+        else:
+            self.info = parse(self.data)
         f = self.info
-        gpu = f.reason == 0 and not (f.has_exif and _orientation(self.data) != 1)
+        gpu = (f.reason == 0 or self.prog is not None) and not (f.has_exif and _orientation(self.data) != 1)
         # a scan that runs to the end of the file has no EOI: PIL raises on such a file, whatever the device makes of its bits
-        self.unterminated = gpu and f.scan_offset + f.scan_length >= len(self.data)
+        if self.prog is not None:
+            last = self.prog.scans[self.prog.nscans - 1]
+            self.unterminated = gpu and last.offset + last.length >= len(self.data)
+        else:
+            self.unterminated = gpu and f.scan_offset + f.scan_length >= len(self.data)
         if gpu:
             self.shape = (int(f.height), int(f.width))
         else:
@@ -169,14 +191,16 @@ class Job:
         return out
 
 
-def submit(sources, device=None, stream=None, dst=None, entropy="serial"):
+def submit(sources, device=None, stream=None, dst=None, entropy="serial", progressive=False):
     """Enqueue the decode of ``sources`` (paths, ``bytes`` or prepared `Source` objects) on ``stream`` (default: the current one)
     and return the `Job`.  One device allocation holds, in this order, the upload -- records, offsets, the files' bytes and the
     pixels of the images PIL already decoded -- and the images the kernels write, each at a 256-aligned offset; it is filled by
     ONE host-to-device copy.  ``dst = (tensor, offsets)``: image i is decoded into the uint8 1-D ``tensor`` (`TrainBatches`'
     arena) at ``offsets[i]`` instead, for every i (None entries are not allowed: split the batch).  ``entropy="parallel"``: the
     self-synchronising entropy stage (``yv3_jpeg_decode_batch_ex``) -- the same statuses and pixels; its hand-over counts lie
-    behind the statuses and come back in the same read."""
+    behind the statuses and come back in the same read.  ``progressive=True``: sources are parsed with the progressive flag; an
+    accepted progressive file goes to the device (``yv3_jpeg_decode_batch_prog``, one more launch), its record in the same
+    upload and its status in the same read.  ``entropy`` affects the baseline images of the batch alone."""
     if entropy not in ENTROPY:
         raise ValueError("entropy must be 'serial' or 'parallel'")
     parallel = entropy == "parallel"
@@ -185,7 +209,7 @@ def submit(sources, device=None, stream=None, dst=None, entropy="serial"):
     dev = torch.device(device if device is not None else "cuda")
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
-    items = [s if isinstance(s, Source) else Source(s) for s in sources]
+    items = [s if isinstance(s, Source) else Source(s, progressive=progressive) for s in sources]
     stream = stream if stream is not None else torch.cuda.current_stream(dev)
     counters["calls"] += 1
     lib = _ffi.lib()
@@ -195,14 +219,23 @@ def submit(sources, device=None, stream=None, dst=None, entropy="serial"):
     reasons = [None] * len(items)
     for i, it in enumerate(items):
         if not it.on_gpu:
-            reasons[i] = ("parser", int(it.info.reason)) if it.info.reason else ("exif", None)
+            reasons[i] = ("parser", int(it.info.reason)) if it.info.reason and it.prog is None else ("exif", None)
+    prog_of, progs = [], []                                  # per device image: the index of its progressive record, or -1
+    for i in gpu:
+        prog_of.append(len(progs) if items[i].prog is not None else -1)
+        if items[i].prog is not None:
+            progs.append(items[i].prog)
+    P = len(progs)
 
-    # layout of the allocation: infos | src offsets | dst offsets | status | file bytes | PIL pixels || decoded images
+    # layout of the allocation: infos | src offsets | dst offsets | status | [progressive records | their indices] | file bytes |
+    # PIL pixels || decoded images
     o_info = 0
     o_soff = _round_up(o_info + B * _INFO_BYTES)
     o_doff = _round_up(o_soff + B * 8)
     o_stat = _round_up(o_doff + B * 8)
-    o_src = _round_up(o_stat + B * (8 if parallel else 4))   # parallel: [B] hand-over counts behind the statuses
+    o_prog = _round_up(o_stat + B * (8 if parallel else 4))  # parallel: [B] hand-over counts behind the statuses
+    o_pof = _round_up(o_prog + P * _PROG_BYTES)
+    o_src = _round_up(o_pof + (B * 4 if P else 0))           # (without a progressive image: the layout of a baseline batch)
     src_off, pos = [], o_src
     for i in gpu:
         src_off.append(pos - o_src)
@@ -234,6 +267,11 @@ def submit(sources, device=None, stream=None, dst=None, entropy="serial"):
         if B:
             host[o_info:o_info + B * _INFO_BYTES] = np.frombuffer(infos, dtype=np.uint8, count=B * _INFO_BYTES)
             host[o_soff:o_soff + B * 8].view(np.int64)[:] = src_off
+        if P:
+            prog_arr = (_ffi.JpegProg * P)(*progs)
+            prog_of_arr = (ctypes.c_int * B)(*prog_of)
+            host[o_prog:o_prog + P * _PROG_BYTES] = np.frombuffer(prog_arr, dtype=np.uint8, count=P * _PROG_BYTES)
+            host[o_pof:o_pof + B * 4].view(np.int32)[:] = prog_of
         if dst is None:
             dst_t, dst_off = buf, [own_off[i] for i in gpu]
             views = [None] * len(items)
@@ -264,14 +302,28 @@ def submit(sources, device=None, stream=None, dst=None, entropy="serial"):
         keep = [buf]
         status_host = None
         if B:
-            ws_bytes = lib.yv3_jpeg_workspace_bytes_ex(ctypes.addressof(infos), B, ENTROPY[entropy])
+            if P:
+                ws_bytes = lib.yv3_jpeg_workspace_bytes_prog(ctypes.addressof(infos), ctypes.addressof(prog_of_arr),
+                                                             ctypes.addressof(prog_arr), P, B, ENTROPY[entropy])
+            else:
+                ws_bytes = lib.yv3_jpeg_workspace_bytes_ex(ctypes.addressof(infos), B, ENTROPY[entropy])
             ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
             base = buf.data_ptr()
             desc = _ffi.JpegBatchDesc(src=base + o_src, src_bytes=src_bytes, src_offsets=base + o_soff, infos=base + o_info,
                                       infos_host=ctypes.addressof(infos), dst=dst_t.data_ptr(), dst_bytes=dst_t.numel(),
                                       dst_offsets=base + o_doff, status=base + o_stat, B=B)
-            _ffi.check(lib.yv3_jpeg_decode_batch_ex(ctypes.byref(desc), ENTROPY[entropy], base + o_stat + B * 4 if parallel else None,
-                                                    ws.data_ptr(), ws.numel(), stream.cuda_stream), "yv3_jpeg_decode_batch_ex")
+            handed = base + o_stat + B * 4 if parallel else None
+            launched = lib.yv3_jpeg_launch_count()
+            if P:                                           # a batch without a progressive image takes the call it always took
+                pdesc = _ffi.JpegBatchDescProg(base=desc, progs=base + o_prog, progs_host=ctypes.addressof(prog_arr),
+                                               prog_of=base + o_pof, prog_of_host=ctypes.addressof(prog_of_arr), P=P)
+                _ffi.check(lib.yv3_jpeg_decode_batch_prog(ctypes.byref(pdesc), ENTROPY[entropy], handed, ws.data_ptr(), ws.numel(),
+                                                          stream.cuda_stream), "yv3_jpeg_decode_batch_prog")
+            else:
+                _ffi.check(lib.yv3_jpeg_decode_batch_ex(ctypes.byref(desc), ENTROPY[entropy], handed, ws.data_ptr(), ws.numel(),
+                                                        stream.cuda_stream), "yv3_jpeg_decode_batch_ex")
+            counters["launches"] += lib.yv3_jpeg_launch_count() - launched
+            counters["prog_images"] += P
             n_read = 2 * B if parallel else B
             status_host = torch.empty(n_read, dtype=torch.int32, pin_memory=True)
             status_host.copy_(buf[o_stat:o_stat + n_read * 4].view(torch.int32), non_blocking=True)
@@ -280,12 +332,13 @@ def submit(sources, device=None, stream=None, dst=None, entropy="serial"):
     return Job(items, views, reasons, status_host, event, stream, keep, parallel)
 
 
-def decode_batch(sources, device=None, errors="raise", entropy="serial"):
+def decode_batch(sources, device=None, errors="raise", entropy="serial", progressive=False):
     """uint8 RGB ``[H,W,3]`` GPU tensors of ``sources`` (paths or ``bytes``), each what `evaluate.read_image_rgb` returns for it,
     as views into one allocation at 256-aligned offsets: a `Decoded` list whose ``fallback`` says which images took the PIL path.
     One upload (records + file bytes) and one status read per call.  ``errors="raise"`` (default): an image PIL cannot read
     raises what `read_image_rgb` raises; ``"keep"``: the exception takes the image's place in the list.  ``entropy``: ``"serial"``
-    (default; one lane per restart segment or scan) or ``"parallel"`` (the self-synchronising stage): the same result either way."""
+    (default; one lane per restart segment or scan) or ``"parallel"`` (the self-synchronising stage): the same result either way.
+    ``progressive=True``: progressive files whose script the parser accepts are decoded on the GPU too (the same pixels)."""
     if errors not in ("raise", "keep"):
         raise ValueError("errors must be 'raise' or 'keep'")
-    return submit(sources, device=device, entropy=entropy).finish(errors)
+    return submit(sources, device=device, entropy=entropy, progressive=progressive).finish(errors)
