@@ -1,15 +1,14 @@
 // Stand-alone host program for tests/test_jpeg_prog_host.py: yv3_jpeg_parse_ex, the progressive entropy routine (level by level,
 // each level in file order) and the IDCT and pixel arithmetic of the GPU decoder, compiled for the CPU with
-// -fsanitize=address,undefined and never loaded into Python.  A baseline file takes jpeg_host_check.cpp's own decode.
+// -fsanitize=address,undefined and never loaded into Python.  A baseline file takes the baseline decode of jpeg_host_common.h.
 //   jpeg_prog_host_check decode IN OUT [IN OUT ...]   full decode of each IN; OUT = "W H\n" + W*H*3 bytes when it decodes; prints
 //                                                     "reason R accepted A status S levels L" per file
 //   jpeg_prog_host_check fuzz IN SEED                 every prefix truncation, 2000 seeded single-byte corruptions of the scan
 //                                                     data and 300 of the headers, on exact-size heap copies, each decoded to
 //                                                     its pixels; prints how many inputs ended in each (reason, accepted, status)
-#define main jpeg_host_check_main
-#include "jpeg_host_check.cpp"
-#undef main
+#include <map>
 #include <tuple>
+#include "jpeg_host_common.h"
 #include "../yolo_v3_amd/csrc/jpeg_prog.h"
 
 // What layout_prog_kernel, entropy_prog_kernel, idct_kernel and colour_kernel do, serially.
@@ -34,9 +33,7 @@ static int host_decode_prog(const unsigned char* data, size_t n, yv3_jpeg_info* 
         if ((unsigned long long)sc->offset + (unsigned long long)sc->length > n) return YV3_JPEG_S_BOUNDS;
         const unsigned char* scan = data + sc->offset;
         const int nunits = yv3_jpegp_scan_units(yv3_jpegp_scan_items(&g, sc->ns, sc->comp[0]), sc->restart_interval);
-        if (nunits > 1)
-            for (long long k = 0; k + 1 < sc->length; ++k)
-                if (scan[k] == 0xFF && (scan[k + 1] & 0xF8) == 0xD0) marks[i].push_back(k);
+        if (nunits > 1) marks[i] = restart_marks(scan, sc->length);
         if (nunits > 1 && (long long)marks[i].size() != nunits - 1) return YV3_JPEG_S_MARKER;
     }
     for (int lev = 1; lev <= prog->nlevels; ++lev) {
@@ -56,10 +53,8 @@ static int host_decode_prog(const unsigned char* data, size_t n, yv3_jpeg_info* 
             const int items = yv3_jpegp_scan_items(&g, sc->ns, sc->comp[0]);
             const int nunits = yv3_jpegp_scan_units(items, sc->restart_interval), per = sc->restart_interval ? sc->restart_interval : items;
             for (int u = 0; u < nunits; ++u) {
-                int st = 0;
-                const long long begin = u ? marks[i][u - 1] + 2 : 0, end = u < nunits - 1 ? marks[i][u] : len;
-                if (u < nunits - 1 && scan[marks[i][u] + 1] != 0xD0 + (u & 7)) st = YV3_JPEG_S_MARKER;
-                if (begin > len || end < begin) st = YV3_JPEG_S_MARKER;
+                long long begin, end;
+                int st = yv3_jpeg_unit_bytes(scan, len, marks[i].data(), nunits, u, &begin, &end);
                 const int i0 = u * per, i1 = items - i0 < per ? items : i0 + per;
                 if (!st) st = yv3_jpegp_decode_unit(scan, begin, end, &g, sc, tp, natural, i0, i1, coef.data(), g.nblocks);
                 if (st > status) status = st;
@@ -67,22 +62,7 @@ static int host_decode_prog(const unsigned char* data, size_t n, yv3_jpeg_info* 
         }
         if (status) return status;
     }
-    if (!rgb) return 0;
-    std::vector<unsigned char> planes((size_t)g.nblocks * 64);
-    for (int c = 0; c < g.ncomp; ++c)
-        for (int by = 0; by < g.bh[c]; ++by)
-            for (int bx = 0; bx < g.bw[c]; ++bx)
-                if (yv3_jpeg_idct_block(coef.data() + ((size_t)g.base[c] + (size_t)by * g.bw[c] + bx) * 64, yv3_jpeg_quant_of(&frame, c),
-                                        planes.data() + (size_t)g.base[c] * 64 + ((size_t)by * 8 * g.bw[c] + bx) * 8, g.bw[c] * 8))
-                    return YV3_JPEG_S_RANGE;
-    rgb->resize((size_t)info->width * info->height * 3);
-    for (int y = 0; y < info->height; ++y)
-        for (int x = 0; x < info->width; ++x) {
-            int px[3];
-            yv3_jpeg_pixel(planes.data(), &g, x, y, px);
-            for (int k = 0; k < 3; ++k) (*rgb)[((size_t)y * info->width + x) * 3 + k] = (unsigned char)px[k];
-        }
-    return 0;
+    return rgb ? coef_to_rgb(&frame, g, coef, rgb) : 0;
 }
 
 int main(int argc, char** argv) {
@@ -90,20 +70,12 @@ int main(int argc, char** argv) {
     if (argc >= 4 && argc % 2 == 0 && !strcmp(argv[1], "decode")) {
         for (int a = 2; a + 1 < argc; a += 2) {
             const std::vector<unsigned char> file = read_file(argv[a]);
-            unsigned char* exact = (unsigned char*)malloc(file.size() ? file.size() : 1);
-            if (!file.empty()) memcpy(exact, file.data(), file.size());
+            const ExactCopy exact(file);
             yv3_jpeg_info info;
             std::vector<unsigned char> rgb;
-            const int st = host_decode_prog(exact, file.size(), &info, &prog, &rgb);
-            free(exact);
+            const int st = host_decode_prog(exact.data, exact.size, &info, &prog, &rgb);
             printf("reason %d accepted %d status %d levels %d\n", info.reason, prog.accepted, st, prog.nlevels);
-            if ((info.reason == 0 || prog.accepted) && st == 0) {
-                FILE* f = fopen(argv[a + 1], "wb");
-                if (!f) return 2;
-                fprintf(f, "%d %d\n", info.width, info.height);
-                fwrite(rgb.data(), 1, rgb.size(), f);
-                fclose(f);
-            }
+            if ((info.reason == 0 || prog.accepted) && st == 0 && !write_rgb(argv[a + 1], info.width, info.height, rgb)) return 2;
         }
         return 0;
     }
@@ -116,12 +88,10 @@ int main(int argc, char** argv) {
         std::map<std::tuple<int, int, int>, int> seen;
         int inputs = 0;
         auto run = [&](const std::vector<unsigned char>& v) {
-            unsigned char* exact = (unsigned char*)malloc(v.size() ? v.size() : 1);
-            if (!v.empty()) memcpy(exact, v.data(), v.size());
+            const ExactCopy exact(v);
             yv3_jpeg_info fi;
             std::vector<unsigned char> rgb;                                             // the IDCT and the pixels too: RANGE is a status
-            const int st = host_decode_prog(exact, v.size(), &fi, &prog, &rgb);
-            free(exact);
+            const int st = host_decode_prog(exact.data, exact.size, &fi, &prog, &rgb);
             ++seen[std::make_tuple(fi.reason, prog.accepted, st)];
             ++inputs;
         };

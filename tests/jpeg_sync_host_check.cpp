@@ -8,12 +8,7 @@
 //   jpeg_sync_host_check fuzz IN.jpg SEED          every prefix truncation, 2000 seeded single-byte corruptions, 500 random
 //                                                  tails, at S and S / 2: parallel status == serial status, equal coefficients
 //                                                  at status 0; prints the counts
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <vector>
-#include "../yolo_v3_amd/csrc/jpeg_parse.cpp"
-#include "../yolo_v3_amd/csrc/jpeg_pixel.h"
+#include "jpeg_host_common.h"
 #include "../yolo_v3_amd/csrc/jpeg_sync.h"
 
 struct UnitStats {
@@ -142,9 +137,7 @@ static int entropy_host(const unsigned char* data, size_t n, bool parallel, Deco
     for (int t = 0; t < 8; ++t)
         if (info->huff_defined[t] && yv3_jpeg_build_hufftab(info->huff_counts[t], info->huff_values[t], t < 4 ? 15 : 255, &d->tabs[t]))
             status = YV3_JPEG_S_HUFFTABLE;
-    if (g.nunits > 1)
-        for (long long i = 0; i + 1 < len; ++i)
-            if (scan[i] == 0xFF && (scan[i + 1] & 0xF8) == 0xD0) d->marks.push_back(i);
+    if (g.nunits > 1) d->marks = restart_marks(scan, len);
     if (g.nunits > 1 && (long long)d->marks.size() != g.nunits - 1 && status < YV3_JPEG_S_MARKER) status = YV3_JPEG_S_MARKER;
     d->coef.assign((size_t)g.nblocks * 64, 0);
     if (status) { d->status = status; return 0; }
@@ -152,14 +145,8 @@ static int entropy_host(const unsigned char* data, size_t n, bool parallel, Deco
     unsigned char sel[8];
     for (int t = 0; t < 8; ++t) sel[t] = t < 4 ? info->td[t] : info->ta[t - 4];
     for (int u = 0; u < g.nunits; ++u) {
-        int code = 0;
-        long long begin = 0, end = len;
-        if (u > 0) begin = d->marks[u - 1] + 2;
-        if (u < g.nunits - 1) {
-            end = d->marks[u];
-            if (end < 0 || end + 1 >= len || scan[end + 1] != 0xD0 + (u & 7)) code = YV3_JPEG_S_MARKER;
-        }
-        if (begin < 0 || begin > len || end < begin) code = YV3_JPEG_S_MARKER;
+        long long begin, end;
+        int code = yv3_jpeg_unit_bytes(scan, len, d->marks.data(), g.nunits, u, &begin, &end);
         if (!code) {
             const int m0 = u * g.mcus_per_unit;
             const int m1 = g.nmcu - m0 < g.mcus_per_unit ? g.nmcu : m0 + g.mcus_per_unit;
@@ -231,25 +218,6 @@ static void serial_states(const unsigned char* scan, long long begin, long long 
     out->push_back(yv3_jpeg_sync_state{w.bit(), 0, 0});   // after the last symbol
 }
 
-static std::vector<unsigned char> read_file(const char* path) {
-    std::vector<unsigned char> v;
-    FILE* f = fopen(path, "rb");
-    if (!f) { fprintf(stderr, "cannot open %s\n", path); exit(2); }
-    unsigned char buf[65536];
-    size_t k;
-    while ((k = fread(buf, 1, sizeof buf, f)) > 0) v.insert(v.end(), buf, buf + k);
-    fclose(f);
-    return v;
-}
-
-static unsigned long long rng_state;
-static unsigned rnd() {                                       // splitmix64: the same inputs for the same seed everywhere
-    unsigned long long z = (rng_state += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return (unsigned)((z ^ (z >> 31)) >> 16);
-}
-
 template <int S>
 static int decode_main(const std::vector<unsigned char>& file, const char* out_path) {
     Decode ser, par;
@@ -266,7 +234,8 @@ static int decode_main(const std::vector<unsigned char>& file, const char* out_p
         const long long len = par.info.scan_length;
         for (size_t q = 0; q < par.units.size(); ++q) {
             const int u = par.unit_no[q];
-            const long long begin = u ? par.marks[u - 1] + 2 : 0, end = u < par.g.nunits - 1 ? par.marks[u] : len;
+            long long begin, end;
+            yv3_jpeg_unit_bytes(par.scan.data(), len, par.marks.data(), par.g.nunits, u, &begin, &end);      // (it passed in entropy_host)
             const int m0 = u * par.g.mcus_per_unit, m1 = par.g.nmcu - m0 < par.g.mcus_per_unit ? par.g.nmcu : m0 + par.g.mcus_per_unit;
             std::vector<yv3_jpeg_sync_state> truth;
             serial_states(par.scan.data(), begin, end, &par.g, par.tabs.data(), sel, (m1 - m0) * yv3_jpeg_sync_bpm(&par.g), &truth);
@@ -282,24 +251,9 @@ static int decode_main(const std::vector<unsigned char>& file, const char* out_p
         }
     }
     if (par.status == 0) {
-        const yv3_jpeg_geom& g = par.g;
-        std::vector<unsigned char> planes((size_t)g.nblocks * 64);
-        for (int c = 0; c < g.ncomp; ++c)
-            for (int by = 0; by < g.bh[c]; ++by)
-                for (int bx = 0; bx < g.bw[c]; ++bx)
-                    if (yv3_jpeg_idct_block(par.coef.data() + ((size_t)g.base[c] + (size_t)by * g.bw[c] + bx) * 64, yv3_jpeg_quant_of(&par.info, c),
-                                            planes.data() + (size_t)g.base[c] * 64 + ((size_t)by * 8 * g.bw[c] + bx) * 8, g.bw[c] * 8))
-                        return 3;
-        FILE* f = fopen(out_path, "wb");
-        if (!f) return 2;
-        fprintf(f, "%d %d\n", par.info.width, par.info.height);
-        for (int y = 0; y < par.info.height; ++y)
-            for (int x = 0; x < par.info.width; ++x) {
-                int px[3];
-                yv3_jpeg_pixel(planes.data(), &g, x, y, px);
-                for (int k = 0; k < 3; ++k) fputc(px[k], f);
-            }
-        fclose(f);
+        std::vector<unsigned char> rgb;
+        if (coef_to_rgb(&par.info, par.g, par.coef, &rgb)) return 3;
+        if (!write_rgb(out_path, par.info.width, par.info.height, rgb)) return 2;
     }
     return 0;
 }
@@ -308,12 +262,11 @@ struct FuzzCount { int inputs = 0, decoded = 0, ok = 0, errors = 0, mismatches =
 
 template <int S>
 static void fuzz_one(const std::vector<unsigned char>& v, FuzzCount* c) {
-    unsigned char* exact = (unsigned char*)malloc(v.size() ? v.size() : 1);     // exact size: ASan guards both ends
-    if (!v.empty()) memcpy(exact, v.data(), v.size());
+    const ExactCopy exact(v);
     Decode ser, par;
     ++c->inputs;
-    if (entropy_host<S>(exact, v.size(), false, &ser) == 0) {
-        entropy_host<S>(exact, v.size(), true, &par);
+    if (entropy_host<S>(exact.data, exact.size, false, &ser) == 0) {
+        entropy_host<S>(exact.data, exact.size, true, &par);
         ++c->decoded;
         c->handed += par.handed;
         c->long_units += par.long_units;
@@ -323,7 +276,6 @@ static void fuzz_one(const std::vector<unsigned char>& v, FuzzCount* c) {
             fprintf(stderr, "mismatch: S %d size %zu serial %d parallel %d\n", S, v.size(), ser.status, par.status);
         }
     }
-    free(exact);
 }
 
 int main(int argc, char** argv) {

@@ -11,12 +11,12 @@ import pytest
 import torch
 from PIL import Image
 
+from tests import jpeg_abi
 from tests.test_jpeg_host import PHOTO, encode, picture
 from yolo_v3_amd import _ffi, evaluate, jpeg
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-GUARD = 512
 
 SIZES = [(1, 1), (8, 8), (7, 9), (16, 16), (17, 13), (33, 19), (40, 1), (1, 40), (64, 48)]
 # widths at which libjpeg replaces fancy upsampling by replication (jinit_upsampler: chroma planes of one or two columns)
@@ -56,56 +56,13 @@ def test_every_setting_in_one_mixed_batch_through_the_c_abi(files):
     between guard bytes that must stay as they were, every status 0, every pixel PIL's."""
     cases, refs = files
     assert len(cases) == 9 * 3 * 4 * 4 * 2 * 3 + 5 * 2 * 3 * 2 * 3
-    datas = [d for _, d in cases]
-    order = list(range(len(datas))) + [5]                               # file 5 is decoded twice, from the same bytes
-    B = len(order)
-    lib = _ffi.lib()
-    infos = (_ffi.JpegInfo * B)()
-    src_np, src_off, pos = [], {}, 1
-    for j, d in enumerate(datas):
-        src_off[j] = pos
-        src_np.append((pos, d))
-        pos = (pos + len(d) + 3) | 1                                     # odd offsets
-    src = np.full(pos + 7, 0x5A, np.uint8)
-    for o, d in src_np:
-        src[o:o + len(d)] = np.frombuffer(d, np.uint8)
-    dst_off, dpos = [], GUARD + 1
-    for k, j in enumerate(order):
-        infos[k] = jpeg.parse(datas[j])
-        assert infos[k].reason == 0, cases[j][0]
-        dst_off.append(dpos)
-        dpos += refs[j].size + GUARD + (k % 3)                           # any alignment
-    assert any(o % 4 for o in dst_off) and any(o % 4 == 0 for o in dst_off)
-    dst = torch.full((dpos,), 0xA5, dtype=torch.uint8, device=DEV)
-    need = lib.yv3_jpeg_workspace_bytes(ctypes.addressof(infos), B)
-    ws = torch.full((need + 2 * GUARD,), 0x3C, dtype=torch.uint8, device=DEV)
-    d_src = torch.from_numpy(src).to(DEV)
-    d_soff = torch.tensor([src_off[j] for j in order], dtype=torch.int64, device=DEV)
-    d_doff = torch.tensor(dst_off, dtype=torch.int64, device=DEV)
-    d_info = torch.from_numpy(np.frombuffer(infos, np.uint8).copy()).to(DEV)
-    status = torch.full((B + 2,), 777, dtype=torch.int32, device=DEV)
-    desc = _ffi.JpegBatchDesc(src=d_src.data_ptr(), src_bytes=d_src.numel(), src_offsets=d_soff.data_ptr(), infos=d_info.data_ptr(),
-                              infos_host=ctypes.addressof(infos), dst=dst.data_ptr(), dst_bytes=dst.numel(), dst_offsets=d_doff.data_ptr(),
-                              status=status.data_ptr() + 4, B=B)
-    _ffi.check(lib.yv3_jpeg_decode_batch(ctypes.byref(desc), ws.data_ptr() + GUARD, need, _ffi.stream_ptr()), "yv3_jpeg_decode_batch")
-    torch.cuda.synchronize()
-    st = status.cpu().numpy()
-    assert st[0] == 777 and st[-1] == 777
-    bad = [(cases[order[k]][0], int(st[1 + k])) for k in range(B) if st[1 + k]]
+    order = list(range(len(cases))) + [5]                               # file 5 is decoded twice, from the same bytes
+    r = jpeg_abi.decode([d for _, d in cases], order=order)
+    assert any(o % 4 for o in r.dst_off) and any(o % 4 == 0 for o in r.dst_off)
+    bad = [(cases[j][0], int(s)) for j, s in zip(order, r.statuses) if s]
     assert not bad, bad[:10]
-    got = dst.cpu().numpy()
-    mask = np.ones(got.size, bool)
-    wrong = []
-    for k, j in enumerate(order):
-        o, n = dst_off[k], refs[j].size
-        mask[o:o + n] = False
-        if not np.array_equal(got[o:o + n].reshape(refs[j].shape), refs[j]):
-            wrong.append(cases[j][0])
+    wrong = [cases[j][0] for j, px in zip(order, r.images) if not np.array_equal(px, refs[j])]
     assert not wrong, (len(wrong), wrong[:10])
-    assert (got[mask] == 0xA5).all()                                     # guard bytes around every destination
-    wsn = ws.cpu().numpy()
-    assert (wsn[:GUARD] == 0x3C).all() and (wsn[GUARD + need:] == 0x3C).all()
-    assert (d_src.cpu().numpy() == src).all()
 
 
 def test_decode_batch_one_upload_one_status_read(files):
@@ -183,35 +140,23 @@ def test_damaged_and_refused_files_come_back_through_pil():
         evaluate.read_image_rgb(io.BytesIO(b"not an image"))
 
 
-def test_device_checks_keep_a_lying_record_inside_its_buffers():
-    """Records whose fields do not fit the buffers they come with: status BOUNDS / INFO per image, the neighbour untouched by it."""
-    good, _, _ = damaged_files()
-    lib = _ffi.lib()
-    B = 4
-    infos = (_ffi.JpegInfo * B)()
-    for k in range(B):
+def lying_records(good):
+    """Four records of the file ``good`` for the DEVICE: 1 lies about its scan's length, 2 about its width."""
+    infos = (_ffi.JpegInfo * 4)()
+    for k in range(4):
         infos[k] = jpeg.parse(good)
-    host = (_ffi.JpegInfo * B)()
-    ctypes.memmove(host, infos, ctypes.sizeof(infos))
     infos[1].scan_length = 1 << 40                                       # the device copies lie; the host copies size the workspace
     infos[2].width = 20000
-    n = 64 * 48 * 3
-    d_src = torch.from_numpy(np.frombuffer(good, np.uint8).copy()).to(DEV)
-    d_soff = torch.zeros(B, dtype=torch.int64, device=DEV)
-    d_doff = torch.tensor([0, n, 2 * n, 3 * n - 1], dtype=torch.int64, device=DEV)      # image 3 would end one byte past dst
-    d_info = torch.from_numpy(np.frombuffer(infos, np.uint8).copy()).to(DEV)
-    dst = torch.full((3 * n + GUARD,), 0xA5, dtype=torch.uint8, device=DEV)
-    need = lib.yv3_jpeg_workspace_bytes(ctypes.addressof(host), B)
-    ws = torch.empty(need, dtype=torch.uint8, device=DEV)
-    status = torch.full((B,), 777, dtype=torch.int32, device=DEV)
-    desc = _ffi.JpegBatchDesc(src=d_src.data_ptr(), src_bytes=d_src.numel(), src_offsets=d_soff.data_ptr(), infos=d_info.data_ptr(),
-                              infos_host=ctypes.addressof(host), dst=dst.data_ptr(), dst_bytes=3 * n, dst_offsets=d_doff.data_ptr(),
-                              status=status.data_ptr(), B=B)
-    _ffi.check(lib.yv3_jpeg_decode_batch(ctypes.byref(desc), ws.data_ptr(), need, _ffi.stream_ptr()), "yv3_jpeg_decode_batch")
-    torch.cuda.synchronize()
-    assert status.tolist() == [0, _ffi.JPEG_S_BOUNDS, _ffi.JPEG_S_INFO, _ffi.JPEG_S_BOUNDS]
-    got = dst.cpu().numpy()
-    assert np.array_equal(got[:n].reshape(48, 64, 3), pil_rgb(good)) and (got[n:] == 0xA5).all()
+    return infos
+
+
+def test_device_checks_keep_a_lying_record_inside_its_buffers():
+    """Records whose fields do not fit the buffers they come with, and a destination buffer that ends one byte before the last
+    image does: status BOUNDS / INFO per image, the neighbour untouched by it."""
+    good, _, _ = damaged_files()
+    r = jpeg_abi.decode([good], order=[0, 0, 0, 0], dev_infos=lying_records(good), dst_cut=1)
+    assert r.statuses.tolist() == [0, _ffi.JPEG_S_BOUNDS, _ffi.JPEG_S_INFO, _ffi.JPEG_S_BOUNDS]
+    assert np.array_equal(r.images[0], pil_rgb(good)) and all((px == jpeg_abi.FILL).all() for px in r.images[1:])
 
 
 def test_host_checks_answer_before_any_launch():

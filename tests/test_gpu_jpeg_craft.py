@@ -7,81 +7,33 @@ segments), the marker count, its prefix and ``marks[k]`` for k >= 256, the ``u &
 selectors and quantiser tables 2 and 3, SOF1, other component ids, `idct_kernel` raising YV3_JPEG_S_RANGE, and
 `colour_kernel`'s grid-stride loop (more than 4096 x 256 groups of 4 pixels).  `idct_kernel`'s own stride loop needs more than
 1 048 576 blocks (a 67 MP image) and is left out on purpose."""
-import ctypes
 import io
 
 import numpy as np
 import pytest
 import torch
 
-from tests import jpeg_craft
+from tests import jpeg_abi, jpeg_craft
 from yolo_v3_amd import _ffi, evaluate, jpeg
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-GUARD = 512
-FILL = 0xA5
+FILL = jpeg_abi.FILL
 
 
 def pil_rgb(data):
     return evaluate.read_image_rgb(io.BytesIO(data))
 
 
-def decode_through_the_c_abi(datas):
-    """One yv3_jpeg_decode_batch over ``datas``: sources at odd byte offsets, destinations of any alignment between guard
-    bytes, a workspace between guard bytes.  Returns (statuses, the bytes of each destination); the guards are checked here."""
-    B = len(datas)
-    lib = _ffi.lib()
-    infos = (_ffi.JpegInfo * B)()
-    src_off, pos = [], 1
-    for d in datas:
-        src_off.append(pos)
-        pos = (pos + len(d) + 3) | 1
-    src = np.full(pos + 7, 0x5A, np.uint8)
-    for o, d in zip(src_off, datas):
-        src[o:o + len(d)] = np.frombuffer(d, np.uint8)
-    dst_off, sizes, dpos = [], [], GUARD + 1
-    for k, d in enumerate(datas):
-        infos[k] = jpeg.parse(d)
-        assert infos[k].reason == 0, k
-        sizes.append(infos[k].width * infos[k].height * 3)
-        dst_off.append(dpos)
-        dpos += sizes[k] + GUARD + (k % 3)
-    dst = torch.full((dpos,), FILL, dtype=torch.uint8, device=DEV)
-    need = lib.yv3_jpeg_workspace_bytes(ctypes.addressof(infos), B)
-    ws = torch.full((need + 2 * GUARD,), 0x3C, dtype=torch.uint8, device=DEV)
-    d_src = torch.from_numpy(src).to(DEV)
-    d_soff = torch.tensor(src_off, dtype=torch.int64, device=DEV)
-    d_doff = torch.tensor(dst_off, dtype=torch.int64, device=DEV)
-    d_info = torch.from_numpy(np.frombuffer(infos, np.uint8).copy()).to(DEV)
-    status = torch.full((B + 2,), 777, dtype=torch.int32, device=DEV)
-    desc = _ffi.JpegBatchDesc(src=d_src.data_ptr(), src_bytes=d_src.numel(), src_offsets=d_soff.data_ptr(), infos=d_info.data_ptr(),
-                              infos_host=ctypes.addressof(infos), dst=dst.data_ptr(), dst_bytes=dst.numel(), dst_offsets=d_doff.data_ptr(),
-                              status=status.data_ptr() + 4, B=B)
-    _ffi.check(lib.yv3_jpeg_decode_batch(ctypes.byref(desc), ws.data_ptr() + GUARD, need, _ffi.stream_ptr()), "yv3_jpeg_decode_batch")
-    torch.cuda.synchronize()
-    st = status.cpu().numpy()
-    assert st[0] == 777 and st[-1] == 777
-    got = dst.cpu().numpy()
-    mask = np.ones(got.size, bool)
-    for o, n in zip(dst_off, sizes):
-        mask[o:o + n] = False
-    assert (got[mask] == FILL).all()                                     # guard bytes around every destination
-    wsn = ws.cpu().numpy()
-    assert (wsn[:GUARD] == 0x3C).all() and (wsn[GUARD + need:] == 0x3C).all()
-    assert (d_src.cpu().numpy() == src).all()
-    return [int(s) for s in st[1:-1]], [got[o:o + n] for o, n in zip(dst_off, sizes)]
-
-
 def test_families_a_and_b_in_one_mixed_batch_through_the_c_abi():
     """Everything an encoder can write, crafted and PIL-written, in one batch: every status 0, every image PIL's."""
     cases = jpeg_craft.family_a() + jpeg_craft.family_b()
     assert len(cases) >= 70
-    statuses, images = decode_through_the_c_abi([d for _, d in cases])
-    bad = [(name, s) for (name, _), s in zip(cases, statuses) if s]
+    r = jpeg_abi.decode([d for _, d in cases])
+    bad = [(name, int(s)) for (name, _), s in zip(cases, r.statuses) if s]
     assert not bad, bad
     wrong = []
-    for (name, data), px in zip(cases, images):
+    for (name, data), px in zip(cases, r.images):
         ref = pil_rgb(data)
         if px.size != ref.size or not np.array_equal(px.reshape(ref.shape), ref):
             wrong.append(name)
@@ -133,7 +85,8 @@ def test_a_refused_block_between_good_neighbours_through_the_c_abi():
     """good, RANGE, good: the neighbours are PIL's, the refused image's destination keeps its fill value."""
     c = dict(jpeg_craft.family_c())
     good_a, refused, good_b = c["c q1 A64 n64"], c["c q8 A1023 n64"], c["c q1 A256 n4"]
-    statuses, images = decode_through_the_c_abi([good_a, refused, good_b])
+    r = jpeg_abi.decode([good_a, refused, good_b])
+    statuses, images = r.statuses.tolist(), r.images
     assert statuses == [0, _ffi.JPEG_S_RANGE, 0]
     assert np.array_equal(images[0].reshape(48, 48, 3), pil_rgb(good_a)) and np.array_equal(images[2].reshape(48, 48, 3), pil_rgb(good_b))
     assert images[1].size == 48 * 48 * 3 and (images[1] == FILL).all()

@@ -4,7 +4,6 @@
 device's status of damaged files against the stand-alone host program's; the launch count without a progressive file; the
 parallel entropy stage, determinism, the ``dst=`` arena and the workspace's bounds; and the switch in `TrainBatches` and
 `generate_results_file`."""
-import ctypes
 import io
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 import torch
 from PIL import Image
 
+from tests import jpeg_abi
 from tests import jpeg_prog_craft as craft
 from tests.helpers import load_sw1_net
 from tests.test_gpu_jpeg_loader import epochs, listing, same          # noqa: F401  (listing: a fixture)
@@ -21,7 +21,6 @@ from yolo_v3_amd import augment as aug
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-GUARD = 512
 
 
 def reference(data):
@@ -200,78 +199,24 @@ def test_the_workspace_stays_between_its_sentinels():
     picks = [family[i] for i in (5, 77, 150, 260, 371, 499)] + craft.crafted()[:5] + [craft.crafted()[7]]
     datas = [f for _, f, _ in picks] + [picks[0][2], picks[3][2]] + [picks[2][1]]
     B = len(datas)
-    lib = _ffi.lib()
-    infos, progs, prog_of = (_ffi.JpegInfo * B)(), [], []
-    for k, d in enumerate(datas):
-        info, rec = jpeg.parse_ex(d)
-        infos[k] = info
-        prog_of.append(len(progs) if rec is not None else -1)
-        if rec is not None:
-            progs.append(rec)
+    progs = [rec for rec in (jpeg.parse_ex(d)[1] for d in datas) if rec is not None]
     P = len(progs)
     assert P == B - 2
-    prog_host = (_ffi.JpegProg * P)(*progs)
     prog_dev = (_ffi.JpegProg * P)(*progs)
     prog_dev[P - 1].scans[2].length = 1 << 30                           # the last image's DEVICE record lies: past the source buffer
-    pof = (ctypes.c_int * B)(*prog_of)
     refs = [craft.pil_pixels(d) for d in datas]
-    src = np.concatenate([np.frombuffer(d, np.uint8) for d in datas])
-    src_off = np.cumsum([0] + [len(d) for d in datas[:-1]])
-    dst_off, dpos = [], GUARD + 1
-    for r in refs:
-        dst_off.append(dpos)
-        dpos += r.size + GUARD
-    dst = torch.full((dpos,), 0xA5, dtype=torch.uint8, device=DEV)
-    need = lib.yv3_jpeg_workspace_bytes_prog(ctypes.addressof(infos), ctypes.addressof(pof), ctypes.addressof(prog_host), P, B, 0)
-    assert need > 0
-    ws = torch.full((need + 2 * GUARD,), 0x3C, dtype=torch.uint8, device=DEV)
-    d_src = torch.from_numpy(src.copy()).to(DEV)
-    d_soff = torch.tensor(src_off, dtype=torch.int64, device=DEV)
-    d_doff = torch.tensor(dst_off, dtype=torch.int64, device=DEV)
-    d_info = torch.from_numpy(np.frombuffer(infos, np.uint8).copy()).to(DEV)
-    d_prog = torch.from_numpy(np.frombuffer(prog_dev, np.uint8).copy()).to(DEV)
-    d_pof = torch.tensor(prog_of, dtype=torch.int32, device=DEV)
-    status = torch.full((B + 2,), 777, dtype=torch.int32, device=DEV)
-    base = _ffi.JpegBatchDesc(src=d_src.data_ptr(), src_bytes=d_src.numel(), src_offsets=d_soff.data_ptr(), infos=d_info.data_ptr(),
-                              infos_host=ctypes.addressof(infos), dst=dst.data_ptr(), dst_bytes=dst.numel(), dst_offsets=d_doff.data_ptr(),
-                              status=status.data_ptr() + 4, B=B)
-    desc = _ffi.JpegBatchDescProg(base=base, progs=d_prog.data_ptr(), progs_host=ctypes.addressof(prog_host), prog_of=d_pof.data_ptr(),
-                                  prog_of_host=ctypes.addressof(pof), P=P)
-    launched = lib.yv3_jpeg_launch_count()
-    _ffi.check(lib.yv3_jpeg_decode_batch_prog(ctypes.byref(desc), 0, None, ws.data_ptr() + GUARD, need, _ffi.stream_ptr()),
-               "yv3_jpeg_decode_batch_prog")
-    assert lib.yv3_jpeg_launch_count() - launched == 5
-    torch.cuda.synchronize()
-    st = status.cpu().numpy()
-    assert st[0] == 777 and st[-1] == 777
-    assert st[1:B].tolist() == [0] * (B - 1) and st[B] == _ffi.JPEG_S_BOUNDS
-    got = dst.cpu().numpy()
-    mask = np.ones(got.size, bool)
+    r = jpeg_abi.decode(datas, entry="prog", dev_progs=prog_dev)
+    assert r.launches == 5
+    assert r.statuses.tolist() == [0] * (B - 1) + [_ffi.JPEG_S_BOUNDS]
     for k in range(B - 1):
-        o, n = dst_off[k], refs[k].size
-        mask[o:o + n] = False
-        assert np.array_equal(got[o:o + n].reshape(refs[k].shape), refs[k]), k
-    assert (got[mask] == 0xA5).all()                                    # the refused image's destination too
-    wsn = ws.cpu().numpy()
-    assert (wsn[:GUARD] == 0x3C).all() and (wsn[GUARD + need:] == 0x3C).all()
-    assert (d_src.cpu().numpy() == src).all()
+        assert np.array_equal(r.images[k], refs[k]), k
+    assert (r.images[B - 1] == jpeg_abi.FILL).all()                     # the refused image's destination too
     # the same entry with P = 0 over the two baseline images of the batch: four launches, no entropy_prog_kernel
-    k0, isz = B - 3, ctypes.sizeof(_ffi.JpegInfo)
-    two = (_ffi.JpegInfo * 2)(infos[k0], infos[k0 + 1])
-    status.fill_(777)
-    base0 = _ffi.JpegBatchDesc(src=d_src.data_ptr(), src_bytes=d_src.numel(), src_offsets=d_soff.data_ptr() + 8 * k0,
-                               infos=d_info.data_ptr() + isz * k0, infos_host=ctypes.addressof(two), dst=dst.data_ptr(),
-                               dst_bytes=dst.numel(), dst_offsets=d_doff.data_ptr() + 8 * k0, status=status.data_ptr() + 4, B=2)
-    desc0 = _ffi.JpegBatchDescProg(base=base0, progs=None, progs_host=None, prog_of=None, prog_of_host=None, P=0)
-    need0 = lib.yv3_jpeg_workspace_bytes_prog(ctypes.addressof(two), None, None, 0, 2, 0)
-    assert 0 < need0 <= need
-    launched = lib.yv3_jpeg_launch_count()
-    _ffi.check(lib.yv3_jpeg_decode_batch_prog(ctypes.byref(desc0), 0, None, ws.data_ptr() + GUARD, need0, _ffi.stream_ptr()),
-               "yv3_jpeg_decode_batch_prog")
-    assert lib.yv3_jpeg_launch_count() - launched == 4
-    torch.cuda.synchronize()
-    assert status.cpu().numpy().tolist() == [777, 0, 0] + [777] * (B - 1)
-    assert np.array_equal(dst.cpu().numpy(), got)                       # the same pixels again, nothing else touched
+    k0 = B - 3
+    r0 = jpeg_abi.decode(datas[k0:k0 + 2], entry="prog")
+    assert 0 < r0.need <= r.need and r0.launches == 4
+    assert r0.statuses.tolist() == [0, 0]
+    assert np.array_equal(r0.images[0], refs[k0]) and np.array_equal(r0.images[1], refs[k0 + 1])      # the same pixels again
 
 
 def test_train_batches_and_the_results_file_with_the_switch(listing, monkeypatch, tmp_path):

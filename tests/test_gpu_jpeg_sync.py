@@ -1,15 +1,14 @@
 """The self-synchronising entropy stage on the GPU (``yv3_jpeg_decode_batch_ex`` with ``YV3_JPEG_ENTROPY_PARALLEL``): one mixed batch of
 every setting, scans longer than one window, the files of tests/jpeg_sync_cases.py for the workgroup logic (rounds of units, window
 edges, cuts, the DC pass), damaged files whose status must be the serial stage's, and the Python surface."""
-import ctypes
 import io
 
 import numpy as np
 import pytest
 import torch
 
-from tests import jpeg_craft, jpeg_sync_cases
-from tests.test_gpu_jpeg import damaged_files, files, pil_rgb  # noqa: F401  (files: the fixture of every PIL setting)
+from tests import jpeg_abi, jpeg_craft, jpeg_sync_cases
+from tests.test_gpu_jpeg import damaged_files, files, lying_records, pil_rgb  # noqa: F401  (files: the fixture of every PIL setting)
 from tests.test_jpeg_host import picture
 from tests.test_jpeg_sync_host import crafted_long_files, table_files
 from yolo_v3_amd import _ffi, evaluate, jpeg
@@ -17,63 +16,15 @@ from yolo_v3_amd import augment as aug
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-GUARD = 512
-SERIAL, PARALLEL = jpeg.ENTROPY["serial"], jpeg.ENTROPY["parallel"]
+SERIAL, PARALLEL = jpeg_abi.SERIAL, jpeg_abi.PARALLEL
 
 
-def run_batch(datas, entropy, infos=None, handed_null=False):
-    """One yv3_jpeg_decode_batch_ex over ``datas`` (sources at odd offsets, destinations at any alignment between guard bytes, the
-    workspace between guard bytes).  Returns statuses, hand-over counts and the destination bytes of every image; asserts that
-    nothing outside the destinations, the statuses, the counts and the workspace was written.  ``handed_null``: the call gets no
-    array for the counts (and those returned are the fill value)."""
-    B = len(datas)
-    lib = _ffi.lib()
-    host = (_ffi.JpegInfo * B)()
-    src_off, pos = [], 1
-    for k, d in enumerate(datas):
-        host[k] = jpeg.parse(d)
-        assert host[k].reason == 0, k
-        src_off.append(pos)
-        pos = (pos + len(d) + 3) | 1
-    src = np.full(pos + 7, 0x5A, np.uint8)
-    for o, d in zip(src_off, datas):
-        src[o:o + len(d)] = np.frombuffer(d, np.uint8)
-    sizes = [host[k].width * host[k].height * 3 for k in range(B)]
-    dst_off, dpos = [], GUARD + 1
-    for k in range(B):
-        dst_off.append(dpos)
-        dpos += sizes[k] + GUARD + (k % 3)
-    dst = torch.full((dpos,), 0xA5, dtype=torch.uint8, device=DEV)
-    need = lib.yv3_jpeg_workspace_bytes_ex(ctypes.addressof(host), B, entropy)
-    assert need == lib.yv3_jpeg_workspace_bytes(ctypes.addressof(host), B)
-    ws = torch.full((need + 2 * GUARD,), 0x3C, dtype=torch.uint8, device=DEV)
-    d_src = torch.from_numpy(src).to(DEV)
-    d_soff = torch.tensor(src_off, dtype=torch.int64, device=DEV)
-    d_doff = torch.tensor(dst_off, dtype=torch.int64, device=DEV)
-    d_info = torch.from_numpy(np.frombuffer(infos if infos is not None else host, np.uint8).copy()).to(DEV)
-    status = torch.full((B + 2,), 777, dtype=torch.int32, device=DEV)
-    handed = torch.full((B + 2,), 555, dtype=torch.int32, device=DEV)
-    desc = _ffi.JpegBatchDesc(src=d_src.data_ptr(), src_bytes=d_src.numel(), src_offsets=d_soff.data_ptr(), infos=d_info.data_ptr(),
-                              infos_host=ctypes.addressof(host), dst=dst.data_ptr(), dst_bytes=dst.numel(), dst_offsets=d_doff.data_ptr(),
-                              status=status.data_ptr() + 4, B=B)
-    _ffi.check(lib.yv3_jpeg_decode_batch_ex(ctypes.byref(desc), entropy, None if handed_null else handed.data_ptr() + 4,
-                                            ws.data_ptr() + GUARD, need, _ffi.stream_ptr()), "yv3_jpeg_decode_batch_ex")
-    torch.cuda.synchronize()
-    st, ho = status.cpu().numpy(), handed.cpu().numpy()
-    assert st[0] == 777 and st[-1] == 777 and ho[0] == 555 and ho[-1] == 555
-    if entropy == SERIAL or handed_null:
-        assert (ho == 555).all()                                         # not written by the serial stage, nor without an array
-    got = dst.cpu().numpy()
-    mask = np.ones(got.size, bool)
-    out = []
-    for k in range(B):
-        mask[dst_off[k]:dst_off[k] + sizes[k]] = False
-        out.append(got[dst_off[k]:dst_off[k] + sizes[k]].reshape(host[k].height, host[k].width, 3))
-    assert (got[mask] == 0xA5).all()                                     # the canary around every destination
-    wsn = ws.cpu().numpy()
-    assert (wsn[:GUARD] == 0x3C).all() and (wsn[GUARD + need:] == 0x3C).all()       # and around the workspace
-    assert (d_src.cpu().numpy() == src).all()
-    return st[1:-1], ho[1:-1], out
+def run_batch(datas, entropy, handed_null=False):
+    """One yv3_jpeg_decode_batch_ex over ``datas`` through `tests.jpeg_abi.decode`, which asserts that nothing outside the
+    destinations, the statuses, the counts and the workspace was written.  Returns statuses, hand-over counts and the destination
+    bytes of every image.  ``handed_null``: the call gets no array for the counts (and those returned are the fill value)."""
+    r = jpeg_abi.decode(datas, entry="ex", entropy=entropy, handed_null=handed_null)
+    return r.statuses, r.handed, r.images
 
 
 def test_every_setting_in_one_mixed_batch(files):
@@ -233,39 +184,12 @@ def test_damaged_files_get_the_serial_status():
 def test_lying_records_stay_inside_their_buffers():
     """test_gpu_jpeg's lying-record case through the parallel stage: the same statuses as the serial one."""
     good, _, _ = damaged_files()
-    lib = _ffi.lib()
-    B = 4
-    infos = (_ffi.JpegInfo * B)()
-    for k in range(B):
-        infos[k] = jpeg.parse(good)
-    host = (_ffi.JpegInfo * B)()
-    ctypes.memmove(host, infos, ctypes.sizeof(infos))
-    infos[1].scan_length = 1 << 40
-    infos[2].width = 20000
-    n = 64 * 48 * 3
-    d_src = torch.from_numpy(np.frombuffer(good, np.uint8).copy()).to(DEV)
-    d_soff = torch.zeros(B, dtype=torch.int64, device=DEV)
-    d_doff = torch.tensor([0, n, 2 * n, 3 * n - 1], dtype=torch.int64, device=DEV)
-    d_info = torch.from_numpy(np.frombuffer(infos, np.uint8).copy()).to(DEV)
-    need = lib.yv3_jpeg_workspace_bytes_ex(ctypes.addressof(host), B, PARALLEL)
-    results = []
-    for entropy in (SERIAL, PARALLEL):
-        dst = torch.full((3 * n + GUARD,), 0xA5, dtype=torch.uint8, device=DEV)
-        ws = torch.empty(need, dtype=torch.uint8, device=DEV)
-        status = torch.full((B,), 777, dtype=torch.int32, device=DEV)
-        handed = torch.full((B,), 555, dtype=torch.int32, device=DEV)
-        desc = _ffi.JpegBatchDesc(src=d_src.data_ptr(), src_bytes=d_src.numel(), src_offsets=d_soff.data_ptr(), infos=d_info.data_ptr(),
-                                  infos_host=ctypes.addressof(host), dst=dst.data_ptr(), dst_bytes=3 * n, dst_offsets=d_doff.data_ptr(),
-                                  status=status.data_ptr(), B=B)
-        _ffi.check(lib.yv3_jpeg_decode_batch_ex(ctypes.byref(desc), entropy, handed.data_ptr(), ws.data_ptr(), need, _ffi.stream_ptr()),
-                   "yv3_jpeg_decode_batch_ex")
-        torch.cuda.synchronize()
-        results.append((status.tolist(), dst.cpu().numpy()))
-        if entropy == PARALLEL:
-            assert handed.tolist() == [0, 0, 0, 0]
-    assert results[0][0] == results[1][0] == [0, _ffi.JPEG_S_BOUNDS, _ffi.JPEG_S_INFO, _ffi.JPEG_S_BOUNDS]
-    assert np.array_equal(results[0][1], results[1][1])
-    assert np.array_equal(results[1][1][:n].reshape(48, 64, 3), pil_rgb(good)) and (results[1][1][n:] == 0xA5).all()
+    results = [jpeg_abi.decode([good], entry="ex", entropy=entropy, order=[0, 0, 0, 0], dev_infos=lying_records(good), dst_cut=1)
+               for entropy in (SERIAL, PARALLEL)]
+    assert results[1].handed.tolist() == [0, 0, 0, 0]
+    assert results[0].statuses.tolist() == results[1].statuses.tolist() == [0, _ffi.JPEG_S_BOUNDS, _ffi.JPEG_S_INFO, _ffi.JPEG_S_BOUNDS]
+    assert all(np.array_equal(a, b) for a, b in zip(results[0].images, results[1].images))
+    assert np.array_equal(results[1].images[0], pil_rgb(good)) and all((px == jpeg_abi.FILL).all() for px in results[1].images[1:])
 
 
 def test_decode_batch_parallel_one_upload_one_status_read(files):

@@ -5,13 +5,13 @@ routine and the pixel arithmetic over valid, truncated, corrupted and random inp
 import ctypes
 import io
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 from PIL import Image, JpegImagePlugin
 
+from tests.jpeg_checkers import build_checker, run_checker          # noqa: F401 (run_checker: tests.test_jpeg_craft_host's too)
 from yolo_v3_amd import _ffi, jpeg
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -182,23 +182,7 @@ def test_decode_batch_checks_its_arguments_before_launching():
 # ---- the stand-alone sanitizer program -------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    out = tmp_path_factory.mktemp("jpeg_host") / "jpeg_host_check"
-    cxx = shutil.which("c++")
-    # the sanitizer runtimes are linked statically (clang's default; gcc needs the flags): the program then runs in any environment
-    cmd = [cxx] if cxx else ["/opt/rocm/bin/hipcc", "-x", "c++"]
-    if cxx and b"Free Software Foundation" in subprocess.run([cxx, "--version"], capture_output=True).stdout:
-        cmd += ["-static-libasan", "-static-libubsan"]
-    subprocess.run(cmd + ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall",
-                          "-I", os.path.join(REPO, "include"), "-I", os.path.join(REPO, "yolo_v3_amd", "csrc"),
-                          os.path.join(REPO, "tests", "jpeg_host_check.cpp"), "-o", str(out)], check=True)
-    return str(out)
-
-
-def run_checker(checker, *args):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([checker] + [str(a) for a in args], capture_output=True, text=True, env=env)
-    assert r.returncode == 0 and "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stdout + r.stderr[-4000:]
-    return r.stdout
+    return build_checker("jpeg_host_check.cpp", tmp_path_factory.mktemp("jpeg_host") / "jpeg_host_check")
 
 
 HOST_CASES = [("RGB", 2, (33, 19), 75, False, None), ("RGB", 1, (17, 13), 30, True, 2), ("RGB", 0, (7, 9), 100, False, None),

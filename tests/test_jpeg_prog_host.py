@@ -6,43 +6,27 @@ mirrors against the header and the argument checks that answer before any launch
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests import jpeg_checkers
 from tests import jpeg_prog_craft as craft
+from tests.jpeg_checkers import run_checker
 from yolo_v3_amd import _ffi, jpeg
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def build_checker(out, sanitize):
-    """Compiles tests/jpeg_prog_host_check.cpp to ``out``; with ``sanitize`` under ASan + UBSan (the CPU tests of this file), without
-    as a plain program (what a GPU test may build and run where it runs)."""
-    cxx = shutil.which("c++")
-    cmd = [cxx] if cxx else ["/opt/rocm/bin/hipcc", "-x", "c++"]
-    if sanitize:
-        # the sanitizer runtimes are linked statically (clang's default; gcc needs the flags): the program then runs in any environment
-        if cxx and b"Free Software Foundation" in subprocess.run([cxx, "--version"], capture_output=True).stdout:
-            cmd += ["-static-libasan", "-static-libubsan"]
-        cmd += ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    subprocess.run(cmd + ["-std=c++17", "-O1", "-Wall", "-I", os.path.join(REPO, "include"), "-I", os.path.join(REPO, "yolo_v3_amd", "csrc"),
-                          os.path.join(REPO, "tests", "jpeg_prog_host_check.cpp"), "-o", str(out)], check=True)
-    return str(out)
+    """tests/jpeg_prog_host_check.cpp as the program ``out`` (the GPU tests build it without the sanitizers, for its statuses)."""
+    return jpeg_checkers.build_checker("jpeg_prog_host_check.cpp", out, sanitize)
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
     return build_checker(tmp_path_factory.mktemp("jpeg_prog_host") / "jpeg_prog_host_check", sanitize=True)
-
-
-def run_checker(checker, *args):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([checker] + [str(a) for a in args], capture_output=True, text=True, env=env)
-    assert r.returncode == 0 and "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stdout + r.stderr[-4000:]
-    return r.stdout
 
 
 def host_decode(checker, tmp_path, files):

@@ -7,7 +7,6 @@ import ctypes
 import io
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -15,6 +14,7 @@ import pytest
 from PIL import Image
 
 from tests import jpeg_craft
+from tests.jpeg_checkers import build_checker, run_checker
 from tests.test_jpeg_host import HOST_CASES, PHOTO, encode, picture
 from yolo_v3_amd import _ffi, jpeg
 
@@ -28,22 +28,7 @@ MIN_FACTOR = int(re.search(r"#define YV3_JPEG_SYNC_MIN_BYTES \((\d+) \* YV3_JPEG
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    out = tmp_path_factory.mktemp("jpeg_sync_host") / "jpeg_sync_host_check"
-    cxx = shutil.which("c++")
-    cmd = [cxx] if cxx else ["/opt/rocm/bin/hipcc", "-x", "c++"]
-    if cxx and b"Free Software Foundation" in subprocess.run([cxx, "--version"], capture_output=True).stdout:
-        cmd += ["-static-libasan", "-static-libubsan"]
-    subprocess.run(cmd + ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall",
-                          "-I", os.path.join(REPO, "include"), "-I", os.path.join(REPO, "yolo_v3_amd", "csrc"),
-                          os.path.join(REPO, "tests", "jpeg_sync_host_check.cpp"), "-o", str(out)], check=True)
-    return str(out)
-
-
-def run_checker(checker, *args):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([checker] + [str(a) for a in args], capture_output=True, text=True, env=env)
-    assert r.returncode == 0 and "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout
+    return build_checker("jpeg_sync_host_check.cpp", tmp_path_factory.mktemp("jpeg_sync_host") / "jpeg_sync_host_check")
 
 
 def scan_of(data):

@@ -21,6 +21,11 @@
 //                    section 8f.2): the layout kernel's sibling re-checks the progressive device records and hands the later
 //                    kernels frame records of its own making; one workgroup per progressive image decodes its scans level by
 //                    level, independent scans side by side.  Baseline images of such a batch take entropy_kernel as always
+// What more than one kernel needs is written once: the two layout kernels differ in the frame copy and the source check and share
+// the range checks, the slot record and the hand-out of the workspace (baseline_src_ok, dst_ok, sized_slot, hand_out_shares); both entropy kernels
+// cut a unit's bytes with yv3_jpeg_unit_bytes (jpeg_entropy.h, which the stand-alone host programs of tests/ run too);
+// find_restart_markers is the workgroup's marker search, which entropy_kernel keeps written out (see there); and the three
+// entry points are forwards to one decode_batch, which holds every argument check and the launch sequence.
 // An image whose status is not 0 after any stage is skipped by the later ones: its destination bytes are not written.
 // (compiled with -ffp-contract=off like the other non-MFMA files; there is no floating point here)
 #include "yv3_common.h"
@@ -42,6 +47,49 @@ std::atomic<long long> g_launches{0};
 
 static_assert(sizeof(yv3_jpeg_info) % 8 == 0, "layout_prog_kernel copies the records in 8-byte words");
 
+// ---- what layout_kernel and layout_prog_kernel share ---------------------------------------------------------------------------
+// These take values, not the record: the caller loads what it passes in one go, ahead of the compares (read through the record
+// behind the && chain, each field is a global round trip of its own).
+// The single scan (scan_offset, scan_length) of a baseline record yv3_jpeg_geometry accepted, inside a source buffer of
+// src_bytes at offset so
+__device__ bool baseline_src_ok(long long so, long long scan_offset, long long scan_length, long long src_bytes) {
+    return so >= 0 && so <= src_bytes && scan_offset <= src_bytes - so && scan_length <= src_bytes - so - scan_offset &&
+           scan_length <= 0x7fffffffLL;
+}
+
+// The n3 = 3 * width * height bytes of an image at offset dof of a destination buffer of dst_bytes, in 64 bits
+__device__ bool dst_ok(long long dof, long long n3, long long dst_bytes) { return dof >= 0 && dof <= dst_bytes && n3 <= dst_bytes - dof; }
+
+// An image's slot record from its status so far (0: geometry g); the three offsets are sizes for now (hand_out_shares)
+__device__ yv3_jpeg_slot sized_slot(int code, const yv3_jpeg_geom& g, int prog) {
+    yv3_jpeg_slot s;
+    s.coef_off = code ? 0 : g.coef_bytes;
+    s.plane_off = code ? 0 : g.plane_bytes;
+    s.unit_off = code ? 0 : g.unit_bytes;
+    s.status = code; s.prog = prog;
+    return s;
+}
+
+// One lane, after a barrier behind the sized slots: the sizes of every accepted image become offsets from `pos` on, in batch order
+// (an image whose share does not fit ws_bytes is refused), and status[b] is written for every image.
+__device__ void hand_out_shares(yv3_jpeg_slot* slots, int B, long long pos, long long ws_bytes, int* status) {
+    for (int b = 0; b < B; ++b) {
+        yv3_jpeg_slot s = slots[b];
+        if (!s.status) {
+            const long long total = s.coef_off + s.plane_off + s.unit_off;
+            if (pos > ws_bytes || total > ws_bytes - pos) {
+                s.status = YV3_JPEG_S_BOUNDS;
+            } else {
+                const long long c = pos, p = pos + s.coef_off, u = p + s.plane_off;
+                s.coef_off = c; s.plane_off = p; s.unit_off = u;
+                pos += total;
+            }
+            slots[b] = s;
+        }
+        status[b] = s.status;
+    }
+}
+
 __global__ __launch_bounds__(256) void layout_kernel(const yv3_jpeg_info* __restrict__ infos, const long long* __restrict__ src_offsets,
                                                      long long src_bytes, const long long* __restrict__ dst_offsets, long long dst_bytes,
                                                      int B, yv3_jpeg_slot* __restrict__ slots, long long ws_bytes, int* __restrict__ status) {
@@ -51,37 +99,14 @@ __global__ __launch_bounds__(256) void layout_kernel(const yv3_jpeg_info* __rest
         int code = yv3_jpeg_geometry(f, &g);
         if (!code) {
             const long long so = src_offsets[b], dof = dst_offsets[b], n3 = (long long)f->width * f->height * 3;
-            const bool src_ok = so >= 0 && so <= src_bytes && f->scan_offset <= src_bytes - so &&
-                                f->scan_length <= src_bytes - so - f->scan_offset && f->scan_length <= 0x7fffffffLL;
-            const bool dst_ok = dof >= 0 && dof <= dst_bytes && n3 <= dst_bytes - dof;
-            if (!src_ok || !dst_ok) code = YV3_JPEG_S_BOUNDS;
+            const bool src_ok = baseline_src_ok(so, f->scan_offset, f->scan_length, src_bytes), fits = dst_ok(dof, n3, dst_bytes);
+            if (!src_ok || !fits) code = YV3_JPEG_S_BOUNDS;
         }
-        yv3_jpeg_slot s;
-        s.coef_off = code ? 0 : g.coef_bytes;              // sizes for now; thread 0 turns them into offsets below
-        s.plane_off = code ? 0 : g.plane_bytes;
-        s.unit_off = code ? 0 : g.unit_bytes;
-        s.status = code; s.prog = 0;
-        slots[b] = s;
+        slots[b] = sized_slot(code, g, 0);
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        long long pos = yv3_jpeg_round256((long long)B * (long long)sizeof(yv3_jpeg_slot));
-        for (int b = 0; b < B; ++b) {
-            yv3_jpeg_slot s = slots[b];
-            if (!s.status) {
-                const long long total = s.coef_off + s.plane_off + s.unit_off;
-                if (pos > ws_bytes || total > ws_bytes - pos) {
-                    s.status = YV3_JPEG_S_BOUNDS;
-                } else {
-                    const long long c = pos, p = pos + s.coef_off, u = p + s.plane_off;
-                    s.coef_off = c; s.plane_off = p; s.unit_off = u;
-                    pos += total;
-                }
-                slots[b] = s;
-            }
-            status[b] = s.status;
-        }
-    }
+    if (threadIdx.x == 0)
+        hand_out_shares(slots, B, yv3_jpeg_round256((long long)B * (long long)sizeof(yv3_jpeg_slot)), ws_bytes, status);
 }
 
 // One unit of YV3_JPEG_SYNC_MIN_BYTES or more, by the whole workgroup (every lane calls it with the same arguments).  0: coef
@@ -198,19 +223,42 @@ __device__ int sync_unit(const unsigned char* scan, long long begin, long long e
     return s_err;
 }
 
+// The restart markers of a scan of len bytes and nunits >= 2 units, by the whole workgroup (every lane calls it with the same
+// arguments): each lane counts those of its 256th of the scan, lane 0 turns counts[256] into an exclusive prefix and their sum
+// into *s_total, and where that is the nunits - 1 the scan must hold each lane writes its positions to marks[] in file order.
+// Returns whether it is.  Both barriers are reached by all 256 lanes, and the result is read from LDS after a barrier, the same
+// for every lane.  counts[] and *s_total (LDS) are the caller's again after its next barrier.
+// entropy_prog_kernel calls it once per scan.  entropy_kernel carries the same search written out (see there): called from that
+// kernel the routine compiles to other branches, which moves and re-registers the decode loop behind it.
+__device__ __forceinline__ bool find_restart_markers(const unsigned char* scan, int len, int nunits, int* marks, int* counts, int* s_total) {
+    const int t = threadIdx.x;
+    const int chunk = (len + 255) / 256;
+    const long long lo = (long long)t * chunk;
+    const long long hi = lo + chunk < len ? lo + chunk : len;
+    int cnt = 0;
+    for (long long i = lo; i < hi; ++i)
+        if (yv3_jpeg_restart_at(scan, i, len)) ++cnt;
+    counts[t] = cnt;
+    __syncthreads();
+    if (t == 0) {
+        int run = 0;
+        for (int k = 0; k < 256; ++k) { const int c = counts[k]; counts[k] = run; run += c; }
+        *s_total = run;
+    }
+    __syncthreads();
+    if (*s_total != nunits - 1) return false;
+    int k = counts[t];
+    for (long long i = lo; i < hi; ++i)
+        if (yv3_jpeg_restart_at(scan, i, len)) { if (k < nunits - 1) marks[k] = (int)i; ++k; }
+    return true;
+}
+
 // The byte range [*begin, *end) of unit u between the restart markers found at marks[], and its MCUs [*m0, *m1).  0, or
 // YV3_JPEG_S_MARKER for markers out of order or out of range.
 __device__ int unit_range(const unsigned char* scan, int len, const int* marks, const yv3_jpeg_geom& g, int u, long long* begin,
                           long long* end, int* m0, int* m1) {
-    int code = 0;
-    *begin = 0; *end = len;
-    if (u > 0) *begin = (long long)marks[u - 1] + 2;
-    if (u < g.nunits - 1) {
-        *end = marks[u];
-        if (*end < 0 || *end + 1 >= len || scan[*end + 1] != 0xD0 + (u & 7)) code = YV3_JPEG_S_MARKER;
-    }
-    if (*begin < 0 || *begin > len || *end < *begin) code = YV3_JPEG_S_MARKER;
-    *m0 = u * g.mcus_per_unit;
+    const int code = yv3_jpeg_unit_bytes(scan, len, marks, g.nunits, u, begin, end);      // (first: the other order costs
+    *m0 = u * g.mcus_per_unit;                                                            // entropy_kernel<1> a register)
     *m1 = g.nmcu - *m0 < g.mcus_per_unit ? g.nmcu : *m0 + g.mcus_per_unit;
     return code;
 }
@@ -251,7 +299,9 @@ __global__ __launch_bounds__(256) void entropy_kernel(const unsigned char* __res
     const int len = (int)f->scan_length;                   // <= 2^31 - 1: layout_kernel
     int* marks = (int*)(ws + slot.unit_off);               // [nunits - 1] used, [nunits] reserved
     const int nunits = g.nunits;
-    if (nunits > 1) {
+    if (nunits > 1) {                                      // find_restart_markers, written out: with the call this kernel's decode loop
+                                                           // is laid out differently (same instructions, other registers and
+                                                           // addresses), and the serial stage measured 2 % slower on one file set
         const int chunk = (len + 255) / 256;
         const long long lo = (long long)t * chunk;
         const long long hi = lo + chunk < len ? lo + chunk : len;
@@ -364,7 +414,7 @@ __global__ __launch_bounds__(256) void layout_prog_kernel(const yv3_jpeg_info* _
             const long long so = src_offsets[b], dof = dst_offsets[b], n3 = (long long)f->width * f->height * 3;
             bool src_ok = so >= 0 && so <= src_bytes;
             if (src_ok && pi < 0) {
-                src_ok = f->scan_offset <= src_bytes - so && f->scan_length <= src_bytes - so - f->scan_offset && f->scan_length <= 0x7fffffffLL;
+                src_ok = baseline_src_ok(so, f->scan_offset, f->scan_length, src_bytes);
             } else if (src_ok) {
                 const yv3_jpeg_prog* p = progs + pi;
                 for (int i = 0; i < p->nscans; ++i) {        // offset, length >= 0 and length < 2^31: yv3_jpegp_check
@@ -372,36 +422,15 @@ __global__ __launch_bounds__(256) void layout_prog_kernel(const yv3_jpeg_info* _
                     src_ok = src_ok && o <= src_bytes - so && l <= src_bytes - so - o;
                 }
             }
-            const bool dst_ok = dof >= 0 && dof <= dst_bytes && n3 <= dst_bytes - dof;
-            if (!src_ok || !dst_ok) code = YV3_JPEG_S_BOUNDS;
+            const bool fits = dst_ok(dof, n3, dst_bytes);
+            if (!src_ok || !fits) code = YV3_JPEG_S_BOUNDS;
         }
-        yv3_jpeg_slot s;
-        s.coef_off = code ? 0 : g.coef_bytes;
-        s.plane_off = code ? 0 : g.plane_bytes;
-        s.unit_off = code ? 0 : g.unit_bytes;
-        s.status = code; s.prog = pi >= 0;
-        slots[b] = s;
+        slots[b] = sized_slot(code, g, pi >= 0);
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        long long pos = yv3_jpeg_round256((long long)B * (long long)sizeof(yv3_jpeg_slot)) +
-                        yv3_jpeg_round256((long long)B * (long long)sizeof(yv3_jpeg_info));
-        for (int b = 0; b < B; ++b) {
-            yv3_jpeg_slot s = slots[b];
-            if (!s.status) {
-                const long long total = s.coef_off + s.plane_off + s.unit_off;
-                if (pos > ws_bytes || total > ws_bytes - pos) {
-                    s.status = YV3_JPEG_S_BOUNDS;
-                } else {
-                    const long long c = pos, p = pos + s.coef_off, u = p + s.plane_off;
-                    s.coef_off = c; s.plane_off = p; s.unit_off = u;
-                    pos += total;
-                }
-                slots[b] = s;
-            }
-            status[b] = s.status;
-        }
-    }
+    if (threadIdx.x == 0)                                  // slots | frames | shares
+        hand_out_shares(slots, B, yv3_jpeg_round256((long long)B * (long long)sizeof(yv3_jpeg_slot)) +
+                                      yv3_jpeg_round256((long long)B * (long long)sizeof(yv3_jpeg_info)), ws_bytes, status);
 }
 
 // The entropy stage of a progressive image: one workgroup per image.  Lane 0 derives the geometry, every scan's unit count and
@@ -462,30 +491,9 @@ __global__ __launch_bounds__(256) void entropy_prog_kernel(const unsigned char* 
     for (int i = 0; i < nscans; ++i) {                     // the restart markers of every scan that has some
         const int nunits = s_units[i];
         if (nunits < 2) continue;                          // (the same for every lane: read from LDS after a barrier)
-        const unsigned char* scan = file + p->scans[i].offset;
-        const int len = (int)p->scans[i].length;
-        const int chunk = (len + 255) / 256;
-        const long long lo = (long long)t * chunk;
-        const long long hi = lo + chunk < len ? lo + chunk : len;
-        int cnt = 0;
-        for (long long k = lo; k < hi && k + 1 < len; ++k)
-            if (scan[k] == 0xFF && (scan[k + 1] & 0xF8) == 0xD0) ++cnt;
-        counts[t] = cnt;
-        __syncthreads();
-        if (t == 0) {
-            int run = 0;
-            for (int k = 0; k < 256; ++k) { const int c = counts[k]; counts[k] = run; run += c; }
-            s_total = run;
-        }
-        __syncthreads();
-        if (s_total != nunits - 1) {
-            if (t == 0) atomicMax(&s_status, YV3_JPEG_S_MARKER);
-        } else {
-            int k = counts[t];
-            int* m = marks + s_first[i];
-            for (long long q = lo; q < hi && q + 1 < len; ++q)
-                if (scan[q] == 0xFF && (scan[q + 1] & 0xF8) == 0xD0) { if (k < nunits - 1) m[k] = (int)q; ++k; }
-        }
+        const bool found = find_restart_markers(file + p->scans[i].offset, (int)p->scans[i].length, nunits, marks + s_first[i], counts,
+                                                &s_total);
+        if (!found && t == 0) atomicMax(&s_status, YV3_JPEG_S_MARKER);
         __syncthreads();                                   // counts[] and s_total are free for the next scan
     }
     short* coef = (short*)(ws + slot.coef_off);
@@ -529,15 +537,8 @@ __global__ __launch_bounds__(256) void entropy_prog_kernel(const unsigned char* 
             const yv3_jpegp_scan sc = p->scans[i];
             const int len = (int)sc.length;
             const unsigned char* scan = file + sc.offset;
-            const int* m = marks + s_first[i];
-            long long begin = 0, end = len;
-            int code = 0;
-            if (k > 0) begin = (long long)m[k - 1] + 2;
-            if (k < nunits - 1) {
-                end = m[k];
-                if (end < 0 || end + 1 >= len || scan[end + 1] != 0xD0 + (k & 7)) code = YV3_JPEG_S_MARKER;
-            }
-            if (begin < 0 || begin > len || end < begin) code = YV3_JPEG_S_MARKER;
+            long long begin, end;
+            int code = yv3_jpeg_unit_bytes(scan, len, marks + s_first[i], nunits, k, &begin, &end);
             const int items = yv3_jpegp_scan_items(&g, sc.ns, sc.comp[0]);
             const int per = sc.restart_interval ? sc.restart_interval : items;
             const int i0 = k * per, i1 = items - i0 < per ? items : i0 + per;
@@ -631,95 +632,70 @@ __global__ __launch_bounds__(256) void colour_kernel(const yv3_jpeg_info* __rest
     }
 }
 
-}  // namespace
-
-extern "C" int yv3_jpeg_decode_batch_ex(const yv3_jpeg_batch_desc* desc, int entropy, int* handed_over, void* ws, size_t ws_bytes,
-                                        void* stream) {
+// The three entry points: every argument check (before any launch), then four launches, five with progressive images (P > 0:
+// layout_prog_kernel instead of layout_kernel, the later kernels read its frame records, and entropy_prog_kernel runs behind
+// entropy_kernel).  With P == 0 the four record pointers are not looked at.
+int decode_batch(const yv3_jpeg_batch_desc* d, const yv3_jpeg_prog* progs, const yv3_jpeg_prog* progs_host, const int* prog_of,
+                 const int* prog_of_host, int P, int entropy, int* handed_over, void* ws, size_t ws_bytes, void* stream) {
     if (entropy != YV3_JPEG_ENTROPY_SERIAL && entropy != YV3_JPEG_ENTROPY_PARALLEL) return YV3_EINVAL;
-    if (!desc || !ws || ((uintptr_t)ws & 255) != 0) return YV3_EINVAL;
-    if (!desc->src || !desc->src_offsets || !desc->infos || !desc->infos_host || !desc->dst || !desc->dst_offsets || !desc->status)
-        return YV3_EINVAL;
-    const int B = desc->B;
-    if (B <= 0 || B > 65535 || desc->src_bytes <= 0 || desc->dst_bytes <= 0) return YV3_EINVAL;
+    if (!d || !ws || ((uintptr_t)ws & 255) != 0) return YV3_EINVAL;
+    if (!d->src || !d->src_offsets || !d->infos || !d->infos_host || !d->dst || !d->dst_offsets || !d->status) return YV3_EINVAL;
+    if (P != 0 && (!progs || !progs_host || !prog_of || !prog_of_host)) return YV3_EINVAL;
+    const int B = d->B;
+    if (B <= 0 || B > 65535 || P < 0 || P > 65535 || d->src_bytes <= 0 || d->dst_bytes <= 0) return YV3_EINVAL;
     long long max_blocks = 1, max_groups = 1;
-    for (int b = 0; b < B; ++b) {
-        yv3_jpeg_geom g;
-        if (yv3_jpeg_geometry(desc->infos_host + b, &g)) return YV3_ESHAPE;
-        const long long groups = ((long long)desc->infos_host[b].width * desc->infos_host[b].height + 3) / 4;
-        if (g.nblocks > max_blocks) max_blocks = g.nblocks;
-        if (groups > max_groups) max_groups = groups;
-    }
-    const size_t need = yv3_jpeg_batch_workspace(desc->infos_host, B, true);
+    const size_t need = yv3_jpeg_batch_workspace(d->infos_host, B, prog_of_host, progs_host, P, true, &max_blocks, &max_groups);
     if (need == 0) return YV3_ESHAPE;
     if (ws_bytes < need) return YV3_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     yv3_jpeg_slot* slots = (yv3_jpeg_slot*)ws;
     unsigned char* wsb = (unsigned char*)ws;
-    YV3_JPEG_LAUNCH(layout_kernel, dim3(1), dim3(256), 0, s, desc->infos, desc->src_offsets, desc->src_bytes, desc->dst_offsets,
-                       desc->dst_bytes, B, slots, (long long)ws_bytes, desc->status);
+    const yv3_jpeg_info* infos = d->infos;                 // what the kernels behind the layout read: the records, or its frames
+    if (P) {
+        yv3_jpeg_info* frames = (yv3_jpeg_info*)(wsb + yv3_jpeg_round256((long long)B * (long long)sizeof(yv3_jpeg_slot)));
+        YV3_JPEG_LAUNCH(layout_prog_kernel, dim3(1), dim3(256), 0, s, d->infos, progs, prog_of, P, d->src_offsets, d->src_bytes,
+                           d->dst_offsets, d->dst_bytes, B, slots, frames, (long long)ws_bytes, d->status);
+        infos = frames;
+    } else {
+        YV3_JPEG_LAUNCH(layout_kernel, dim3(1), dim3(256), 0, s, d->infos, d->src_offsets, d->src_bytes, d->dst_offsets, d->dst_bytes, B,
+                           slots, (long long)ws_bytes, d->status);
+    }
     YV3_CHECK_LAUNCH();
+    // (a batch of progressive images alone still takes this launch: its workgroups leave at once, after zeroing handed_over)
     if (entropy == YV3_JPEG_ENTROPY_PARALLEL)
-        YV3_JPEG_LAUNCH(entropy_kernel<1>, dim3(B), dim3(256), 0, s, desc->src, desc->src_offsets, desc->infos, slots, wsb, desc->status,
-                           handed_over);
+        YV3_JPEG_LAUNCH(entropy_kernel<1>, dim3(B), dim3(256), 0, s, d->src, d->src_offsets, infos, slots, wsb, d->status, handed_over);
     else
-        YV3_JPEG_LAUNCH(entropy_kernel<0>, dim3(B), dim3(256), 0, s, desc->src, desc->src_offsets, desc->infos, slots, wsb, desc->status,
-                           (int*)0);
+        YV3_JPEG_LAUNCH(entropy_kernel<0>, dim3(B), dim3(256), 0, s, d->src, d->src_offsets, infos, slots, wsb, d->status, (int*)0);
     YV3_CHECK_LAUNCH();
+    if (P) {
+        YV3_JPEG_LAUNCH(entropy_prog_kernel, dim3(B), dim3(256), 0, s, d->src, d->src_offsets, infos, progs, prog_of, slots, wsb, d->status);
+        YV3_CHECK_LAUNCH();
+    }
     const int gx_idct = (int)(max_blocks / 256 + 1 < 4096 ? max_blocks / 256 + 1 : 4096);
-    YV3_JPEG_LAUNCH(idct_kernel, dim3(gx_idct, B), dim3(256), 0, s, desc->infos, slots, wsb, desc->status);
+    YV3_JPEG_LAUNCH(idct_kernel, dim3(gx_idct, B), dim3(256), 0, s, infos, slots, wsb, d->status);
     YV3_CHECK_LAUNCH();
     const int gx_col = (int)(max_groups / 256 + 1 < 4096 ? max_groups / 256 + 1 : 4096);
-    YV3_JPEG_LAUNCH(colour_kernel, dim3(gx_col, B), dim3(256), 0, s, desc->infos, slots, (const unsigned char*)wsb, desc->dst,
-                       desc->dst_offsets);
+    YV3_JPEG_LAUNCH(colour_kernel, dim3(gx_col, B), dim3(256), 0, s, infos, slots, (const unsigned char*)wsb, d->dst, d->dst_offsets);
     YV3_CHECK_LAUNCH();
     return 0;
 }
 
+}  // namespace
+
 extern "C" int yv3_jpeg_decode_batch(const yv3_jpeg_batch_desc* desc, void* ws, size_t ws_bytes, void* stream) {
-    return yv3_jpeg_decode_batch_ex(desc, YV3_JPEG_ENTROPY_SERIAL, 0, ws, ws_bytes, stream);
+    return decode_batch(desc, 0, 0, 0, 0, 0, YV3_JPEG_ENTROPY_SERIAL, 0, ws, ws_bytes, stream);
+}
+
+extern "C" int yv3_jpeg_decode_batch_ex(const yv3_jpeg_batch_desc* desc, int entropy, int* handed_over, void* ws, size_t ws_bytes,
+                                        void* stream) {
+    return decode_batch(desc, 0, 0, 0, 0, 0, entropy, handed_over, ws, ws_bytes, stream);
 }
 
 extern "C" int yv3_jpeg_decode_batch_prog(const yv3_jpeg_batch_desc_prog* desc, int entropy, int* handed_over, void* ws, size_t ws_bytes,
                                           void* stream) {
     if (!desc) return YV3_EINVAL;
-    if (desc->P == 0) return yv3_jpeg_decode_batch_ex(&desc->base, entropy, handed_over, ws, ws_bytes, stream);
-    if (entropy != YV3_JPEG_ENTROPY_SERIAL && entropy != YV3_JPEG_ENTROPY_PARALLEL) return YV3_EINVAL;
-    const yv3_jpeg_batch_desc* d = &desc->base;
-    if (!ws || ((uintptr_t)ws & 255) != 0) return YV3_EINVAL;
-    if (!d->src || !d->src_offsets || !d->infos || !d->infos_host || !d->dst || !d->dst_offsets || !d->status) return YV3_EINVAL;
-    if (!desc->progs || !desc->progs_host || !desc->prog_of || !desc->prog_of_host) return YV3_EINVAL;
-    const int B = d->B, P = desc->P;
-    if (B <= 0 || B > 65535 || P < 0 || P > 65535 || d->src_bytes <= 0 || d->dst_bytes <= 0) return YV3_EINVAL;
-    long long max_blocks = 1, max_groups = 1;
-    const size_t need = yv3_jpeg_batch_workspace_prog(d->infos_host, desc->prog_of_host, desc->progs_host, P, B, &max_blocks, &max_groups);
-    if (need == 0) return YV3_ESHAPE;
-    if (ws_bytes < need) return YV3_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    yv3_jpeg_slot* slots = (yv3_jpeg_slot*)ws;
-    unsigned char* wsb = (unsigned char*)ws;
-    yv3_jpeg_info* frames = (yv3_jpeg_info*)(wsb + yv3_jpeg_round256((long long)B * (long long)sizeof(yv3_jpeg_slot)));
-    YV3_JPEG_LAUNCH(layout_prog_kernel, dim3(1), dim3(256), 0, s, d->infos, desc->progs, desc->prog_of, P, d->src_offsets, d->src_bytes,
-                       d->dst_offsets, d->dst_bytes, B, slots, frames, (long long)ws_bytes, d->status);
-    YV3_CHECK_LAUNCH();
-    // (a batch of progressive images alone still takes this launch: its workgroups leave at once, after zeroing handed_over)
-    if (entropy == YV3_JPEG_ENTROPY_PARALLEL)
-        YV3_JPEG_LAUNCH(entropy_kernel<1>, dim3(B), dim3(256), 0, s, d->src, d->src_offsets, (const yv3_jpeg_info*)frames, slots, wsb,
-                           d->status, handed_over);
-    else
-        YV3_JPEG_LAUNCH(entropy_kernel<0>, dim3(B), dim3(256), 0, s, d->src, d->src_offsets, (const yv3_jpeg_info*)frames, slots, wsb,
-                           d->status, (int*)0);
-    YV3_CHECK_LAUNCH();
-    YV3_JPEG_LAUNCH(entropy_prog_kernel, dim3(B), dim3(256), 0, s, d->src, d->src_offsets, (const yv3_jpeg_info*)frames, desc->progs,
-                       desc->prog_of, slots, wsb, d->status);
-    YV3_CHECK_LAUNCH();
-    const int gx_idct = (int)(max_blocks / 256 + 1 < 4096 ? max_blocks / 256 + 1 : 4096);
-    YV3_JPEG_LAUNCH(idct_kernel, dim3(gx_idct, B), dim3(256), 0, s, (const yv3_jpeg_info*)frames, slots, wsb, d->status);
-    YV3_CHECK_LAUNCH();
-    const int gx_col = (int)(max_groups / 256 + 1 < 4096 ? max_groups / 256 + 1 : 4096);
-    YV3_JPEG_LAUNCH(colour_kernel, dim3(gx_col, B), dim3(256), 0, s, (const yv3_jpeg_info*)frames, slots, (const unsigned char*)wsb, d->dst,
-                       d->dst_offsets);
-    YV3_CHECK_LAUNCH();
-    return 0;
+    return decode_batch(&desc->base, desc->progs, desc->progs_host, desc->prog_of, desc->prog_of_host, desc->P, entropy, handed_over, ws,
+                        ws_bytes, stream);
 }
 
 extern "C" long long yv3_jpeg_launch_count(void) { return g_launches.load(std::memory_order_relaxed); }

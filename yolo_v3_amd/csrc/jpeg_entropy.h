@@ -164,6 +164,28 @@ YV3_HD int yv3_jpeg_natural(int k) {
     return zz[k & 63];
 }
 
+// Whether a restart marker (FF D0 .. FF D7) stands at byte i of a scan of len bytes
+YV3_HD bool yv3_jpeg_restart_at(const unsigned char* scan, long long i, long long len) {
+    return i + 1 < len && scan[i] == 0xFF && (scan[i + 1] & 0xF8) == 0xD0;
+}
+
+// The byte range [*begin, *end) of unit u of a scan of len bytes and nunits units, between the restart markers found at
+// marks[0 .. nunits - 2] (int in the kernels, long long in the host programs).  0, or YV3_JPEG_S_MARKER for markers out of
+// order or out of range.  Which MCUs or items the unit holds is the caller's: baseline and progressive scans differ there.
+template <typename M>
+YV3_HD int yv3_jpeg_unit_bytes(const unsigned char* scan, long long len, const M* marks, int nunits, int u, long long* begin,
+                               long long* end) {
+    int code = 0;
+    *begin = 0; *end = len;
+    if (u > 0) *begin = (long long)marks[u - 1] + 2;
+    if (u < nunits - 1) {
+        *end = marks[u];
+        if (*end < 0 || *end + 1 >= len || scan[*end + 1] != 0xD0 + (u & 7)) code = YV3_JPEG_S_MARKER;
+    }
+    if (*begin < 0 || *begin > len || *end < *begin) code = YV3_JPEG_S_MARKER;
+    return code;
+}
+
 // Decodes MCUs [mcu0, mcu1) of the frame from bytes [begin, end) of `scan` into coef ([nblocks][64] int16, natural order,
 // zeroed by the caller: EOB and runs leave zeros).  tabs: the eight tables (DC 0..3, AC 0..3); td / ta: the selectors per
 // component; natural: yv3_jpeg_natural as a table of 64 (the kernel keeps it in LDS).  DC prediction starts at 0 (a unit

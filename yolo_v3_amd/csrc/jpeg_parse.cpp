@@ -305,41 +305,25 @@ extern "C" int yv3_jpeg_parse_ex(const unsigned char* data, size_t n, int accept
     return rc;
 }
 
-size_t yv3_jpeg_batch_workspace(const yv3_jpeg_info* infos, int B, bool strict) {
-    if (!infos || B <= 0 || B > 65535) return 0;
+size_t yv3_jpeg_batch_workspace(const yv3_jpeg_info* infos, int B, const int* prog_of, const yv3_jpeg_prog* progs, int P, bool strict,
+                                long long* max_blocks, long long* max_groups) {
+    if (!infos || B <= 0 || B > 65535 || P < 0 || P > 65535 || (P && (!prog_of || !progs))) return 0;
     long long total = yv3_jpeg_round256((long long)B * (long long)sizeof(yv3_jpeg_slot));
+    if (P) total += yv3_jpeg_round256((long long)B * (long long)sizeof(yv3_jpeg_info));       // layout_prog_kernel's frame records
     for (int b = 0; b < B; ++b) {
         yv3_jpeg_geom g;
-        if (yv3_jpeg_geometry(infos + b, &g) == 0) total += g.total_bytes;
-        else if (strict) return 0;
-    }
-    return (size_t)total;
-}
-
-extern "C" size_t yv3_jpeg_workspace_bytes(const yv3_jpeg_info* infos_host, int B) {
-    return yv3_jpeg_batch_workspace(infos_host, B, false);
-}
-
-extern "C" size_t yv3_jpeg_workspace_bytes_ex(const yv3_jpeg_info* infos_host, int B, int entropy) {
-    if (entropy != YV3_JPEG_ENTROPY_SERIAL && entropy != YV3_JPEG_ENTROPY_PARALLEL) return 0;
-    return yv3_jpeg_batch_workspace(infos_host, B, false);      // the parallel stage's records live in LDS
-}
-
-size_t yv3_jpeg_batch_workspace_prog(const yv3_jpeg_info* infos, const int* prog_of, const yv3_jpeg_prog* progs, int P, int B,
-                                     long long* max_blocks, long long* max_groups) {
-    if (!infos || !prog_of || !progs || P <= 0 || P > 65535 || B <= 0 || B > 65535) return 0;
-    long long total = yv3_jpeg_round256((long long)B * (long long)sizeof(yv3_jpeg_slot)) +
-                      yv3_jpeg_round256((long long)B * (long long)sizeof(yv3_jpeg_info));
-    for (int b = 0; b < B; ++b) {
-        yv3_jpeg_geom g;
-        if (prog_of[b] < -1 || prog_of[b] >= P) return 0;
-        if (prog_of[b] < 0) {
-            if (yv3_jpeg_geometry(infos + b, &g) != 0) return 0;
+        const int pi = P ? prog_of[b] : -1;
+        bool ok;
+        if (pi < 0) {
+            ok = pi == -1 && yv3_jpeg_geometry(infos + b, &g) == 0;
         } else {
-            if (infos[b].reason != YV3_JPEG_PROGRESSIVE) return 0;
             yv3_jpeg_info frame = infos[b];
             yv3_jpegp_as_frame(&frame);
-            if (yv3_jpegp_geometry(&frame, progs + prog_of[b], &g) != 0) return 0;
+            ok = pi < P && infos[b].reason == YV3_JPEG_PROGRESSIVE && yv3_jpegp_geometry(&frame, progs + pi, &g) == 0;
+        }
+        if (!ok) {
+            if (strict || P) return 0;
+            continue;
         }
         total += g.total_bytes;
         const long long groups = ((long long)infos[b].width * infos[b].height + 3) / 4;
@@ -352,6 +336,13 @@ size_t yv3_jpeg_batch_workspace_prog(const yv3_jpeg_info* infos, const int* prog
 extern "C" size_t yv3_jpeg_workspace_bytes_prog(const yv3_jpeg_info* infos_host, const int* prog_of_host, const yv3_jpeg_prog* progs_host,
                                                 int P, int B, int entropy) {
     if (entropy != YV3_JPEG_ENTROPY_SERIAL && entropy != YV3_JPEG_ENTROPY_PARALLEL) return 0;
-    if (P == 0) return yv3_jpeg_batch_workspace(infos_host, B, false);
-    return yv3_jpeg_batch_workspace_prog(infos_host, prog_of_host, progs_host, P, B, 0, 0);
+    return yv3_jpeg_batch_workspace(infos_host, B, prog_of_host, progs_host, P, false, 0, 0);
+}
+
+extern "C" size_t yv3_jpeg_workspace_bytes_ex(const yv3_jpeg_info* infos_host, int B, int entropy) {
+    return yv3_jpeg_workspace_bytes_prog(infos_host, 0, 0, 0, B, entropy);      // (the parallel stage's records live in LDS)
+}
+
+extern "C" size_t yv3_jpeg_workspace_bytes(const yv3_jpeg_info* infos_host, int B) {
+    return yv3_jpeg_workspace_bytes_prog(infos_host, 0, 0, 0, B, YV3_JPEG_ENTROPY_SERIAL);
 }

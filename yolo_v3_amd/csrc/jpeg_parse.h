@@ -10,11 +10,10 @@ struct yv3_jpeg_slot {
     int prog;                                    // 1: a progressive image (yv3_jpeg_decode_batch_prog), entropy_prog_kernel's
 };
 
-// Workspace bytes of a batch from its host records; with `strict`, a record yv3_jpeg_geometry refuses makes the result 0.
-size_t yv3_jpeg_batch_workspace(const yv3_jpeg_info* infos, int B, bool strict);
-
-// The workspace of yv3_jpeg_decode_batch_prog with P > 0: the B slot records, a copy of the B info records in which every
-// progressive image's is a frame record (yv3_jpegp_as_frame; both 256-aligned as a whole), then each image's share.
-// 0 for a record or an index that is refused.
-size_t yv3_jpeg_batch_workspace_prog(const yv3_jpeg_info* infos, const int* prog_of, const yv3_jpeg_prog* progs, int P, int B,
-                                     long long* max_blocks, long long* max_groups);
+// Workspace bytes of a batch from its host records: the B slot records, with P > 0 a copy of the B info records in which every
+// progressive image's is a frame record (yv3_jpegp_as_frame; both 256-aligned as a whole), then each image's share.  P == 0:
+// every image is a baseline one, prog_of and progs are not looked at, and a record yv3_jpeg_geometry refuses is skipped, or with
+// `strict` makes the result 0.  P > 0: always strict, and 0 too for a prog_of entry outside [-1, P).  max_blocks / max_groups
+// (or null): raised to the largest image's blocks and groups of four pixels, which size the grids of idct_kernel and colour_kernel.
+size_t yv3_jpeg_batch_workspace(const yv3_jpeg_info* infos, int B, const int* prog_of, const yv3_jpeg_prog* progs, int P, bool strict,
+                                long long* max_blocks, long long* max_groups);

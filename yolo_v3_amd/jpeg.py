@@ -197,7 +197,7 @@ def submit(sources, device=None, stream=None, dst=None, entropy="serial", progre
     pixels of the images PIL already decoded -- and the images the kernels write, each at a 256-aligned offset; it is filled by
     ONE host-to-device copy.  ``dst = (tensor, offsets)``: image i is decoded into the uint8 1-D ``tensor`` (`TrainBatches`'
     arena) at ``offsets[i]`` instead, for every i (None entries are not allowed: split the batch).  ``entropy="parallel"``: the
-    self-synchronising entropy stage (``yv3_jpeg_decode_batch_ex``) -- the same statuses and pixels; its hand-over counts lie
+    self-synchronising entropy stage (``YV3_JPEG_ENTROPY_PARALLEL``) -- the same statuses and pixels; its hand-over counts lie
     behind the statuses and come back in the same read.  ``progressive=True``: sources are parsed with the progressive flag; an
     accepted progressive file goes to the device (``yv3_jpeg_decode_batch_prog``, one more launch), its record in the same
     upload and its status in the same read.  ``entropy`` affects the baseline images of the batch alone."""
@@ -267,9 +267,11 @@ def submit(sources, device=None, stream=None, dst=None, entropy="serial", progre
         if B:
             host[o_info:o_info + B * _INFO_BYTES] = np.frombuffer(infos, dtype=np.uint8, count=B * _INFO_BYTES)
             host[o_soff:o_soff + B * 8].view(np.int64)[:] = src_off
+        progs_host = prog_of_host = None                     # without a progressive image the calls below get null record pointers
         if P:
             prog_arr = (_ffi.JpegProg * P)(*progs)
             prog_of_arr = (ctypes.c_int * B)(*prog_of)
+            progs_host, prog_of_host = ctypes.addressof(prog_arr), ctypes.addressof(prog_of_arr)
             host[o_prog:o_prog + P * _PROG_BYTES] = np.frombuffer(prog_arr, dtype=np.uint8, count=P * _PROG_BYTES)
             host[o_pof:o_pof + B * 4].view(np.int32)[:] = prog_of
         if dst is None:
@@ -302,11 +304,7 @@ def submit(sources, device=None, stream=None, dst=None, entropy="serial", progre
         keep = [buf]
         status_host = None
         if B:
-            if P:
-                ws_bytes = lib.yv3_jpeg_workspace_bytes_prog(ctypes.addressof(infos), ctypes.addressof(prog_of_arr),
-                                                             ctypes.addressof(prog_arr), P, B, ENTROPY[entropy])
-            else:
-                ws_bytes = lib.yv3_jpeg_workspace_bytes_ex(ctypes.addressof(infos), B, ENTROPY[entropy])
+            ws_bytes = lib.yv3_jpeg_workspace_bytes_prog(ctypes.addressof(infos), prog_of_host, progs_host, P, B, ENTROPY[entropy])
             ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
             base = buf.data_ptr()
             desc = _ffi.JpegBatchDesc(src=base + o_src, src_bytes=src_bytes, src_offsets=base + o_soff, infos=base + o_info,
@@ -314,14 +312,11 @@ def submit(sources, device=None, stream=None, dst=None, entropy="serial", progre
                                       dst_offsets=base + o_doff, status=base + o_stat, B=B)
             handed = base + o_stat + B * 4 if parallel else None
             launched = lib.yv3_jpeg_launch_count()
-            if P:                                           # a batch without a progressive image takes the call it always took
-                pdesc = _ffi.JpegBatchDescProg(base=desc, progs=base + o_prog, progs_host=ctypes.addressof(prog_arr),
-                                               prog_of=base + o_pof, prog_of_host=ctypes.addressof(prog_of_arr), P=P)
-                _ffi.check(lib.yv3_jpeg_decode_batch_prog(ctypes.byref(pdesc), ENTROPY[entropy], handed, ws.data_ptr(), ws.numel(),
-                                                          stream.cuda_stream), "yv3_jpeg_decode_batch_prog")
-            else:
-                _ffi.check(lib.yv3_jpeg_decode_batch_ex(ctypes.byref(desc), ENTROPY[entropy], handed, ws.data_ptr(), ws.numel(),
-                                                        stream.cuda_stream), "yv3_jpeg_decode_batch_ex")
+            # (P == 0: the same four launches as yv3_jpeg_decode_batch_ex, by definition)
+            pdesc = _ffi.JpegBatchDescProg(base=desc, progs=base + o_prog if P else None, progs_host=progs_host,
+                                           prog_of=base + o_pof if P else None, prog_of_host=prog_of_host, P=P)
+            _ffi.check(lib.yv3_jpeg_decode_batch_prog(ctypes.byref(pdesc), ENTROPY[entropy], handed, ws.data_ptr(), ws.numel(),
+                                                      stream.cuda_stream), "yv3_jpeg_decode_batch_prog")
             counters["launches"] += lib.yv3_jpeg_launch_count() - launched
             counters["prog_images"] += P
             n_read = 2 * B if parallel else B
