@@ -535,6 +535,45 @@ int yv3_extra_augment(const unsigned char* src, long long src_bytes, const long 
                       const void* programs, int B, unsigned char* out, long long out_bytes, const long long* out_offsets,
                       void* workspace, size_t workspace_bytes, int* status, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Affine training augmentation: rotate, scale, shear, shift (csrc/affine_augment.hip) for B packed uint8 RGB images of any
+ * sizes, one program per image; the output has the source's size.  tests/affine_aug_ref.py is the definition.  A program holds
+ * two 2x3 float64 matrices in continuous pixel coordinates (pixel (x, y) covers [x, x+1) x [y, y+1)), both computed by the
+ * caller: fwd maps source to output and moves the labels, inv (its inverse) maps output to source and fetches the pixels.
+ *   pixels   Pillow's Image.transform(size, AFFINE, inv, BILINEAR, fillcolor 128) on RGB, float64 without fused multiply-add:
+ *            xin = inv0 (x + 0.5) + inv1 (y + 0.5) + inv2 (yin from inv3..5); (128, 128, 128) unless 0 <= xin < W and
+ *            0 <= yin < H; otherwise, after xin -= 0.5, yin -= 0.5: x0 = floor(xin), dx = xin - x0 (y likewise), columns x0 and
+ *            x0 + 1 and row y0 clamped to the image, v1 = p[y0][x0] + (p[y0][x1] - p[y0][x0]) dx, v2 the same on row y0 + 1
+ *            (v2 = v1 when that row is outside), the byte is trunc(v1 + (v2 - v1) dy)
+ *   labels   rows (cls, cx, cy, w, h) relative to the source, float64: a row with w <= 0 or h <= 0 becomes zeros; otherwise its
+ *            absolute corners through fwd, the axis-aligned hull of the four, clipped to [0, W - eps] x [0, H - eps] (eps =
+ *            float32's), kept iff clipped area / hull area > 0.1 (bbs_remove_cut_out; a hull area <= 0 drops it) and written
+ *            back relative, in place; a dropped row is zeros (yv3_augment_labels drops zero rows and keeps order)
+ * active == 0 (the augmentation did not fire for this image): the image is copied, its rows are passed through untouched.
+ * The kernels check every image themselves and write status[b]: 0, or YV3_EINVAL (H or W <= 0, a byte range outside its
+ * buffer, a non-finite coefficient, active not 0 / 1); such an image is copied through and its rows are passed through (nothing
+ * is written for an image whose ranges are out of bounds).  The return value covers the host arguments (YV3_EINVAL), checked
+ * before the launch.  No workspace, no allocation, no synchronisation, no atomics: identical calls give identical bits.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct yv3_affine_program {
+    int active;                  /* 0: copy the image, pass its rows through; 1: transform        */
+    int reserved;
+    double fwd[6];               /* source -> output: x' = fwd0 x + fwd1 y + fwd2, y' from 3..5   */
+    double inv[6];               /* output -> source, the inverse of fwd                          */
+} yv3_affine_program;            /* 104 bytes */
+
+/* Pixels, one launch.  Image b = hw[2b] x hw[2b+1] x 3 bytes, read at src + src_offsets[b] (inside src_bytes: src may be a
+ * packed batch or a larger allocation the images are gathered from; it is not written; the same source may occur twice) and
+ * written at out + out_offsets[b] (inside out_bytes).  The out ranges of a batch must not overlap each other or the sources (the
+ * caller's duty).  All offsets are int64 bytes and need no alignment.  programs: yv3_affine_program[B] in device memory. */
+int yv3_affine_augment(const unsigned char* src, long long src_bytes, const long long* src_offsets, const int* hw,
+                       const void* programs, int B, unsigned char* out, long long out_bytes, const long long* out_offsets,
+                       int* status, void* stream);
+
+/* Labels, one launch.  labels, labels_out: [B][T][5] float64 (NULL when T == 0); labels_out may be labels. */
+int yv3_affine_labels(const double* labels, int B, int T, const int* hw, const void* programs,
+                      double* labels_out, int* status, void* stream);
+
 /* Stand-alone UpsampleGroup tail (reference darknet.py:159-162: ``F.interpolate(out, scale_factor=2, mode='nearest')`` then
  * ``torch.cat((out, route_tail), 1)``), NCHW fp32:  out[b, c, y, x] = up[b, c, y/2, x/2] for c < c_up, tail[b, c - c_up, y, x] beyond.
  * up [B, c_up, h, w], tail [B, c_tail, 2h, 2w], out [B, c_up + c_tail, 2h, 2w].  Pure data movement (bit-exact).  Inside YoloNet

@@ -21,6 +21,7 @@ from .detect import detect, Detector, predict  # noqa: F401
 from .dist import detect_sharded                # noqa: F401
 from .augment import sample_params, augment_batch, TrainBatches, epoch_schedule   # noqa: F401
 from .extra_augment import sample_extra, extra_augment_batch   # noqa: F401
+from .affine_augment import sample_affine, affine_augment_batch   # noqa: F401
 from . import optim                             # noqa: F401
 from .optim import SGD, clip_grad_norm_         # noqa: F401
 

@@ -147,6 +147,11 @@ class JpegBatchDescProg(ctypes.Structure):
                 ("prog_of_host", c_void_p), ("P", c_int)]
 
 
+class AffineProgram(ctypes.Structure):
+    """struct yv3_affine_program (include/yv3.h)."""
+    _fields_ = [("active", c_int), ("reserved", c_int), ("fwd", ctypes.c_double * 6), ("inv", ctypes.c_double * 6)]
+
+
 _SIGNATURES = {
     "yv3_version": (c_int, []),
     "yv3_conv_workspace_bytes": (ctypes.c_size_t, []),
@@ -195,6 +200,9 @@ _SIGNATURES = {
     "yv3_extra_augment_workspace_bytes": (c_size_t, [c_longlong]),
     "yv3_extra_augment": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_longlong, c_void_p,
                                   c_void_p, c_size_t, c_void_p, c_void_p]),
+    "yv3_affine_augment": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_longlong, c_void_p,
+                                   c_void_p, c_void_p]),
+    "yv3_affine_labels": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "yv3_upsample2x_concat": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "yv3_correct_boxes": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "yv3_gather_boxes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),

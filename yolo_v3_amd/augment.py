@@ -31,6 +31,7 @@ import torch
 
 from . import _ffi
 from .extra_augment import sample_extra, check_programs, extra_augment_batch      # noqa: F401 (part of this module's interface)
+from .affine_augment import sample_affine, check_affine_programs, affine_augment_batch      # noqa: F401 (likewise)
 
 MAX_LABELS = 90
 N_PARAMS = 8                 # dhue, dsat, dexp, top, right, bottom, left, flip
@@ -388,17 +389,28 @@ class TrainBatches:
     sample_extra(seeds, shapes)), ...)`` (`yolo_v3_amd.extra_augment`) -- the extras run on the raw source (the arena keeps raw
     sources), labels are untouched.  The switch is part of a ``state_dict``'s config when it is on.
 
+    ``affine`` (None / False, True, or a dict of ``sample_affine``'s keyword arguments; True takes its defaults): rotation, zoom,
+    shear and shift (`yolo_v3_amd.affine_augment`) in front of the extras: every batch is ``augment_batch(*affine_augment_batch(
+    images, labels, sample_affine(seeds, shapes, **affine)), ...)``, with ``extra_augment_batch`` on the warped images in between
+    when ``extra`` is on too -- so blur, sharpen and noise act on the warped image and are not interpolated.  The boxes move with
+    the pixels.  The setting is part of a ``state_dict``'s config when it is on.
+
     ``state_dict()`` / ``load_state_dict()`` resume between two batches with the same data order."""
 
     def __init__(self, list_file, batch_size, dim, seed, shuffle=True, max_labels=MAX_LABELS, multiscale=None, dim_interval=10,
                  workers=0, prefetch=2, cache_bytes=0, decode="pil", extra=False, entropy="serial", progressive=False,
-                 **aug):
+                 affine=None, **aug):
         if decode not in ("pil", "gpu"):
             raise ValueError("decode must be 'pil' or 'gpu'")
         if entropy not in ("serial", "parallel"):
             raise ValueError("entropy must be 'serial' or 'parallel'")
         self.decode, self._side, self.extra, self.entropy = decode, None, bool(extra), entropy
         self.progressive = bool(progressive)
+        if affine is None or affine is False:
+            self.affine = None
+        else:
+            self.affine = {} if affine is True else {k: (float(v) if k == "p" else [float(x) for x in v]) for k, v in dict(affine).items()}
+            sample_affine([], [], **self.affine)         # validates the names and the ranges
         with open(list_file, 'r') as f:
             self.img_list = [line.strip() for line in f.readlines() if line.strip()]
         self.label_list = [label_path(p) for p in self.img_list]
@@ -431,6 +443,8 @@ class TrainBatches:
                   "aug": dict(self.aug)}
         if self.extra:                                   # absent when off: a state written before the switch existed still loads
             config["extra"] = True
+        if self.affine is not None:                      # likewise
+            config["affine"] = dict(self.affine) or True
         return config
 
     def state_dict(self):
@@ -460,7 +474,7 @@ class TrainBatches:
         """One epoch's batches as ``(images, labels, params, dim)``, everything ``augment_batch`` takes, without touching a GPU.
         ``images[i]`` is None for a source that is resident in the arena (``params`` were drawn with its recorded shape); with
         ``decode="gpu"`` it is the undecoded `jpeg.Source` (``.shape`` from its header)."""
-        for _, images, labels, params, dim, _ in self._host_batches():
+        for _, images, labels, params, dim, _, _ in self._host_batches():
             yield images, labels, params, dim
 
     def _host_batches(self):
@@ -507,8 +521,9 @@ class TrainBatches:
                     labels.append(rows)
                 params = sample_params(seeds[k * bs:k * bs + len(idx)], shapes=shapes, **self.aug)
                 programs = sample_extra(seeds[k * bs:k * bs + len(idx)], shapes) if self.extra else None
+                warps = sample_affine(seeds[k * bs:k * bs + len(idx)], shapes, **self.affine) if self.affine is not None else None
                 self._pos = (epoch, k + 1)
-                yield idx, images, labels, params, self.dim if dims is None else dims[k], programs
+                yield idx, images, labels, params, self.dim if dims is None else dims[k], programs, warps
         finally:
             if pool is not None:
                 pool.shutdown(wait=True, cancel_futures=True)
@@ -540,7 +555,7 @@ class TrainBatches:
         """Enqueue the decode of a host batch's sources on the loader's stream: those the arena admits (in batch order, by the
         same rule and so at the same offsets as ``decode="pil"``) straight into it, the others into a buffer of the batch."""
         from . import jpeg
-        idx, images, labels, params, dim, _ = batch
+        idx, images, labels, params, dim, _, _ = batch
         new = [i for i, im in enumerate(images) if im is not None]
         admitted, offsets = [], []
         if self.cache_bytes > 0 and new:
@@ -566,7 +581,7 @@ class TrainBatches:
 
     def _complete(self, launched):
         batch, admitted, jobs, pos = launched
-        idx, images, labels, params, dim, programs = batch
+        idx, images, labels, params, dim, programs, warps = batch
         out = list(images)
         for which, job in jobs:
             for i, view in zip(which, job.finish()):         # raises what read_image_rgb raises for a file nobody can decode
@@ -577,6 +592,8 @@ class TrainBatches:
             if out[i] is None:
                 out[i] = self._resident[j][0]
         self._pos = pos                                      # the host half runs one batch ahead: report the batch handed out
+        if warps is not None:
+            out, labels = affine_augment_batch(out, labels, warps)
         if programs is not None:
             out = extra_augment_batch(out, programs)
         return augment_batch(out, labels, dim, params, self.max_labels)
@@ -608,9 +625,11 @@ class TrainBatches:
     def _iter_pil(self):
         host = self._host_batches()
         try:
-            for idx, images, labels, params, dim, programs in host:
+            for idx, images, labels, params, dim, programs, warps in host:
                 if self.cache_bytes > 0:
                     images = self._admit(idx, images, labels)
+                if warps is not None:
+                    images, labels = affine_augment_batch(images, labels, warps)
                 if programs is not None:
                     images = extra_augment_batch(images, programs)
                 yield augment_batch(images, labels, dim, params, self.max_labels)
