@@ -1002,8 +1002,8 @@ int yv3_jpeg_decode_batch_prog(const yv3_jpeg_batch_desc_prog* desc, int entropy
 long long yv3_jpeg_launch_count(void);
 
 /* ------------------------------------------------------------------------------------------
- * The update step (csrc/optim.hip; yolo_v3_amd/optim.py): torch's clip_grad_norm_ and torch.optim.SGD over a list of fp32
- * tensors, a few launches for the whole list.  The list arguments (g, p, buf, n) are HOST arrays of `count` device pointers /
+ * The update step (csrc/optim.hip; yolo_v3_amd/optim.py): torch's clip_grad_norm_, torch.optim.SGD and torch.optim.Adam / AdamW
+ * over a list of fp32 tensors, a few launches for the whole list.  The list arguments (g, p, buf, n, ...) are HOST arrays of `count` device pointers /
  * element counts; they are read during the call and travel in the kernel arguments, so the caller may reuse them at once.
  * Each workgroup owns YV3_OPTIM_CHUNK consecutive elements of one tensor.  Pointers need 4-byte alignment only (16-byte
  * aligned entries take 16-byte accesses); every access is bounded by the entry's n.  Entries must not overlap.  No allocation,
@@ -1037,6 +1037,28 @@ int yv3_grad_scale(float* const* g, const long long* n, int count, const float* 
  * g is not written.  buf may be NULL when momentum == 0; coef (device) may be NULL. */
 int yv3_sgd_step(float* const* p, const float* const* g, float* const* buf, const long long* n, int count, const float* coef,
                  float lr, float momentum, float one_minus_dampening, float weight_decay, int flags, void* stream);
+
+#define YV3_ADAM_FIRST     1  /* the first step of these parameters: exp_avg, exp_avg_sq, max_exp_avg_sq are +0 and not read */
+#define YV3_ADAM_AMSGRAD   2
+#define YV3_ADAM_MAXIMIZE  4
+#define YV3_ADAM_DECOUPLED 8  /* AdamW: decay multiplies p; without it decay is the L2 coefficient added to g     */
+
+/* One Adam / AdamW step (torch.optim.Adam, not capturable) on every (p, g, exp_avg m, exp_avg_sq v, max_exp_avg_sq vmax) of the
+ * list with one set of scalars, which the caller reduces in double and rounds to fp32: w = 1 - beta1, beta2, one_minus_beta2,
+ * sqrt_bc2 = sqrt(1 - beta2^step), eps, neg_step_size = -(lr / (1 - beta1^step)), and decay = 1 - lr * weight_decay with
+ * DECOUPLED, weight_decay without (0: no decay).  Per element, each operation one fp32 rounding, no fused multiply-add, sqrt
+ * and divide correctly rounded, denormals kept:
+ *   gs = coef ? g * (*coef) : g;  if MAXIMIZE: gs = -gs;
+ *   if DECOUPLED: p = p * decay;  else if decay != 0: gs = gs + decay * p;
+ *   d = gs - m;   m = |w| < 0.5 ? m + w * d : gs - d * (1.0f - w);
+ *   v = v * beta2;   v = v + (one_minus_beta2 * gs) * gs;
+ *   s = v;  if AMSGRAD: s = vmax = vmax is NaN ? vmax : v is NaN ? v : vmax > v ? vmax : v;
+ *   den = sqrt(s) / sqrt_bc2 + eps;   p = p + neg_step_size * (m / den).
+ * g is not written.  max_exp_avg_sq may be NULL without AMSGRAD; coef (device) may be NULL.  The float4 path needs all of an
+ * entry's pointers 16-byte aligned. */
+int yv3_adam_step(float* const* p, const float* const* g, float* const* exp_avg, float* const* exp_avg_sq,
+                  float* const* max_exp_avg_sq, const long long* n, int count, const float* coef, float w, float beta2,
+                  float one_minus_beta2, float sqrt_bc2, float eps, float neg_step_size, float decay, int flags, void* stream);
 
 #ifdef __cplusplus
 }

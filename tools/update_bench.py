@@ -17,7 +17,18 @@ buffers; all three update the same parameters.  Interleaved rounds, median repor
 GB/s is over the bytes each must move, in fp32 words per parameter element: torch and `separate` 8 (norm: read g; clip: read and
 write g; update: read g, p, buf, write p, buf), `clipped` 6 (no rewrite of g).
 
-    python tools/update_bench.py [--batch 16] [--rounds 9] [--math bf16]
+With --optimizer adam | adamw the same protocol times Adam / AdamW (torch's default hyper-parameters on the same two groups):
+
+  torch       torch.nn.utils.clip_grad_norm_(params, 1000) + torch.optim.Adam.step(), torch's defaults (foreach kernels)
+  torch_fused the same with torch.optim.Adam(fused=True)
+  separate    yolo_v3_amd.optim.clip_grad_norm_(params, 1000) + yolo_v3_amd.optim.Adam.step()
+  clipped     yolo_v3_amd.optim.Adam.step_clipped(1000)
+
+and each row also carries `step_bytes`, the bytes the Adam step itself must move -- 28 per element (read g, p, exp_avg, exp_avg_sq;
+write p, exp_avg, exp_avg_sq), 36 with --amsgrad -- and `step_TBps`, those bytes over the row's median time (the norm's read of g
+and, where the gradients are rewritten, the clip's traffic come on top: `bytes` counts them as for SGD).
+
+    python tools/update_bench.py [--batch 16] [--rounds 9] [--math bf16] [--optimizer sgd|adam|adamw] [--amsgrad]
 """
 import argparse
 import json
@@ -39,12 +50,15 @@ MATH = {"f32": F32, "bf16": BF16, "bf16_act": BF16_ACT}
 DEV = "cuda:0"
 MAX_NORM, LR, BACKBONE_LR, WD, MOMENTUM = 1000.0, 1e-3, 1e-4, 5e-4, 0.9
 WORDS = {"torch": 8, "separate": 8, "clipped": 6}
+ADAM = {"adam": (torch.optim.Adam, optim.Adam), "adamw": (torch.optim.AdamW, optim.AdamW)}
 
 
-def two_groups(net, cls):
+def two_groups(net, cls, **hyper):
+    """The reference's two param groups; without `hyper`, its SGD settings."""
     backbone = {id(p) for p in net.feature.parameters()}
-    return cls([{"params": [p for p in net.parameters() if id(p) not in backbone], "lr": LR},
-                {"params": list(net.feature.parameters()), "lr": BACKBONE_LR}], LR, weight_decay=WD, momentum=MOMENTUM)
+    groups = [{"params": [p for p in net.parameters() if id(p) not in backbone], "lr": LR},
+              {"params": list(net.feature.parameters()), "lr": BACKBONE_LR}]
+    return cls(groups, LR, **hyper) if hyper else cls(groups, LR, weight_decay=WD, momentum=MOMENTUM)
 
 
 def summary(v):
@@ -56,7 +70,11 @@ def main():
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--math", choices=tuple(MATH), default="bf16")
+    ap.add_argument("--optimizer", choices=("sgd",) + tuple(ADAM), default="sgd")
+    ap.add_argument("--amsgrad", action="store_true", help="Adam / AdamW with amsgrad (36 bytes per element)")
     a = ap.parse_args()
+    if a.amsgrad and a.optimizer == "sgd":
+        ap.error("--amsgrad goes with --optimizer adam or adamw")
     net = YoloNet((416, 416), numClass=80)
     WeightManager(net).load_stream(trained_like_stream(80))
     net = net.to(DEV).train()
@@ -64,7 +82,12 @@ def main():
     x = torch.from_numpy(synth.images(a.batch, 416, 7)).to(DEV)
     tg = torch.from_numpy(R.random_rows(5, a.batch, 30, 80, (0.03, 0.8)))
     params = list(net.parameters())
-    opt_torch, opt_sep, opt_clip = two_groups(net, torch.optim.SGD), two_groups(net, optim.SGD), two_groups(net, optim.SGD)
+    if a.optimizer == "sgd":
+        opt_torch, opt_sep, opt_clip = two_groups(net, torch.optim.SGD), two_groups(net, optim.SGD), two_groups(net, optim.SGD)
+    else:
+        theirs, ours = ADAM[a.optimizer]
+        opt_torch, opt_fused = two_groups(net, theirs, amsgrad=a.amsgrad), two_groups(net, theirs, amsgrad=a.amsgrad, fused=True)
+        opt_sep, opt_clip = two_groups(net, ours, amsgrad=a.amsgrad), two_groups(net, ours, amsgrad=a.amsgrad)
 
     def backward():
         net.zero_grad(set_to_none=True)
@@ -78,7 +101,16 @@ def main():
         optim.clip_grad_norm_(params, MAX_NORM)
         opt_sep.step()
 
+    def torch_fused_update():
+        torch.nn.utils.clip_grad_norm_(params, MAX_NORM)
+        opt_fused.step()
+
     updates = {"torch": torch_update, "separate": separate_update, "clipped": lambda: opt_clip.step_clipped(MAX_NORM)}
+    words, step_bytes = dict(WORDS), None
+    if a.optimizer != "sgd":
+        updates = {"torch": torch_update, "torch_fused": torch_fused_update, "separate": updates["separate"], "clipped": updates["clipped"]}
+        step_words = 9 if a.amsgrad else 7
+        words = {"torch": step_words + 3, "torch_fused": step_words + 3, "separate": step_words + 3, "clipped": step_words + 1}
     backward()
     torch.cuda.synchronize()
     saved = [p.grad.detach().clone() for p in params]
@@ -87,6 +119,9 @@ def main():
     norm0 = float(torch.sqrt(sum((g.double() ** 2).sum() for g in saved)))
     out = {"batch": a.batch, "math": a.math, "tensors": len(params), "elements": n_elem, "grad_norm": round(norm0, 3),
            "max_norm": MAX_NORM, "rounds": a.rounds}
+    if a.optimizer != "sgd":
+        step_bytes = step_words * 4 * n_elem
+        out.update(optimizer=a.optimizer, amsgrad=a.amsgrad, step_bytes=step_bytes)
 
     # ---- the update alone, device events
     filler = torch.zeros(1 << 28, device=DEV)
@@ -114,8 +149,10 @@ def main():
         out[mode] = {}
         for k, v in times.items():
             r = summary(v)
-            r["bytes"] = WORDS[k] * 4 * n_elem
+            r["bytes"] = words[k] * 4 * n_elem
             r["GBps"] = round(r["bytes"] / r["median_ms"] / 1e6, 1)
+            if step_bytes:
+                r["step_TBps"] = round(step_bytes / r["median_ms"] / 1e9, 3)
             out[mode][k] = r
         print(mode, json.dumps(out[mode]), flush=True)
     del filler
@@ -152,8 +189,9 @@ def main():
     for k in updates:
         out["step"][k]["update_share_ms"] = round(out["step"][k]["median_ms"] - out["step"]["no_update"]["median_ms"], 4)
     for mode in ("alone", "queued"):           # the acceptance rule: the medians differ by more than max - min of either side
-        spread = max(out[mode][k]["max_ms"] - out[mode][k]["min_ms"] for k in ("torch", "clipped"))
-        out["clipped_faster_than_torch_beyond_spread_" + mode] = bool(out[mode]["torch"]["median_ms"] - out[mode]["clipped"]["median_ms"] > spread)
+        for rival in ("torch", "torch_fused")[:1 if a.optimizer == "sgd" else 2]:
+            spread = max(out[mode][k]["max_ms"] - out[mode][k]["min_ms"] for k in (rival, "clipped"))
+            out["clipped_faster_than_%s_beyond_spread_%s" % (rival, mode)] = bool(out[mode][rival]["median_ms"] - out[mode]["clipped"]["median_ms"] > spread)
     assert all(bool(torch.isfinite(p).all()) for p in params), "a parameter left the finite range"
     print(json.dumps(out))
 

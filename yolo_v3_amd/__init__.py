@@ -23,6 +23,6 @@ from .augment import sample_params, augment_batch, TrainBatches, epoch_schedule 
 from .extra_augment import sample_extra, extra_augment_batch   # noqa: F401
 from .affine_augment import sample_affine, affine_augment_batch   # noqa: F401
 from . import optim                             # noqa: F401
-from .optim import SGD, clip_grad_norm_         # noqa: F401
+from .optim import SGD, Adam, AdamW, clip_grad_norm_   # noqa: F401
 
 __version__ = "0.1.0"

@@ -245,6 +245,8 @@ _SIGNATURES = {
     "yv3_clip_coef": (c_int, [c_void_p, c_longlong, c_float, c_void_p, c_void_p]),
     "yv3_grad_scale": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "yv3_sgd_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_float, c_float, c_float, c_float, c_int, c_void_p]),
+    "yv3_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                              c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_int, c_void_p]),
 }
 # a _bf16 twin takes its base entry's arguments, with bf16 tensors where the base has fp32 ones (all void* here)
 _SIGNATURES.update({twin: _SIGNATURES[twin.replace("_bf16", "")] for twin in (

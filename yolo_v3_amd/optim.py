@@ -1,14 +1,15 @@
-"""The update step of training on the package's own kernels (csrc/optim.hip): ``clip_grad_norm_`` and ``SGD``.
+"""The update step of training on the package's own kernels (csrc/optim.hip): ``clip_grad_norm_``, ``SGD``, ``Adam`` and ``AdamW``.
 
 The reference's ``train_impl`` ends every mini-batch with ``nn.utils.clip_grad_norm_(net.parameters(), 1000)`` and
 ``optimizer.step()`` of a ``torch.optim.SGD``.  Both are here as multi-tensor HIP launches with torch's arithmetic, one fp32
 rounding per operation (include/yv3.h states it; tests/optim_ref.py restates it in numpy), and the norm summed in fp64 in a
 fixed order: repeated steps give identical bits.  ``SGD`` keeps torch's optimizer contract -- param groups, ``state_dict``
 (interchangeable with ``torch.optim.SGD`` in both directions), hooks, ``torch.optim.lr_scheduler`` -- and adds
-``step_clipped(max_norm)``, which applies the clip coefficient inside the update instead of rewriting the gradients.
+``step_clipped(max_norm)``, which applies the clip coefficient inside the update instead of rewriting the gradients.  ``Adam`` and
+``AdamW`` do the same for ``torch.optim.Adam`` / ``AdamW`` (tests/adam_ref.py is their definition).
 
 Everything runs on the current stream of the parameters' device, without a device-to-host read; the only allocations are the
-workspace (sized by the first call, grown when a later call has more chunks) and the momentum buffers of a parameter's first step.
+workspace (sized by the first call, grown when a later call has more chunks) and the state tensors of a parameter's first step.
 The workspace is per device: calls on one device are meant to come from one stream at a time.
 
 Parameters and gradients must be fp32, contiguous and on one GPU: anything else raises ``TypeError`` -- dtype and layout at
@@ -22,6 +23,8 @@ from . import _ffi
 
 CHUNK = 16384             # elements per workgroup: YV3_OPTIM_CHUNK of include/yv3.h (yv3_optim_chunk() returns it)
 _SGD_FIRST, _SGD_NESTEROV, _SGD_MAXIMIZE = 1, 2, 4
+_ADAM_FIRST, _ADAM_AMSGRAD, _ADAM_MAXIMIZE, _ADAM_DECOUPLED = 1, 2, 4, 8
+_ADAM_STATE = ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")
 
 _workspaces = {}          # device index -> _Workspace
 
@@ -77,6 +80,28 @@ def _with_grads(params):
         if p.numel():
             pairs.append((p, g))
     return pairs, device
+
+
+def _check_state(t, what, p):
+    """A per-parameter state tensor the kernels read and write: as its parameter, element for element."""
+    _check(t, what, p.device)
+    if t.numel() != p.numel():
+        raise TypeError("%s of %d elements for a parameter of %d" % (what, t.numel(), p.numel()))
+
+
+def _grouped(param_groups):
+    """[(group, its (p, g) pairs)] for the groups that have any, and the one device of them all."""
+    out, device = [], None
+    for group in param_groups:
+        pairs, dev = _with_grads(group["params"])
+        if not pairs:
+            continue
+        if device is None:
+            device = dev
+        elif dev != device:
+            raise TypeError("parameters on %s and %s: one update runs on one GPU" % (device, dev))
+        out.append((group, pairs))
+    return out, device
 
 
 def _ptrs(tensors):
@@ -184,23 +209,15 @@ class SGD(torch.optim.Optimizer):
     @torch.no_grad()
     def _update(self, max_norm):
         # everything is checked before the first launch
-        work, device, everything = [], None, []
-        for group in self.param_groups:
-            pairs, dev = _with_grads(group["params"])
-            if not pairs:
-                continue
-            if device is None:
-                device = dev
-            elif dev != device:
-                raise TypeError("parameters on %s and %s: one update runs on one GPU" % (device, dev))
+        work, everything = [], []
+        grouped, device = _grouped(self.param_groups)
+        for group, pairs in grouped:
             momentum = float(group["momentum"])
             first, later = [], []
             for p, g in pairs:
                 buf = self.state.get(p, {}).get("momentum_buffer") if momentum != 0 else None      # (no state entry made by looking)
                 if buf is not None:
-                    _check(buf, "a momentum buffer", p.device)
-                    if buf.numel() != p.numel():
-                        raise TypeError("a momentum buffer of %d elements for a parameter of %d" % (buf.numel(), p.numel()))
+                    _check_state(buf, "a momentum buffer", p)
                 (later if buf is not None else first).append((p, g, buf))
             flags = (_SGD_NESTEROV if group["nesterov"] else 0) | (_SGD_MAXIMIZE if group["maximize"] else 0)
             hyper = (float(group["lr"]), momentum, 1.0 - float(group["dampening"]), float(group["weight_decay"]))
@@ -233,3 +250,177 @@ class SGD(torch.optim.Optimizer):
                 written += ps
         torch.autograd.graph.increment_version(written)
         return total_norm
+
+
+def _refuse_device_reads(lr, betas, capturable):
+    """What would need a device-to-host read at every step."""
+    if capturable:
+        raise ValueError("capturable=True keeps `step` on the GPU; the bias corrections are computed on the host here")
+    if isinstance(betas[0], torch.Tensor) or isinstance(betas[1], torch.Tensor):
+        raise ValueError("tensor betas are not supported: pass floats")
+    if isinstance(lr, torch.Tensor):
+        if lr.numel() != 1:
+            raise ValueError("Tensor lr must be 1-element")
+        if lr.device.type != "cpu":
+            raise ValueError("a tensor lr on %s would be read back at every step: pass a float or a CPU tensor" % (lr.device,))
+
+
+def _adam_hyper(group):
+    """A param group's hyper-parameters as host numbers: (lr, beta1, beta2, eps, weight_decay, amsgrad, maximize, decoupled)."""
+    _refuse_device_reads(group["lr"], group["betas"], group.get("capturable"))
+    return (float(group["lr"]), float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]),
+            float(group["weight_decay"]), bool(group["amsgrad"]), bool(group["maximize"]), bool(group["decoupled_weight_decay"]))
+
+
+class Adam(torch.optim.Optimizer):
+    """``torch.optim.Adam`` on the package's kernels: the same constructor, ``defaults``, param groups and per-parameter state
+    (``step`` as a 0-dim fp32 CPU tensor, ``exp_avg``, ``exp_avg_sq``, ``max_exp_avg_sq`` with amsgrad; created by the parameter's
+    first step, uninitialised: that step does not read them), so ``state_dict()`` / ``load_state_dict()`` interchange with torch's
+    and ``torch.optim.lr_scheduler`` works (hyper-parameters are read from ``param_groups`` at every step).  The arithmetic is
+    torch's single-tensor path, one fp32 rounding per operation (include/yv3.h).  ``foreach``, ``differentiable`` and ``fused``
+    are accepted and ignored; ``capturable=True``, a tensor ``lr`` on the GPU, tensor betas and a ``step`` state on the GPU are
+    refused, since each would need a device-to-host read at every step.  ``load_state_dict`` brings ``step`` to the CPU (one read
+    per load), so checkpoints of torch's ``fused=True`` Adam load, and a group that carries ``fused=True`` resumes from its own.  Parameters are bucketed by
+    (hyper-parameters, step count, first step or not) -- the bias corrections depend on the step -- with one launch per block of
+    64 tensors of a bucket.  ``step_clipped`` and ``max_norm`` are those of ``SGD``."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None,
+                 maximize=False, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False):
+        _refuse_device_reads(lr, betas, capturable)                # (before the range checks: they would read a GPU lr)
+        if not 0.0 <= lr:
+            raise ValueError("Invalid learning rate: %s" % (lr,))
+        if not 0.0 <= eps:
+            raise ValueError("Invalid epsilon value: %s" % (eps,))
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError("Invalid beta parameter at index 0: %s" % (betas[0],))
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError("Invalid beta parameter at index 1: %s" % (betas[1],))
+        if not 0.0 <= weight_decay:
+            raise ValueError("Invalid weight_decay value: %s" % (weight_decay,))
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
+                        foreach=foreach, capturable=capturable, differentiable=differentiable, fused=fused,
+                        decoupled_weight_decay=decoupled_weight_decay)
+        super().__init__(params, defaults)
+        self._total_norm = None
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for group in self.param_groups:
+            group.setdefault("amsgrad", False)
+            group.setdefault("maximize", False)
+            group.setdefault("foreach", None)
+            group.setdefault("capturable", False)
+            group.setdefault("differentiable", False)
+            group.setdefault("fused", None)
+            group.setdefault("decoupled_weight_decay", False)
+            for p in group["params"]:
+                st = self.state.get(p, {})
+                if len(st) == 0:
+                    continue
+                if not torch.is_tensor(st["step"]):
+                    st["step"] = torch.tensor(float(st["step"]), dtype=torch.float32)
+                elif st["step"].device.type != "cpu":       # torch's fused layout, or load_state_dict's cast under fused=True
+                    st["step"] = st["step"].to("cpu", torch.float32)
+        self.__dict__.setdefault("_total_norm", None)
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        _adam_hyper(self.param_groups[-1])
+        for p in self.param_groups[-1]["params"]:           # (the device is checked by step(): a net may move to the GPU later)
+            _check(p, "a parameter", need_gpu=False)
+
+    def step(self, closure=None, *, max_norm=None):
+        """One update of every parameter that requires grad and has a ``.grad``; only their ``step`` moves.  With ``max_norm``, the
+        gradients' clip coefficient is computed first and applied inside the update (see ``step_clipped``)."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._total_norm = self._update(max_norm)
+        return loss
+
+    def step_clipped(self, max_norm):
+        """``clip_grad_norm_(all parameters, max_norm)`` and ``step()`` in one pass over the gradients: parameters and state get the
+        bits of the two separate calls, but the coefficient is applied while the update reads ``g``, so ``.grad`` IS LEFT UNSCALED
+        (the two calls leave ``g * coef`` there).  Returns ``total_norm`` like ``clip_grad_norm_``."""
+        self.step(max_norm=max_norm)
+        return self._total_norm
+
+    @torch.no_grad()
+    def _update(self, max_norm):
+        # everything is checked before the first launch and before any state is made or moved
+        buckets, everything = {}, []
+        hypers = {id(group): _adam_hyper(group) for group in self.param_groups}
+        grouped, device = _grouped(self.param_groups)
+        for group, pairs in grouped:
+            hyper = hypers[id(group)]
+            amsgrad = hyper[5]
+            for p, g in pairs:
+                st = self.state.get(p)                      # (no state entry made by looking)
+                if not st:
+                    now, entry = 1.0, (p, g, None, None, None)
+                else:
+                    step = st["step"]
+                    if not isinstance(step, torch.Tensor) or step.numel() != 1:
+                        raise TypeError("the `step` state must be a 1-element tensor, got %r" % (step,))
+                    if step.device.type != "cpu":
+                        raise TypeError("a `step` state on %s (torch's capturable / fused layout) would be read back at every step: "
+                                        "move it to the CPU" % (step.device,))
+                    now = step.item() + 1.0                 # (a CPU tensor: no device read)
+                    for name in _ADAM_STATE if amsgrad else _ADAM_STATE[:2]:
+                        if name not in st:
+                            raise TypeError("a parameter's state lacks %s" % name)
+                        _check_state(st[name], name, p)
+                    entry = (p, g, st["exp_avg"], st["exp_avg_sq"], st["max_exp_avg_sq"] if amsgrad else None)
+                buckets.setdefault((hyper, now, not st), []).append(entry)
+                everything.append(entry)
+        if not everything:
+            return torch.tensor(0.0) if max_norm is not None else None
+        lib = _ffi.lib()
+        with torch.cuda.device(device):
+            s, coef, total_norm = _ffi.stream_ptr(), None, None
+            if max_norm is not None:
+                ws = _norm_and_coef([e[1] for e in everything], max_norm, device)
+                coef, total_norm = ws.out.data_ptr() + 4, ws.out[0]
+            written = []
+            for ((lr, beta1, beta2, eps, wd, amsgrad, maximize, decoupled), now, first), entries in buckets.items():
+                ps, gs = [e[0] for e in entries], [e[1] for e in entries]
+                if first:
+                    for p in ps:
+                        st = self.state[p]
+                        st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                        st["exp_avg"] = torch.empty_like(p, memory_format=torch.contiguous_format)
+                        st["exp_avg_sq"] = torch.empty_like(p, memory_format=torch.contiguous_format)
+                        if amsgrad:
+                            st["max_exp_avg_sq"] = torch.empty_like(p, memory_format=torch.contiguous_format)
+                states = [self.state[p] for p in ps]
+                for st in states:
+                    st["step"].fill_(now)                   # step + 1, rounded to the tensor's dtype as `step += 1` rounds it
+                ms, vs = [st["exp_avg"] for st in states], [st["exp_avg_sq"] for st in states]
+                xs = [st["max_exp_avg_sq"] for st in states] if amsgrad else None
+                bc1, bc2 = 1 - beta1 ** now, 1 - beta2 ** now
+                flags = (_ADAM_FIRST if first else 0) | (_ADAM_AMSGRAD if amsgrad else 0) | (_ADAM_MAXIMIZE if maximize else 0)
+                decay = 0.0
+                if wd != 0:
+                    decay = 1 - lr * wd if decoupled else wd
+                    flags |= _ADAM_DECOUPLED if decoupled else 0
+                _ffi.check(lib.yv3_adam_step(_ptrs(ps), _ptrs(gs), _ptrs(ms), _ptrs(vs), _ptrs(xs) if xs else None, _sizes(ps), len(ps),
+                                             coef, 1 - beta1, beta2, 1 - beta2, bc2 ** 0.5, eps, -(lr / bc1), decay, flags, s),
+                           "yv3_adam_step")
+                written += ps + ms + vs + (xs or [])
+        torch.autograd.graph.increment_version(written)
+        return total_norm
+
+
+class AdamW(Adam):
+    """``torch.optim.AdamW``: ``Adam`` with ``decoupled_weight_decay=True`` and torch's default ``weight_decay=1e-2``."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
+                 foreach=None, capturable=False, differentiable=False, fused=None):
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, foreach=foreach, maximize=maximize, capturable=capturable,
+                         differentiable=differentiable, fused=fused, decoupled_weight_decay=True)
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for group in self.param_groups:
+            group["decoupled_weight_decay"] = True
