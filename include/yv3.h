@@ -1002,6 +1002,98 @@ int yv3_jpeg_decode_batch_prog(const yv3_jpeg_batch_desc_prog* desc, int entropy
 long long yv3_jpeg_launch_count(void);
 
 /* ------------------------------------------------------------------------------------------
+ * Baseline JPEG encode (csrc/jpeg_enc.h, csrc/jpeg_enc.hip): uint8 RGB or grey pixels on the device ->
+ * the file libjpeg(-turbo) writes for them at the same quality and subsampling with its defaults -- Annex K tables scaled by
+ * the quality, fixed-point RGB -> YCbCr, h2v1 / h2v2 downsampling, the "islow" forward DCT, the standard Huffman tables, no
+ * restart markers, a JFIF APP0 -- byte for byte.  A batch of images of any sizes and modes takes nine launches; nothing
+ * allocates, nothing synchronises, identical calls give identical bytes.
+ * Limits: sides up to 16384 and at most 2 000 000 blocks in the scan, dummy blocks included (4096 x 4096 in 4:4:4 has 786 432),
+ * so that every bit offset of an image fits 32 bits; beyond that YV3_ELIMIT.  (The encoder's names carry the prefix YV3_JPEGE_,
+ * as the progressive decoder's carry YV3_JPEGP_: the YV3_JPEG_ codes are the baseline decoder's closed set.)
+ * ------------------------------------------------------------------------------------------ */
+enum { YV3_JPEGE_444 = 0, YV3_JPEGE_422 = 1, YV3_JPEGE_420 = 2 };      /* `subsampling` (PIL's numbers); ignored for grey */
+
+/* status[b] of the encode call (0 = out holds the file, out_len[b] bytes) */
+#define YV3_JPEGE_S_INFO    1   /* the device record is no image the encoder takes (sizes, pitch, null pointers)        */
+#define YV3_JPEGE_S_BOUNDS  2   /* the device records need more workspace than the host records the call was sized by   */
+#define YV3_JPEGE_S_SPACE   3   /* out_cap is smaller than the file: nothing is written, out_len[b] is the length needed */
+#define YV3_JPEGE_S_RANGE   4   /* a DC difference above category 11 or an AC value above category 10 (no 8-bit image
+                                      gives one): no code exists for it, nothing is written                                */
+
+typedef struct yv3_jpeg_enc_image {
+    const unsigned char* pixels;      /* device: [height] rows of width * ncomp bytes, `pitch` bytes apart (RGB or grey)        */
+    long long pitch;                  /* >= width * ncomp                                                                      */
+    unsigned char* out;               /* device: the file is written to out[0, out_len)                                        */
+    long long out_cap;                /* bytes at out; no byte at or past out + out_cap is ever written                        */
+    int width, height;
+    int ncomp;                        /* 3: RGB -> YCbCr; 1: grey                                                              */
+    int subsampling;                  /* YV3_JPEGE_*                                                                        */
+    int quality;                      /* 1..100, libjpeg's scale                                                               */
+    int reserved;
+} yv3_jpeg_enc_image;
+
+typedef struct yv3_jpeg_enc_desc {
+    const yv3_jpeg_enc_image* images;       /* device [B]: what the kernels read and check                                     */
+    const yv3_jpeg_enc_image* images_host;  /* host [B]: the same records, for the argument checks, the workspace and the grids */
+    int* out_len;                     /* device [B] out: the file's length (also when status is YV3_JPEGE_S_SPACE)          */
+    int* status;                      /* device [B] out: YV3_JPEGE_S_*                                                      */
+    int B;                            /* 1..65535                                                                              */
+} yv3_jpeg_enc_desc;
+
+/* Host only: the bytes of the file up to and including the SOS segment, in libjpeg's order (SOI, APP0, one DQT per table, SOF0,
+ * DHT DC0 AC0 [DC1 AC1], SOS).  Writes at most cap bytes and returns the header's length (out may be null when cap is 0), or
+ * YV3_EINVAL / YV3_ELIMIT. */
+long long yv3_jpeg_encode_header(int width, int height, int ncomp, int subsampling, int quality, unsigned char* out, long long cap);
+
+/* Host only: a length no file of this size and mode exceeds -- the header, the scan at 11 + 11 bits for every DC and 16 + 10 for
+ * every AC coefficient (the longest codes of the standard tables with the widest values), doubled for stuffing, and EOI.
+ * YV3_EINVAL / YV3_ELIMIT (negative) otherwise. */
+long long yv3_jpeg_encode_bound(int width, int height, int ncomp, int subsampling);
+
+/* Host only: workspace bytes of the encode call for these records; 0 on a bad argument or a record the call refuses. */
+size_t yv3_jpeg_encode_workspace_bytes(const yv3_jpeg_enc_image* images_host, int B);
+
+/* Encodes the batch on `stream`.  ws: device, 256-aligned, its contents need not be cleared and may be reused by the next call.
+ * YV3_EINVAL (null pointer, B outside 1..65535, sizes < 1, ncomp not 1 or 3, unknown subsampling, quality outside 1..100, pitch
+ * too small), YV3_ELIMIT (see above), YV3_EWORKSPACE -- all from the host records, before any launch.  The device records are
+ * checked again by the kernels (status). */
+int yv3_jpeg_encode_batch(const yv3_jpeg_enc_desc* desc, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Box outlines and label tags drawn into a batch of uint8 RGB images in place (csrc/draw.hip), one launch.
+ * Every pixel decides its own colour by walking its image's boxes in order -- outline, then tag, the last writer wins -- so the
+ * result needs no atomics and does not depend on scheduling.  Box j's outline: the pixels of [x1, x2] x [y1, y2] less than
+ * `thickness` pixels from one of the four sides.  Its tag (tag >= 0; mask of mw x mh bits): left = max(min(max(x1, 0), W - mw), 0),
+ * bottom = min(max(y1, mh), H), top = bottom - mh; the pixels of [left, left + mw) x [top, bottom) inside the image take the box
+ * colour, and black where the mask bit is set.  A mask row is ceil(mw / 8) bytes, the leftmost pixel in bit 7.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct yv3_draw_image {
+    unsigned char* pixels;            /* device: [height][width][3] with rows `pitch` bytes apart                              */
+    long long pitch;
+    int width, height;
+    int first_box, num_boxes;         /* this image's boxes: boxes[first_box, first_box + num_boxes), painted in that order    */
+} yv3_draw_image;
+
+typedef struct yv3_draw_box {
+    int x1, y1, x2, y2;
+    int tag;                          /* index into tags, or -1: no tag                                                        */
+    unsigned char rgb[3], reserved;
+} yv3_draw_box;
+
+typedef struct yv3_draw_tag {
+    long long offset;                 /* of the mask's first byte in the atlas                                                 */
+    int width, height;
+} yv3_draw_tag;
+
+/* images, boxes, tags, atlas: device.  max_width / max_height: at least every image's (they size the grid; an image larger than
+ * that is left untouched).  Images without boxes are not written.  The kernel bounds every box, tag and atlas access by num_boxes_total,
+ * num_tags and atlas_bytes.  YV3_EINVAL: null pointer (boxes / tags / atlas may be null when their count is 0), B < 1,
+ * thickness < 1, non-positive sizes. */
+int yv3_draw_boxes(const yv3_draw_image* images, int B, const yv3_draw_box* boxes, int num_boxes_total, const yv3_draw_tag* tags,
+                   int num_tags, const unsigned char* atlas, long long atlas_bytes, int thickness, int max_width, int max_height,
+                   void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The update step (csrc/optim.hip; yolo_v3_amd/optim.py): torch's clip_grad_norm_, torch.optim.SGD and torch.optim.Adam / AdamW
  * over a list of fp32 tensors, a few launches for the whole list.  The list arguments (g, p, buf, n, ...) are HOST arrays of `count` device pointers /
  * element counts; they are read during the call and travel in the kernel arguments, so the caller may reuse them at once.

@@ -147,6 +147,36 @@ class JpegBatchDescProg(ctypes.Structure):
                 ("prog_of_host", c_void_p), ("P", c_int)]
 
 
+JPEGE_444, JPEGE_422, JPEGE_420 = 0, 1, 2
+JPEGE_S_INFO, JPEGE_S_BOUNDS, JPEGE_S_SPACE, JPEGE_S_RANGE = 1, 2, 3, 4
+
+
+class JpegEncImage(ctypes.Structure):
+    """struct yv3_jpeg_enc_image (include/yv3.h)."""
+    _fields_ = [("pixels", c_void_p), ("pitch", c_longlong), ("out", c_void_p), ("out_cap", c_longlong),
+                ("width", c_int), ("height", c_int), ("ncomp", c_int), ("subsampling", c_int), ("quality", c_int), ("reserved", c_int)]
+
+
+class JpegEncDesc(ctypes.Structure):
+    """struct yv3_jpeg_enc_desc (include/yv3.h)."""
+    _fields_ = [("images", c_void_p), ("images_host", c_void_p), ("out_len", c_void_p), ("status", c_void_p), ("B", c_int)]
+
+
+class DrawImage(ctypes.Structure):
+    """struct yv3_draw_image (include/yv3.h)."""
+    _fields_ = [("pixels", c_void_p), ("pitch", c_longlong), ("width", c_int), ("height", c_int), ("first_box", c_int), ("num_boxes", c_int)]
+
+
+class DrawBox(ctypes.Structure):
+    """struct yv3_draw_box (include/yv3.h)."""
+    _fields_ = [("x1", c_int), ("y1", c_int), ("x2", c_int), ("y2", c_int), ("tag", c_int), ("rgb", ctypes.c_ubyte * 3), ("reserved", ctypes.c_ubyte)]
+
+
+class DrawTag(ctypes.Structure):
+    """struct yv3_draw_tag (include/yv3.h)."""
+    _fields_ = [("offset", c_longlong), ("width", c_int), ("height", c_int)]
+
+
 class AffineProgram(ctypes.Structure):
     """struct yv3_affine_program (include/yv3.h)."""
     _fields_ = [("active", c_int), ("reserved", c_int), ("fwd", ctypes.c_double * 6), ("inv", ctypes.c_double * 6)]
@@ -240,6 +270,11 @@ _SIGNATURES = {
     "yv3_jpeg_workspace_bytes_prog": (c_size_t, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int]),
     "yv3_jpeg_decode_batch_prog": (c_int, [ctypes.POINTER(JpegBatchDescProg), c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "yv3_jpeg_launch_count": (c_longlong, []),
+    "yv3_jpeg_encode_header": (c_longlong, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_longlong]),
+    "yv3_jpeg_encode_bound": (c_longlong, [c_int, c_int, c_int, c_int]),
+    "yv3_jpeg_encode_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "yv3_jpeg_encode_batch": (c_int, [ctypes.POINTER(JpegEncDesc), c_void_p, c_size_t, c_void_p]),
+    "yv3_draw_boxes": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_longlong, c_int, c_int, c_int, c_void_p]),
     "yv3_optim_chunk": (c_int, []),
     "yv3_grad_sumsq": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_longlong, c_void_p]),
     "yv3_clip_coef": (c_int, [c_void_p, c_longlong, c_float, c_void_p, c_void_p]),

@@ -146,6 +146,41 @@ class BatchHandler:
         raise NotImplementedError
 
 
+def _wh(img):
+    # CHW tensors as the reference's ToTensor produces (evaluate.py:182); HWC uint8 arrays also accepted
+    s = tuple(img.shape)
+    return (s[2], s[1]) if (len(s) == 3 and s[0] in (1, 3) and s[2] not in (1, 3)) else (s[1], s[0])
+
+
+def correct_batch(sample, predictions, is_letterbox):
+    """The boxes of a batch mapped back to the ORIGINAL images by one ``yv3_correct_boxes`` launch: ``(host, counts, xywh)`` --
+    the predictions padded to CPU ``[B, cap, 7]``, the per-image counts and the corrected CPU ``[B, cap, 4]`` boxes ``x, y, w, h``
+    -- or None when no image of the batch has a detection."""
+    imgs, org_imgs, img_paths = sample['img'], sample['org_img'], sample['img_path']
+    B = len(img_paths)
+    preds = [predictions[i] if (i < len(predictions) and predictions[i] is not None) else torch.Tensor() for i in range(B)]
+    counts = [int(p.shape[0]) if p.numel() else 0 for p in preds]
+    cap = max(counts) if counts else 0
+    if cap == 0:
+        return None
+    if not torch.cuda.is_available():
+        raise _ffi.Yv3Error("no GPU available: this package has no CPU path")
+    img_w, img_h = _wh(imgs[0])
+    # one launch for the whole batch: padded [B, cap, 7] boxes + per-image counts + original sizes
+    host = torch.zeros((B, cap, 7), dtype=torch.float32)
+    for i, p in enumerate(preds):
+        if counts[i]:
+            host[i, :counts[i]] = p.detach().float().cpu()[:, :7]
+    org = torch.tensor([list(_wh(o)) for o in org_imgs], dtype=torch.int32)
+    dev = torch.device("cuda")
+    boxes, cnt, orgd = host.to(dev), torch.tensor(counts, dtype=torch.int32, device=dev), org.to(dev)
+    out = torch.empty((B, cap, 4), dtype=torch.float32, device=dev)
+    _ffi.check(_ffi.lib().yv3_correct_boxes(boxes.data_ptr(), B, cap, 7, cnt.data_ptr(), orgd.data_ptr(), int(img_w), int(img_h),
+                                            int(bool(is_letterbox)), 0, out.data_ptr(), _ffi.stream_ptr()),
+               "yv3_correct_boxes")
+    return host, counts, out.cpu()
+
+
 class JsonPredictionWriter(BatchHandler):
     """reference evaluate.py:164-195"""
 
@@ -163,37 +198,15 @@ class JsonPredictionWriter(BatchHandler):
         self.file.write(']')
         self.file.close()
 
-    @staticmethod
-    def _wh(img):
-        # CHW tensors as the reference's ToTensor produces (evaluate.py:182); HWC uint8 arrays also accepted
-        s = tuple(img.shape)
-        return (s[2], s[1]) if (len(s) == 3 and s[0] in (1, 3) and s[2] not in (1, 3)) else (s[1], s[0])
+    _wh = staticmethod(_wh)
 
     def process_batch(self, sample, predictions):
-        imgs, org_imgs, img_paths = sample['img'], sample['org_img'], sample['img_path']
-        B = len(img_paths)
-        preds = [predictions[i] if (i < len(predictions) and predictions[i] is not None) else torch.Tensor() for i in range(B)]
-        counts = [int(p.shape[0]) if p.numel() else 0 for p in preds]
-        cap = max(counts) if counts else 0
-        if cap == 0:
+        img_paths = sample['img_path']
+        corrected = correct_batch(sample, predictions, self.is_letterbox)
+        if corrected is None:
             return
-        if not torch.cuda.is_available():
-            raise _ffi.Yv3Error("no GPU available: this package has no CPU path")
-        img_w, img_h = self._wh(imgs[0])
-        # one launch for the whole batch: padded [B, cap, 7] boxes + per-image counts + original sizes
-        host = torch.zeros((B, cap, 7), dtype=torch.float32)
-        for i, p in enumerate(preds):
-            if counts[i]:
-                host[i, :counts[i]] = p.detach().float().cpu()[:, :7]
-        org = torch.tensor([list(self._wh(o)) for o in org_imgs], dtype=torch.int32)
-        dev = torch.device("cuda")
-        boxes, cnt, orgd = host.to(dev), torch.tensor(counts, dtype=torch.int32, device=dev), org.to(dev)
-        out = torch.empty((B, cap, 4), dtype=torch.float32, device=dev)
-        _ffi.check(_ffi.lib().yv3_correct_boxes(boxes.data_ptr(), B, cap, 7, cnt.data_ptr(), orgd.data_ptr(), int(img_w), int(img_h),
-                                                int(bool(self.is_letterbox)), 0, out.data_ptr(), _ffi.stream_ptr()),
-                   "yv3_correct_boxes")
-        xywh = out.cpu()
-        for i in range(B):
+        host, counts, xywh = corrected
+        for i in range(len(img_paths)):
             image_id = get_image_id_from_path(img_paths[i])
             for j in range(counts[i]):
                 res = create_results_entry(image_id, int(host[i, j, 6].item()), xywh[i, j].tolist(), host[i, j, 5].item())
@@ -242,6 +255,34 @@ def read_image_rgb(path):
         return np.asarray(im.convert("RGB"), dtype=np.uint8).copy()
 
 
+def image_batches(target_txt, bs, dim, is_letterbox=False, decode="pil", entropy="serial", progressive=False):
+    """The samples `generate_results_file` and `annotate_images` feed to the network, ``bs`` images at a time:
+    ``{'img': [B,3,h,w] GPU tensor, 'org_img': the original images (HWC uint8: arrays, or GPU tensors with decode="gpu"),
+    'img_path': [...]}``.  ``target_txt``: the reference's text file with one image path per line, or a list of paths or of
+    ``(path, uint8 RGB [H,W,3] array)`` pairs."""
+    from .utils import letterbox_batch
+    if isinstance(target_txt, str):
+        with open(target_txt, 'r') as f:
+            items = [line.strip() for line in f.readlines() if line.strip()]
+    else:
+        items = list(target_txt)
+
+    def batches():                                                  # (the list is read before the first batch is asked for)
+        for i in range(0, len(items), bs):
+            chunk = items[i:i + bs]
+            paths = [c if isinstance(c, str) else c[0] for c in chunk]
+            if decode == "gpu":
+                from . import jpeg
+                files = iter(jpeg.decode_batch([c for c in chunk if isinstance(c, str)], entropy=entropy, progressive=progressive))
+                imgs = [next(files) if isinstance(c, str) else c[1] for c in chunk]
+            else:
+                imgs = [read_image_rgb(c) if isinstance(c, str) else c[1] for c in chunk]
+            x, _ = letterbox_batch(imgs, dim, variant="eval" if is_letterbox else "scale")
+            yield {"img": x, "org_img": imgs, "img_path": paths}    # (the writers need the ORIGINAL images: HWC)
+
+    return batches()
+
+
 def generate_results_file(net, target_txt, classes_names, out, bs, dim, is_letterbox=False, decode="pil", entropy="serial",
                           progressive=False):
     """reference evaluate.py:208-219: the COCO-results file of a list of images -- ``target_txt`` is the reference's text file with one
@@ -254,31 +295,71 @@ def generate_results_file(net, target_txt, classes_names, out, bs, dim, is_lette
     pixels (files the GPU decoder does not take still go through `read_image_rgb`), so the same file.  ``entropy`` is passed on to
     it (``"serial"`` or ``"parallel"``; it changes no pixel), and so is ``progressive`` (True: accepted progressive files are
     decoded on the GPU too)."""
-    from .utils import letterbox_batch
     if decode not in ("pil", "gpu"):
         raise ValueError("decode must be 'pil' or 'gpu'")
     if entropy not in ("serial", "parallel"):
         raise ValueError("entropy must be 'serial' or 'parallel'")
-    if isinstance(target_txt, str):
-        with open(target_txt, 'r') as f:
-            items = [line.strip() for line in f.readlines() if line.strip()]
-    else:
-        items = list(target_txt)
     numclass = len(classes_names)
-
-    def batches():
-        for i in range(0, len(items), bs):
-            chunk = items[i:i + bs]
-            paths = [c if isinstance(c, str) else c[0] for c in chunk]
-            if decode == "gpu":
-                from . import jpeg
-                files = iter(jpeg.decode_batch([c for c in chunk if isinstance(c, str)], entropy=entropy, progressive=progressive))
-                imgs = [next(files) if isinstance(c, str) else c[1] for c in chunk]
-            else:
-                imgs = [read_image_rgb(c) if isinstance(c, str) else c[1] for c in chunk]
-            x, _ = letterbox_batch(imgs, dim, variant="eval" if is_letterbox else "scale")
-            yield {"img": x, "org_img": imgs, "img_path": paths}       # (the writer needs only the ORIGINAL sizes: HWC arrays)
+    batches = image_batches(target_txt, bs, dim, is_letterbox, decode, entropy, progressive)
 
     with open_json_pred_writer(out, classes_names, is_letterbox) as pred_writer:
-        predict_and_process(batches(), net, num_classes=numclass, batch_handler=pred_writer)
+        predict_and_process(batches, net, num_classes=numclass, batch_handler=pred_writer)
         return pred_writer.entries
+
+
+class JpegAnnotationWriter(BatchHandler):
+    """Annotated frames out (what the reference shows with ``test.py:predict`` / ``show_detections`` and ``draw.py``): per batch the
+    boxes are corrected as `JsonPredictionWriter` corrects them, drawn on the ORIGINAL-size images with their class names
+    (`draw.draw_boxes`: box j in colour ``palette[class]``, outline then label tag, in detection order) and the images are encoded
+    on the GPU (`jpeg.encode_batch`) and written to ``out_dir/<image stem>.jpg``.  Only the box integers go to the device and only
+    the compressed bytes come back; original images that are GPU tensors (``decode="gpu"``) never leave it, host arrays are
+    uploaded.  An image without detections is written without boxes.  ``written``: the paths written so far; ``boxes``: per
+    written file its ``(rectangles, classes)``, int32 ``[n, 4]`` / int ``[n]``, as drawn."""
+
+    def __init__(self, out_dir, classes_names, is_letterbox=False, quality=75, subsampling="4:2:0", thickness=2):
+        from . import draw
+        self.out_dir, self.classes_names, self.is_letterbox = out_dir, list(classes_names), is_letterbox
+        self.quality, self.subsampling, self.thickness = quality, subsampling, thickness
+        self.atlas = draw.LabelAtlas(self.classes_names)
+        self.palette = draw.palette(len(self.classes_names))
+        self.written, self.boxes = [], []
+
+    def process_batch(self, sample, predictions):
+        from . import draw, jpeg
+        org_imgs, img_paths = sample['org_img'], sample['img_path']
+        B = len(img_paths)
+        if not torch.cuda.is_available():
+            raise _ffi.Yv3Error("no GPU available: this package has no CPU path")
+        corrected = correct_batch(sample, predictions, self.is_letterbox)
+        rects, classes = [np.zeros((0, 4), np.int32)] * B, [np.zeros(0, np.int64)] * B
+        if corrected is not None:
+            host, counts, xywh = corrected
+            rects = [draw.rectangles(xywh[i, :counts[i]].numpy()) for i in range(B)]
+            classes = [host[i, :counts[i], 6].numpy().astype(np.int64) for i in range(B)]
+        # the drawing is in place: on a copy, so that the caller's originals (the decoder's buffer, with decode="gpu") stay as they were
+        frames = [o.clone() if isinstance(o, torch.Tensor) and o.is_cuda else torch.as_tensor(np.ascontiguousarray(o)).cuda() for o in org_imgs]
+        draw.draw_boxes(frames, rects, [self.palette[c] for c in classes], classes, self.atlas, thickness=self.thickness)
+        files = jpeg.encode_batch(frames, quality=self.quality, subsampling=self.subsampling)
+        for path, data, r, c in zip(img_paths, files, rects, classes):
+            out = osp.join(self.out_dir, osp.splitext(osp.basename(path))[0] + ".jpg")
+            with open(out, "wb") as f:
+                f.write(data)
+            self.written.append(out)
+            self.boxes.append((r, c))
+
+
+def annotate_images(net, target_txt, classes_names, out_dir, bs, dim, is_letterbox=False, decode="pil", obj_conf_thr=0.5, nms_thr=0.4,
+                    quality=75):
+    """Detect, draw and encode the images listed in ``target_txt`` (as `generate_results_file` takes it), ``bs`` at a time, and
+    write ``out_dir/<image stem>.jpg`` for each: the original image with its boxes and class names on it.  ``dim`` = (w, h) of the
+    network input; ``obj_conf_thr`` / ``nms_thr`` are the detection thresholds.  ``decode="gpu"``: the files are decoded by
+    `jpeg.decode_batch` and the originals stay on the device from decode to encode (files that decoder hands to PIL are uploaded).
+    Returns the `JpegAnnotationWriter`, whose ``written`` lists the files."""
+    if decode not in ("pil", "gpu"):
+        raise ValueError("decode must be 'pil' or 'gpu'")
+    import os
+    os.makedirs(out_dir, exist_ok=True)
+    writer = JpegAnnotationWriter(out_dir, classes_names, is_letterbox, quality=quality)
+    predict_and_process(image_batches(target_txt, bs, dim, is_letterbox, decode), net, num_classes=len(classes_names), batch_handler=writer,
+                        obj_conf_thr=obj_conf_thr, nms_thr=nms_thr)
+    return writer

@@ -8,6 +8,9 @@ whose EXIF orientation is not 1, a file whose entropy-coded data the device repo
 the range in which every libjpeg computes the same bytes (``JPEG_S_RANGE``) and a file that ends without its EOI marker are
 decoded by ``read_image_rgb`` itself -- same pixels, same exceptions.  Nothing here is a default anywhere:
 ``TrainBatches(decode="gpu")`` and ``generate_results_file(decode="gpu")`` opt in.
+
+``encode_batch(images)`` is the way out: uint8 RGB or grey images on the GPU become baseline JPEG files, byte for byte the files
+PIL writes for the same pixels, quality and subsampling (``csrc/jpeg_enc.hip``, nine launches per batch).
 """
 import ctypes
 import io
@@ -325,6 +328,163 @@ def submit(sources, device=None, stream=None, dst=None, entropy="serial", progre
         event = torch.cuda.Event()                          # after this job's upload, kernels and status copy, and nothing else
         event.record(stream)
     return Job(items, views, reasons, status_host, event, stream, keep, parallel)
+
+
+# ---- encode (csrc/jpeg_enc.hip) ------------------------------------------------------------------------
+SUBSAMPLING = {"4:4:4": _ffi.JPEGE_444, "4:2:2": _ffi.JPEGE_422, "4:2:0": _ffi.JPEGE_420}
+_ENC_BYTES = ctypes.sizeof(_ffi.JpegEncImage)
+
+
+def encode_bound(width, height, ncomp, subsampling="4:2:0"):
+    """``yv3_jpeg_encode_bound``: a length no file of this size and mode exceeds (raises beyond the encoder's size limit)."""
+    n = _ffi.lib().yv3_jpeg_encode_bound(int(width), int(height), int(ncomp), SUBSAMPLING[subsampling])
+    if n < 0:
+        _ffi.check(int(n), "yv3_jpeg_encode_bound")
+    return int(n)
+
+
+def _encode_input(image, dev):
+    """A uint8 GPU tensor ``[H,W,3]`` or ``[H,W]`` whose pixels are contiguous inside a row (rows may be pitched)."""
+    if isinstance(image, torch.Tensor):
+        t = image
+    else:
+        a = np.asarray(image)
+        if a.dtype != np.uint8:
+            raise TypeError("encode: images must be uint8, got %s" % a.dtype)
+        t = torch.from_numpy(np.ascontiguousarray(a))
+    if t.dtype != torch.uint8:
+        raise TypeError("encode: images must be uint8, got %s" % t.dtype)
+    if not (t.dim() == 2 or (t.dim() == 3 and t.shape[2] == 3)) or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError("encode: images must be [H, W, 3] or [H, W] with H, W >= 1, got %s" % (tuple(t.shape),))
+    if not t.is_cuda:
+        counters["uploads"] += 1
+        counters["upload_bytes"] += t.numel()
+        t = t.to(dev)
+    elif t.device != dev:
+        raise _ffi.Yv3Error("encode: an image lives on %s, the call runs on %s" % (t.device, dev))
+    rows_ok = t.stride(1) == 1 if t.dim() == 2 else (t.stride(2) == 1 and t.stride(1) == 3)
+    if not rows_ok or (t.shape[0] > 1 and t.stride(0) < t.shape[1] * (1 if t.dim() == 2 else 3)):
+        t = t.contiguous()
+    return t
+
+
+def encode_launch(tensors, qualities, subsamplings, out, offsets, capacities, ws=None, stream=None):
+    """Enqueue ``yv3_jpeg_encode_batch`` for prepared GPU tensors (see `submit_encode`): image i's file goes to the uint8 1-D GPU
+    tensor ``out`` at ``offsets[i]``, at most ``capacities[i]`` bytes.  ``ws``: a uint8 GPU tensor to use as the workspace when it
+    is large enough (its contents do not matter), else one is allocated.  Returns ``(lengths, statuses, keep)``: two int32 GPU
+    tensors ``[B]`` and the tensors that must stay alive until the stream has run the call.  Nothing here waits for the device."""
+    lib = _ffi.lib()
+    dev = out.device
+    stream = stream if stream is not None else torch.cuda.current_stream(dev)
+    B = len(tensors)
+    if out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous():
+        raise _ffi.Yv3Error("encode: out must be a contiguous 1-D uint8 tensor")
+    if not (len(qualities) == len(subsamplings) == len(offsets) == len(capacities) == B) or B < 1:
+        raise ValueError("encode: one quality, subsampling, offset and capacity per image")
+    recs = (_ffi.JpegEncImage * B)()
+    for i, t in enumerate(tensors):
+        ncomp = 1 if t.dim() == 2 else 3
+        if int(offsets[i]) < 0 or int(capacities[i]) < 0 or int(offsets[i]) + int(capacities[i]) > out.numel():
+            raise _ffi.Yv3Error("encode: image %d's output range lies outside out" % i)
+        recs[i] = _ffi.JpegEncImage(pixels=t.data_ptr(), pitch=t.stride(0) if t.shape[0] > 1 else t.shape[1] * ncomp,
+                                    out=out.data_ptr() + int(offsets[i]), out_cap=int(capacities[i]), width=t.shape[1], height=t.shape[0],
+                                    ncomp=ncomp, subsampling=int(subsamplings[i]), quality=int(qualities[i]))
+    need = lib.yv3_jpeg_encode_workspace_bytes(recs, B)
+    with torch.cuda.device(dev), torch.cuda.stream(stream):
+        o_len = _round_up(B * _ENC_BYTES)
+        staging = torch.empty(o_len, dtype=torch.uint8, pin_memory=True)
+        staging.numpy()[:B * _ENC_BYTES] = np.frombuffer(recs, dtype=np.uint8, count=B * _ENC_BYTES)
+        meta = torch.empty(o_len + 8 * B, dtype=torch.uint8, device=dev)           # records | lengths [B] | statuses [B]
+        meta[:o_len].copy_(staging, non_blocking=True)
+        if ws is None or ws.numel() < need or ws.device != dev or ws.data_ptr() % _ALIGN:
+            ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        base = meta.data_ptr()
+        desc = _ffi.JpegEncDesc(images=base, images_host=ctypes.addressof(recs), out_len=base + o_len, status=base + o_len + 4 * B, B=B)
+        _ffi.check(lib.yv3_jpeg_encode_batch(ctypes.byref(desc), ws.data_ptr(), ws.numel(), stream.cuda_stream), "yv3_jpeg_encode_batch")
+        both = meta[o_len:].view(torch.int32)
+    return both[:B], both[B:], [meta, ws, staging, out] + list(tensors)
+
+
+class EncodeJob:
+    """An encode in flight: the files stay on the device until `finish`, which waits for this job's event, reads the lengths and
+    statuses once, and copies the files' bytes -- packed back to back on the device first -- in one transfer."""
+
+    def __init__(self, out, offsets, both_host, event, stream, keep):
+        self._out, self._offsets, self._both_host, self._event, self._stream, self._keep = out, offsets, both_host, event, stream, keep
+        self._result = None
+
+    def finish(self):
+        if self._result is None:
+            self._event.synchronize()
+            counters["status_reads"] += 1
+            B = len(self._offsets)
+            both = self._both_host.numpy()
+            lengths, statuses = [int(v) for v in both[:B]], [int(v) for v in both[B:]]
+            for i, st in enumerate(statuses):
+                if st:
+                    err = _ffi.Yv3Error("encode: image %d ended with device status %d" % (i, st))
+                    err.code = st
+                    raise err
+            with torch.cuda.stream(self._stream):
+                packed = torch.cat([self._out[o:o + n] for o, n in zip(self._offsets, lengths)]).cpu()
+            data, pos, files = packed.numpy().tobytes(), 0, []
+            for n in lengths:
+                files.append(data[pos:pos + n])
+                pos += n
+            self._result, self._keep, self._out = files, None, None
+        return list(self._result)
+
+
+def submit_encode(images, quality=75, subsampling="4:2:0", device=None, stream=None):
+    """Enqueue the baseline JPEG encode of ``images`` on ``stream`` (default: the current one) and return the `EncodeJob`.
+    ``images``: uint8 ``[H,W,3]`` (RGB) or ``[H,W]`` (grey), GPU tensors or host arrays (which are uploaded); sizes and kinds may
+    differ inside the batch; rows may be pitched (a row slice of a larger tensor is read in place).  ``quality`` 1..100 and
+    ``subsampling`` (``"4:4:4"``, ``"4:2:2"``, ``"4:2:0"``; ignored for grey) are one value or one per image.  Every file is the
+    one ``PIL.Image.save(..., "JPEG", quality=, subsampling=)`` writes for the same pixels, byte for byte."""
+    images = list(images)
+    B = len(images)
+    qualities = list(quality) if isinstance(quality, (list, tuple)) else [quality] * max(B, 1)
+    subs = list(subsampling) if isinstance(subsampling, (list, tuple)) else [subsampling] * max(B, 1)
+    if len(qualities) != max(B, 1) or len(subs) != max(B, 1):
+        raise ValueError("encode: one quality and one subsampling, or one per image")
+    for q in qualities:
+        if not isinstance(q, (int, np.integer)) or isinstance(q, bool) or not 1 <= q <= 100:
+            raise ValueError("encode: quality must be an integer in 1..100, got %r" % (q,))
+    for s in subs:
+        if s not in SUBSAMPLING:
+            raise ValueError("encode: subsampling must be one of %s, got %r" % (sorted(SUBSAMPLING), s))
+    if not torch.cuda.is_available():
+        raise _ffi.Yv3Error("no GPU available: this package has no CPU path")
+    dev = torch.device(device if device is not None else "cuda")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    stream = stream if stream is not None else torch.cuda.current_stream(dev)
+    if B == 0:
+        job = EncodeJob(None, [], None, None, stream, None)
+        job._result = []
+        return job
+    with torch.cuda.device(dev), torch.cuda.stream(stream):
+        tensors = [_encode_input(im, dev) for im in images]
+        offsets, caps, pos = [], [], 0
+        for t, s in zip(tensors, subs):
+            cap = encode_bound(t.shape[1], t.shape[0], 1 if t.dim() == 2 else 3, s)
+            offsets.append(pos)
+            caps.append(cap)
+            pos = _round_up(pos + cap)
+        out = torch.empty(pos, dtype=torch.uint8, device=dev)
+        lengths, statuses, keep = encode_launch(tensors, qualities, [SUBSAMPLING[s] for s in subs], out, offsets, caps, stream=stream)
+        both_host = torch.empty(2 * B, dtype=torch.int32, pin_memory=True)
+        both_host[:B].copy_(lengths, non_blocking=True)
+        both_host[B:].copy_(statuses, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record(stream)
+    return EncodeJob(out, offsets, both_host, event, stream, keep)
+
+
+def encode_batch(images, quality=75, subsampling="4:2:0", device=None):
+    """``list[bytes]``: the baseline JPEG file of every image, byte for byte the file PIL writes for the same pixels and settings
+    (see `submit_encode`).  One read of the lengths and one transfer of the bytes per call."""
+    return submit_encode(images, quality=quality, subsampling=subsampling, device=device).finish()
 
 
 def decode_batch(sources, device=None, errors="raise", entropy="serial", progressive=False):
