@@ -92,6 +92,7 @@ def main():
         print(json.dumps({"bs": bs, "dim": dim, "src": "640x480", "kernels_ms": round(k, 4), "end_to_end_ms": round(e, 4),
                           "upload_bytes": src, "kernel_bytes": moved, "kernel_GBps": round(moved / k / 1e6, 1),
                           "kernels_min_ms": round(min(times[c]["kernels"]), 4), "end_to_end_min_ms": round(min(times[c]["end_to_end"]), 4),
+                          "end_to_end_max_ms": round(max(times[c]["end_to_end"]), 4),
                           "rounds": a.rounds}))
 
 

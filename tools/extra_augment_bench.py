@@ -134,7 +134,8 @@ def main():
         steps["sampled"] = steps["end to end"] = sum(max(len(p), 1) for p in state[bs][1]) / bs
         for n in names + ["end to end", "augment"]:
             ms = float(np.median(times[(bs, n)]))
-            line = {"bs": bs, "src": "640x480", "row": n, "ms": round(ms, 4), "min_ms": round(min(times[(bs, n)]), 4), "rounds": a.rounds}
+            line = {"bs": bs, "src": "640x480", "row": n, "ms": round(ms, 4), "min_ms": round(min(times[(bs, n)]), 4),
+                    "max_ms": round(max(times[(bs, n)]), 4), "rounds": a.rounds}
             if n in steps:
                 moved = int(2 * batch * steps[n])
                 line.update(steps_per_image=round(steps[n], 3), bytes_moved=moved, GBps=round(moved / ms / 1e6, 1))

@@ -11,7 +11,7 @@ their label files in a temporary directory, bs 16, dim 416, whole epochs ending 
              start-up to --step-ms of device time and only enqueued (as a training loop enqueues its step), so that the setting's
              ms per batch minus --step-ms is what the loader adds to a step it can overlap with
 Rounds are interleaved (one epoch of every setting per round); per setting the median, minimum and maximum of the per-epoch
-ms per batch, the batches per second of the median, the host's share (time inside ``next()``, before the synchronise) and the
+ms per batch, the batches per second of the median, the host's share (time inside ``next()``, before the synchronise; median, minimum and maximum too) and the
 bytes uploaded per batch as the code counts them (``augment.counters``).  One JSON line per setting.
 
     python tools/loader_bench.py [--rounds 9] [--warmup 2] [--workers 8] [--entropy serial|parallel|both]
@@ -134,13 +134,14 @@ def main():
                 if r >= a.warmup:
                     samples[k].append(s)
         for k, v in samples.items():
-            wall = sorted(s[0] for s in v)
+            wall, host = sorted(s[0] for s in v), sorted(s[1] for s in v)
             med = float(np.median(wall))
             print(json.dumps({"setting": k, "bs": BS, "dim": DIM, "src": "%dx%d jpeg q90" % (W, H), "images": N_IMAGES,
                               "workers": loaders[k].workers, "cache_bytes": loaders[k].cache_bytes, "decode": loaders[k].decode,
                               "entropy": loaders[k].entropy if loaders[k].decode == "gpu" else None,
                               "ms_per_batch": round(med, 3), "min_ms": round(wall[0], 3), "max_ms": round(wall[-1], 3),
-                              "batches_per_s": round(1e3 / med, 1), "host_ms_per_batch": round(float(np.median([s[1] for s in v])), 3),
+                              "batches_per_s": round(1e3 / med, 1), "host_ms_per_batch": round(float(np.median(host)), 3),
+                              "host_min_ms": round(host[0], 3), "host_max_ms": round(host[-1], 3),
                               "upload_bytes_per_batch": int(np.median([s[2] for s in v])), "rounds": a.rounds,
                               "step_ms": round(step_ms, 3) if k in steps else None}))
 

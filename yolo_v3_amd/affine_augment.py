@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _ffi
+from ._staging import as_images, pad_labels, stage_batch
 
 STREAM = 0x41666669           # "Affi": the second word of the draws' seed, apart from sample_params' and sample_extra's streams
 
@@ -124,99 +125,25 @@ def affine_augment_batch(images, labels, programs):
     ``images``: list of uint8 RGB ``[H,W,3]`` numpy arrays or tensors (CPU or GPU), any sizes.  ``labels``: what ``augment_batch``
     takes (a list of ``[n_i,5]`` arrays, a padded ``[B,T,5]`` tensor on either side, or None).  ``programs``: one per image
     (``sample_affine``), checked here (``check_affine_programs``).  Programs, offsets, shapes, host labels and host images go up in
-    one copy through ``augment_batch``'s pinned staging buffers; GPU images are copied on the device -- unless all of them are
-    contiguous views into one allocation (``TrainBatches``' arena): then they are read where they are.  Two launches, ordered on
-    the current stream; neither the sources nor a label tensor passed in is written."""
-    from . import augment as A
-    if not torch.cuda.is_available():
-        raise _ffi.Yv3Error("no GPU available: this package has no CPU path")
-    imgs = [A._as_image(im) for im in images]
+    one copy; GPU images are copied on the device or, as views into one allocation (``TrainBatches``' arena), read where they are
+    (``_staging.stage_batch``).  Two launches, ordered on the current stream; neither the sources nor a label tensor passed in
+    is written."""
+    imgs, shapes = as_images(images)
     B = len(imgs)
-    if B == 0:
-        raise ValueError("empty batch")
-    shapes = [(int(t.shape[0]), int(t.shape[1])) for t in imgs]
     programs = list(programs)
     check_affine_programs(programs, shapes)
-    packed = pack_programs(programs)
+    dev_labels, host_labels, T = pad_labels(labels, B)
 
-    dev_labels, host_labels, T = None, None, 0
-    if isinstance(labels, torch.Tensor):
-        if labels.dim() != 3 or labels.shape[0] != B or labels.shape[2] != 5:
-            raise ValueError("padded labels must be [B,T,5]")
-        T = int(labels.shape[1])
-        if labels.is_cuda:
-            dev_labels = labels.to(torch.float64).contiguous()
-        else:
-            host_labels = labels.to(torch.float64).numpy()
-    elif labels is not None:
-        if len(labels) != B:
-            raise ValueError("one label array per image")
-        rows = [np.asarray(l, dtype=np.float64).reshape(-1, 5) for l in labels]
-        T = max(r.shape[0] for r in rows)
-        host_labels = np.zeros((B, T, 5), dtype=np.float64)
-        for b, r in enumerate(rows):
-            host_labels[b, :r.shape[0]] = r
-
-    offsets, pos = [], 0
-    for H, W in shapes:
-        offsets.append(pos)
-        pos = A._round_up(pos + H * W * 3)
-    out_bytes = pos
+    st = stage_batch(imgs, shapes, pack_programs(programs), host_labels)
     lib = _ffi.lib()
-    dev_index = torch.cuda.current_device()
-    gather = (all(t.is_cuda and t.device.index == dev_index and t.is_contiguous() for t in imgs)
-              and len({t.untyped_storage().data_ptr() for t in imgs}) == 1)
-
-    # staging layout: programs | out offsets | hw | labels | [gather: source offsets] or [images (each image 256-aligned)]
-    o_prog = 0
-    o_off = A._round_up(o_prog + packed.nbytes)
-    o_hw = A._round_up(o_off + B * 8)
-    o_lab = A._round_up(o_hw + B * 8)
-    o_img = A._round_up(o_lab + (host_labels.nbytes if host_labels is not None else 0))
-    host_img_bytes = sum(H * W * 3 for (H, W), t in zip(shapes, imgs) if not t.is_cuda)
-    if gather:
-        total = upload = o_img + B * 8
-    else:
-        total = o_img + out_bytes
-        upload = total if host_img_bytes else o_img
-
-    staging = A._staging.setdefault(dev_index, A._Staging())
-    slot, buf = staging.take(upload)
-    host = buf.numpy()
-    host[o_prog:o_prog + packed.nbytes] = packed.view(np.uint8).reshape(-1)
-    host[o_off:o_off + B * 8].view(np.int64)[:] = offsets
-    host[o_hw:o_hw + B * 8].view(np.int32)[:] = np.asarray(shapes, dtype=np.int32).reshape(-1)
-    if host_labels is not None and host_labels.size:
-        host[o_lab:o_lab + host_labels.nbytes].view(np.float64)[:] = host_labels.reshape(-1)
-    if gather:
-        arena = imgs[0].untyped_storage()
-        host[o_img:o_img + B * 8].view(np.int64)[:] = [t.data_ptr() - arena.data_ptr() for t in imgs]
-    for off, t in zip(offsets, imgs):
-        if not t.is_cuda:
-            n = t.numel()
-            host[o_img + off:o_img + off + n] = t.reshape(-1).numpy()
-    dev = torch.empty(total, dtype=torch.uint8, device="cuda")
-    dev[:upload].copy_(buf[:upload], non_blocking=True)
-    staging.release(slot)
-    A.counters["upload_bytes"] += upload
-    if not gather:
-        for off, t in zip(offsets, imgs):
-            if t.is_cuda:
-                dev[o_img + off:o_img + off + t.numel()].copy_(t.reshape(-1))
-
-    base = dev.data_ptr()
-    out = torch.empty(out_bytes, dtype=torch.uint8, device="cuda")
+    out = torch.empty(st.span, dtype=torch.uint8, device="cuda")
     labels_out = torch.empty((B, T, 5), dtype=torch.float64, device="cuda")
     status = torch.empty((2, B), dtype=torch.int32, device="cuda")
     s = _ffi.stream_ptr()
-    if gather:
-        src, src_bytes, src_off = arena.data_ptr(), arena.nbytes(), base + o_img
-    else:
-        src, src_bytes, src_off = base + o_img, out_bytes, base + o_off
-    _ffi.check(lib.yv3_affine_augment(src, src_bytes, src_off, base + o_hw, base + o_prog, B, out.data_ptr(), out_bytes,
-                                      base + o_off, status.data_ptr(), s), "yv3_affine_augment")
+    _ffi.check(lib.yv3_affine_augment(st.src, st.src_bytes, st.src_offsets, st.hw, st.records, B, out.data_ptr(), st.span,
+                                      st.out_offsets, status.data_ptr(), s), "yv3_affine_augment")
     if T:
-        lab_ptr = dev_labels.data_ptr() if dev_labels is not None else base + o_lab
-        _ffi.check(lib.yv3_affine_labels(lab_ptr, B, T, base + o_hw, base + o_prog, labels_out.data_ptr(),
+        lab_ptr = dev_labels.data_ptr() if dev_labels is not None else st.labels
+        _ffi.check(lib.yv3_affine_labels(lab_ptr, B, T, st.hw, st.records, labels_out.data_ptr(),
                                          status.data_ptr() + 4 * B, s), "yv3_affine_labels")
-    return [out[off:off + H * W * 3].view(H, W, 3) for off, (H, W) in zip(offsets, shapes)], labels_out
+    return [out[off:off + H * W * 3].view(H, W, 3) for off, (H, W) in zip(st.offsets, shapes)], labels_out

@@ -30,12 +30,12 @@ import numpy as np
 import torch
 
 from . import _ffi
+from ._staging import as_images, counters, pad_labels, round_up, stage_batch      # counters: read by tools and tests under this name
 from .extra_augment import sample_extra, check_programs, extra_augment_batch      # noqa: F401 (part of this module's interface)
 from .affine_augment import sample_affine, check_affine_programs, affine_augment_batch      # noqa: F401 (likewise)
 
 MAX_LABELS = 90
 N_PARAMS = 8                 # dhue, dsat, dexp, top, right, bottom, left, flip
-_ALIGN = 256
 
 
 def _rand_scale(rng, s):
@@ -124,45 +124,6 @@ def check_params(params, shapes, dim):
             fail(_ffi.ESHAPE, i, "the letterboxed %d x %d image has no pixel on the canvas" % (H1, W1))
 
 
-class _Staging:
-    """Pinned host buffers for augment_batch's one upload, used in turn.  A buffer is rewritten only after the copy that last read
-    it has completed: waiting for that copy's event is the path's only host synchronisation."""
-
-    def __init__(self, n=2):
-        self.bufs, self.events, self.i = [None] * n, [None] * n, 0
-
-    def take(self, nbytes):
-        i = self.i
-        self.i = (i + 1) % len(self.bufs)
-        if self.events[i] is not None:
-            self.events[i].synchronize()
-            self.events[i] = None
-        if self.bufs[i] is None or self.bufs[i].numel() < nbytes:
-            self.bufs[i] = None
-            self.bufs[i] = torch.empty(max(1 << 20, 1 << (nbytes - 1).bit_length()), dtype=torch.uint8, pin_memory=True)
-        return i, self.bufs[i]
-
-    def release(self, i):
-        ev = torch.cuda.Event()
-        ev.record()
-        self.events[i] = ev
-
-
-_staging = {}
-counters = {"batches": 0, "upload_bytes": 0}     # augment_batch calls and the bytes of their host-to-device uploads, for measurements
-
-
-def _round_up(n, a=_ALIGN):
-    return (n + a - 1) // a * a
-
-
-def _as_image(img):
-    t = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
-    if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise _ffi.Yv3Error("images must be uint8 [H,W,3] RGB")
-    return t
-
-
 def augment_batch(images, labels, dim, params, max_labels=MAX_LABELS):
     """The training transform of a batch: ``(x [B,3,h,w] fp32, target [B,max_labels,5] fp32)``, both on the current GPU.
 
@@ -170,115 +131,46 @@ def augment_batch(images, labels, dim, params, max_labels=MAX_LABELS):
     arrays (cls, cx, cy, w, h relative to the source; n_i may be 0), or a zero-padded ``[B,T,5]`` tensor, or None.  ``dim`` =
     (w, h).  ``params``: ``[B,8]`` float64 on the host (``sample_params``), checked here (``check_params``).
 
-    Host inputs (params, shapes, offsets, labels, host images) are packed into one pinned buffer and uploaded in one copy; GPU
-    images are copied on the device -- unless all of them are contiguous views into one allocation on this GPU: then no pixel is
-    copied, their offsets in that allocation are uploaded instead and ``yv3_augment_images_from`` reads them in place (the same
-    bits either way).  Three kernels follow: colour, crop / pad / flip / letterbox / ToTensor, labels.  Everything
-    is ordered on the current stream; the host waits only before a pinned buffer is reused (two are kept)."""
+    Host inputs (params, shapes, offsets, labels, host images) go up in one copy and GPU images are copied on the device or, as
+    views into one allocation, read in place by ``yv3_augment_images_from`` -- the same bits either way (``_staging.stage_batch``).
+    Three kernels follow: colour, crop / pad / flip / letterbox / ToTensor, labels.  Everything is ordered on the current
+    stream; the host waits only before a pinned buffer is reused (two are kept)."""
     if not torch.cuda.is_available():
         raise _ffi.Yv3Error("no GPU available: this package has no CPU path")
     out_w, out_h = int(dim[0]), int(dim[1])
     if out_w <= 0 or out_h <= 0 or max_labels <= 0:
         raise ValueError("dim and max_labels must be positive")
-    imgs = [_as_image(im) for im in images]
+    imgs, shapes = as_images(images)
     B = len(imgs)
-    if B == 0:
-        raise ValueError("empty batch")
-    shapes = [(int(t.shape[0]), int(t.shape[1])) for t in imgs]
     if isinstance(params, torch.Tensor):
         if params.is_cuda:
             raise _ffi.Yv3Error("params must be on the host (they are checked there before the launch)")
         params = params.numpy()
     params = np.ascontiguousarray(params, dtype=np.float64)
     check_params(params, shapes, (out_w, out_h))
+    dev_labels, host_labels, T = pad_labels(labels, B)
 
-    dev_labels, host_labels, T = None, None, 0
-    if isinstance(labels, torch.Tensor):
-        if labels.dim() != 3 or labels.shape[0] != B or labels.shape[2] != 5:
-            raise ValueError("padded labels must be [B,T,5]")
-        T = int(labels.shape[1])
-        if labels.is_cuda:
-            dev_labels = labels.to(torch.float64).contiguous()
-        else:
-            host_labels = labels.to(torch.float64).numpy()
-    elif labels is not None:
-        if len(labels) != B:
-            raise ValueError("one label array per image")
-        rows = [np.asarray(l, dtype=np.float64).reshape(-1, 5) for l in labels]
-        T = max(r.shape[0] for r in rows)
-        host_labels = np.zeros((B, T, 5), dtype=np.float64)
-        for b, r in enumerate(rows):
-            host_labels[b, :r.shape[0]] = r
-
-    offsets, pos = [], 0
-    for H, W in shapes:
-        offsets.append(pos)
-        pos = _round_up(pos + H * W * 3)
-    src_bytes = pos
-    lib = _ffi.lib()
-    dev_index = torch.cuda.current_device()
-    # the gather path: every source already on this GPU, all of them views into one allocation (TrainBatches' arena) -- no pixel
-    # is copied, the kernels read the sources where they are and the colour copies take the batch's own bytes of workspace
-    gather = (all(t.is_cuda and t.device.index == dev_index and t.is_contiguous() for t in imgs)
-              and len({t.untyped_storage().data_ptr() for t in imgs}) == 1)
-
-    # staging layout: params | offsets | hw | labels | [gather: source offsets] or [images (each image 256-aligned)]
-    o_par = 0
-    o_off = _round_up(o_par + B * N_PARAMS * 8)
-    o_hw = _round_up(o_off + B * 8)
-    o_lab = _round_up(o_hw + B * 8)
-    o_img = _round_up(o_lab + (host_labels.nbytes if host_labels is not None else 0))
-    host_img_bytes = sum(H * W * 3 for (H, W), t in zip(shapes, imgs) if not t.is_cuda)
-    if gather:
-        total = upload = o_img + B * 8
-    else:
-        total = o_img + src_bytes
-        upload = total if host_img_bytes else o_img
-
-    staging = _staging.setdefault(dev_index, _Staging())
-    slot, buf = staging.take(upload)
-    host = buf.numpy()
-    host[o_par:o_par + params.nbytes].view(np.float64)[:] = params.reshape(-1)
-    host[o_off:o_off + B * 8].view(np.int64)[:] = offsets
-    host[o_hw:o_hw + B * 8].view(np.int32)[:] = np.asarray(shapes, dtype=np.int32).reshape(-1)
-    if host_labels is not None and host_labels.size:
-        host[o_lab:o_lab + host_labels.nbytes].view(np.float64)[:] = host_labels.reshape(-1)
-    if gather:
-        arena = imgs[0].untyped_storage()
-        host[o_img:o_img + B * 8].view(np.int64)[:] = [t.data_ptr() - arena.data_ptr() for t in imgs]
-    for off, t in zip(offsets, imgs):
-        if not t.is_cuda:
-            n = t.numel()
-            host[o_img + off:o_img + off + n] = t.reshape(-1).numpy()
-    dev = torch.empty(total, dtype=torch.uint8, device="cuda")
-    dev[:upload].copy_(buf[:upload], non_blocking=True)
-    staging.release(slot)
+    st = stage_batch(imgs, shapes, params, host_labels)
     counters["batches"] += 1
-    counters["upload_bytes"] += upload
-    if not gather:
-        for off, t in zip(offsets, imgs):
-            if t.is_cuda:
-                dev[o_img + off:o_img + off + t.numel()].copy_(t.reshape(-1))
-
-    base = dev.data_ptr()
+    lib = _ffi.lib()
     x = torch.empty((B, 3, out_h, out_w), dtype=torch.float32, device="cuda")
     target = torch.empty((B, max_labels, 5), dtype=torch.float32, device="cuda")
-    ws = torch.empty(max(1, lib.yv3_augment_workspace_bytes(src_bytes)), dtype=torch.uint8, device="cuda")
+    ws = torch.empty(max(1, lib.yv3_augment_workspace_bytes(st.span)), dtype=torch.uint8, device="cuda")
     status = torch.empty((2, B), dtype=torch.int32, device="cuda")
     s = _ffi.stream_ptr()
-    if gather:
-        _ffi.check(lib.yv3_augment_images_from(arena.data_ptr(), arena.nbytes(), base + o_img, base + o_off, src_bytes, base + o_hw,
-                                               base + o_par, B, x.data_ptr(), out_h, out_w, ws.data_ptr(), ws.numel(),
-                                               status.data_ptr(), s), "yv3_augment_images_from")
+    if st.gather:          # the colour copies take the batch's own bytes of workspace, not the span of the sources' allocation
+        _ffi.check(lib.yv3_augment_images_from(st.src, st.src_bytes, st.src_offsets, st.out_offsets, st.span, st.hw, st.records, B,
+                                               x.data_ptr(), out_h, out_w, ws.data_ptr(), ws.numel(), status.data_ptr(), s),
+                   "yv3_augment_images_from")
     else:
-        _ffi.check(lib.yv3_augment_images(base + o_img, src_bytes, base + o_off, base + o_hw, base + o_par, B,
+        _ffi.check(lib.yv3_augment_images(st.src, st.src_bytes, st.src_offsets, st.hw, st.records, B,
                                           x.data_ptr(), out_h, out_w, ws.data_ptr(), ws.numel(), status.data_ptr(), s),
                    "yv3_augment_images")
     if dev_labels is not None:
         lab_ptr = dev_labels.data_ptr() if T else None
     else:
-        lab_ptr = base + o_lab if T else None
-    _ffi.check(lib.yv3_augment_labels(lab_ptr, B, T, base + o_hw, base + o_par, target.data_ptr(), max_labels, out_h, out_w,
+        lab_ptr = st.labels if T else None
+    _ffi.check(lib.yv3_augment_labels(lab_ptr, B, T, st.hw, st.records, target.data_ptr(), max_labels, out_h, out_w,
                                       status.data_ptr() + 4 * B, s), "yv3_augment_labels")
     return x, target
 
@@ -329,7 +221,7 @@ def arena_admit(sizes, budget, start=0):
     is ever evicted); ``offsets[i]`` is None for one that does not fit -- a later, smaller one still may."""
     offsets, pos = [], int(start)
     for n in sizes:
-        off = _round_up(pos)
+        off = round_up(pos)
         if off + int(n) <= budget:
             offsets.append(off)
             pos = off + int(n)
@@ -430,7 +322,7 @@ class TrainBatches:
         """The ``cache_bytes`` that keeps every image of the list resident: the sum of their 256-aligned ``H * W * 3``, from the
         files' headers (``evaluate.image_size``)."""
         from . import evaluate
-        return sum(_round_up(w * h * 3) for w, h in (evaluate.image_size(p) for p in self.img_list))
+        return sum(round_up(w * h * 3) for w, h in (evaluate.image_size(p) for p in self.img_list))
 
     def resident_images(self):
         """How many images of the list are resident in the arena."""

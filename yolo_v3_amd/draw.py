@@ -10,12 +10,7 @@ import numpy as np
 import torch
 
 from . import _ffi
-
-_ALIGN = 256
-
-
-def _round_up(n, a=_ALIGN):
-    return (n + a - 1) // a * a
+from ._staging import round_up
 
 
 def palette(n):
@@ -130,7 +125,7 @@ def draw_boxes(images, rects, colors, tags=None, atlas=None, thickness=2):
         return images
     box_arr = (_ffi.DrawBox * first)(*boxes)
     n_img, n_box = ctypes.sizeof(recs), ctypes.sizeof(box_arr)
-    o_box = _round_up(n_img)
+    o_box = round_up(n_img)
     with torch.cuda.device(dev):
         staging = torch.empty(o_box + n_box, dtype=torch.uint8, pin_memory=True)
         host = staging.numpy()

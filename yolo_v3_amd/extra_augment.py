@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _ffi
+from ._staging import as_images, stage_batch
 
 MAX_STEPS, MAX_RADIUS = 6, 12
 OPS = {"GAUSS": 1, "AVERAGE": 2, "MEDIAN": 3, "SHARPEN": 4, "NOISE": 5, "ADD": 6, "MUL": 7, "CONTRAST": 8}
@@ -181,75 +182,20 @@ def extra_augment_batch(images, programs):
     new allocation -- so ``augment_batch`` reads them in place (its gather path).
 
     ``images``: list of uint8 RGB ``[H,W,3]`` numpy arrays or tensors (CPU or GPU), any sizes; ``programs``: one per image
-    (``sample_extra``), checked here (``check_programs``).  Programs, offsets, shapes and host images go up in one copy through
-    ``augment_batch``'s pinned staging buffers; GPU images are copied on the device -- unless all of them are contiguous views into
-    one allocation (``TrainBatches``' arena): then they are read where they are.  Six launches, ordered on the current stream; the
-    sources are not written."""
-    from . import augment as A
-    if not torch.cuda.is_available():
-        raise _ffi.Yv3Error("no GPU available: this package has no CPU path")
-    imgs = [A._as_image(im) for im in images]
+    (``sample_extra``), checked here (``check_programs``).  Programs, offsets, shapes and host images go up in one copy; GPU
+    images are copied on the device or, as views into one allocation (``TrainBatches``' arena), read where they are
+    (``_staging.stage_batch``).  Six launches, ordered on the current stream; the sources are not written."""
+    imgs, shapes = as_images(images)
     B = len(imgs)
-    if B == 0:
-        raise ValueError("empty batch")
-    shapes = [(int(t.shape[0]), int(t.shape[1])) for t in imgs]
     programs = list(programs)
     check_programs(programs, shapes)
-    packed = pack_programs(programs)
 
-    offsets, pos = [], 0
-    for H, W in shapes:
-        offsets.append(pos)
-        pos = A._round_up(pos + H * W * 3)
-    out_bytes = pos
+    st = stage_batch(imgs, shapes, pack_programs(programs))
     lib = _ffi.lib()
-    dev_index = torch.cuda.current_device()
-    gather = (all(t.is_cuda and t.device.index == dev_index and t.is_contiguous() for t in imgs)
-              and len({t.untyped_storage().data_ptr() for t in imgs}) == 1)
-
-    # staging layout: programs | out offsets | hw | [gather: source offsets] or [images (each image 256-aligned)]
-    o_prog = 0
-    o_off = A._round_up(o_prog + packed.nbytes)
-    o_hw = A._round_up(o_off + B * 8)
-    o_img = A._round_up(o_hw + B * 8)
-    host_img_bytes = sum(H * W * 3 for (H, W), t in zip(shapes, imgs) if not t.is_cuda)
-    if gather:
-        total = upload = o_img + B * 8
-    else:
-        total = o_img + out_bytes
-        upload = total if host_img_bytes else o_img
-
-    staging = A._staging.setdefault(dev_index, A._Staging())
-    slot, buf = staging.take(upload)
-    host = buf.numpy()
-    host[o_prog:o_prog + packed.nbytes] = packed.view(np.uint8).reshape(-1)
-    host[o_off:o_off + B * 8].view(np.int64)[:] = offsets
-    host[o_hw:o_hw + B * 8].view(np.int32)[:] = np.asarray(shapes, dtype=np.int32).reshape(-1)
-    if gather:
-        arena = imgs[0].untyped_storage()
-        host[o_img:o_img + B * 8].view(np.int64)[:] = [t.data_ptr() - arena.data_ptr() for t in imgs]
-    for off, t in zip(offsets, imgs):
-        if not t.is_cuda:
-            n = t.numel()
-            host[o_img + off:o_img + off + n] = t.reshape(-1).numpy()
-    dev = torch.empty(total, dtype=torch.uint8, device="cuda")
-    dev[:upload].copy_(buf[:upload], non_blocking=True)
-    staging.release(slot)
-    A.counters["upload_bytes"] += upload
-    if not gather:
-        for off, t in zip(offsets, imgs):
-            if t.is_cuda:
-                dev[o_img + off:o_img + off + t.numel()].copy_(t.reshape(-1))
-
-    base = dev.data_ptr()
-    out = torch.empty(out_bytes, dtype=torch.uint8, device="cuda")
-    ws = torch.empty(max(1, lib.yv3_extra_augment_workspace_bytes(out_bytes)), dtype=torch.uint8, device="cuda")
+    out = torch.empty(st.span, dtype=torch.uint8, device="cuda")
+    ws = torch.empty(max(1, lib.yv3_extra_augment_workspace_bytes(st.span)), dtype=torch.uint8, device="cuda")
     status = torch.empty(B, dtype=torch.int32, device="cuda")
-    if gather:
-        src, src_bytes, src_off = arena.data_ptr(), arena.nbytes(), base + o_img
-    else:
-        src, src_bytes, src_off = base + o_img, out_bytes, base + o_off
-    _ffi.check(lib.yv3_extra_augment(src, src_bytes, src_off, base + o_hw, base + o_prog, B, out.data_ptr(), out_bytes,
-                                     base + o_off, ws.data_ptr(), ws.numel(), status.data_ptr(), _ffi.stream_ptr()),
+    _ffi.check(lib.yv3_extra_augment(st.src, st.src_bytes, st.src_offsets, st.hw, st.records, B, out.data_ptr(), st.span,
+                                     st.out_offsets, ws.data_ptr(), ws.numel(), status.data_ptr(), _ffi.stream_ptr()),
                "yv3_extra_augment")
-    return [out[off:off + H * W * 3].view(H, W, 3) for off, (H, W) in zip(offsets, shapes)]
+    return [out[off:off + H * W * 3].view(H, W, 3) for off, (H, W) in zip(st.offsets, shapes)]

@@ -20,8 +20,8 @@ import numpy as np
 import torch
 
 from . import _ffi
+from ._staging import ALIGN, round_up
 
-_ALIGN = 256
 _INFO_BYTES = ctypes.sizeof(_ffi.JpegInfo)
 _PROG_BYTES = ctypes.sizeof(_ffi.JpegProg)
 
@@ -30,10 +30,6 @@ ENTROPY = {"serial": 0, "parallel": 1}                    # enum YV3_JPEG_ENTROP
 # for measurements and tests; "launches": the kernels the calls launched, as the library counts them where it launches them
 # (yv3_jpeg_launch_count before and after the call); "prog_images": progressive images sent to the device
 counters = {"calls": 0, "uploads": 0, "upload_bytes": 0, "status_reads": 0, "fallbacks": 0, "launches": 0, "prog_images": 0}
-
-
-def _round_up(n, a=_ALIGN):
-    return (n + a - 1) // a * a
 
 
 def read_bytes(source):
@@ -233,29 +229,29 @@ def submit(sources, device=None, stream=None, dst=None, entropy="serial", progre
     # layout of the allocation: infos | src offsets | dst offsets | status | [progressive records | their indices] | file bytes |
     # PIL pixels || decoded images
     o_info = 0
-    o_soff = _round_up(o_info + B * _INFO_BYTES)
-    o_doff = _round_up(o_soff + B * 8)
-    o_stat = _round_up(o_doff + B * 8)
-    o_prog = _round_up(o_stat + B * (8 if parallel else 4))  # parallel: [B] hand-over counts behind the statuses
-    o_pof = _round_up(o_prog + P * _PROG_BYTES)
-    o_src = _round_up(o_pof + (B * 4 if P else 0))           # (without a progressive image: the layout of a baseline batch)
+    o_soff = round_up(o_info + B * _INFO_BYTES)
+    o_doff = round_up(o_soff + B * 8)
+    o_stat = round_up(o_doff + B * 8)
+    o_prog = round_up(o_stat + B * (8 if parallel else 4))  # parallel: [B] hand-over counts behind the statuses
+    o_pof = round_up(o_prog + P * _PROG_BYTES)
+    o_src = round_up(o_pof + (B * 4 if P else 0))           # (without a progressive image: the layout of a baseline batch)
     src_off, pos = [], o_src
     for i in gpu:
         src_off.append(pos - o_src)
         pos += len(items[i].data)                           # files are packed back to back: any byte offset will do
     src_bytes = max(pos - o_src, 1)
-    pos = _round_up(pos)
+    pos = round_up(pos)
     px_off = {}
     for i in host_px:
         if dst is None:
             px_off[i] = pos
-            pos = _round_up(pos + items[i].nbytes)
+            pos = round_up(pos + items[i].nbytes)
     upload = pos
     own_off = {}
     if dst is None:
         for i in gpu:
             own_off[i] = pos
-            pos = _round_up(pos + items[i].nbytes)
+            pos = round_up(pos + items[i].nbytes)
     total = max(pos, 1)
 
     with torch.cuda.device(dev), torch.cuda.stream(stream):
@@ -391,12 +387,12 @@ def encode_launch(tensors, qualities, subsamplings, out, offsets, capacities, ws
                                     ncomp=ncomp, subsampling=int(subsamplings[i]), quality=int(qualities[i]))
     need = lib.yv3_jpeg_encode_workspace_bytes(recs, B)
     with torch.cuda.device(dev), torch.cuda.stream(stream):
-        o_len = _round_up(B * _ENC_BYTES)
+        o_len = round_up(B * _ENC_BYTES)
         staging = torch.empty(o_len, dtype=torch.uint8, pin_memory=True)
         staging.numpy()[:B * _ENC_BYTES] = np.frombuffer(recs, dtype=np.uint8, count=B * _ENC_BYTES)
         meta = torch.empty(o_len + 8 * B, dtype=torch.uint8, device=dev)           # records | lengths [B] | statuses [B]
         meta[:o_len].copy_(staging, non_blocking=True)
-        if ws is None or ws.numel() < need or ws.device != dev or ws.data_ptr() % _ALIGN:
+        if ws is None or ws.numel() < need or ws.device != dev or ws.data_ptr() % ALIGN:
             ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
         base = meta.data_ptr()
         desc = _ffi.JpegEncDesc(images=base, images_host=ctypes.addressof(recs), out_len=base + o_len, status=base + o_len + 4 * B, B=B)
@@ -470,7 +466,7 @@ def submit_encode(images, quality=75, subsampling="4:2:0", device=None, stream=N
             cap = encode_bound(t.shape[1], t.shape[0], 1 if t.dim() == 2 else 3, s)
             offsets.append(pos)
             caps.append(cap)
-            pos = _round_up(pos + cap)
+            pos = round_up(pos + cap)
         out = torch.empty(pos, dtype=torch.uint8, device=dev)
         lengths, statuses, keep = encode_launch(tensors, qualities, [SUBSAMPLING[s] for s in subs], out, offsets, caps, stream=stream)
         both_host = torch.empty(2 * B, dtype=torch.int32, pin_memory=True)
